@@ -134,6 +134,21 @@ def note(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each device tensor as out_dir/<name>.npy (float32 stays float32, anything else becomes float64)."""
+    host = {n: t.detach().cpu().numpy() for n, t in arrays.items()}
+    host = {n: a if a.dtype == np.float32 else a.astype(np.float64) for n, a in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in host.items():
+        np.save(os.path.join(out_dir, f"{n}.npy"), a)
+    note(f"outputs of the last timed step: {', '.join(f'{n}{list(a.shape)}' for n, a in host.items())} -> {out_dir}")
+
+
 def run_steps(task, X, Wt, B, steps, warmup, tag, world, dev, max_batches=8, preheat_ms=0.0):
     """W untimed + EXACTLY K timed train steps of the product's own step path on this rank's resident rows, B frames per rank
     per step.  As EigenFunctionTask.train() replays one hipGraph per EPOCH (all its static batches), the steps run in chunks of
@@ -171,6 +186,11 @@ def run_steps(task, X, Wt, B, steps, warmup, tag, world, dev, max_batches=8, pre
         step(i)
     run_steps.preheat_steps = 0
     if preheat_ms > 0:
+        # the preheat's step count follows the GPU's speed: the state it trains into is put back afterwards, so that the timed
+        # steps start from the same parameters and Adam moments in every run with the same arguments (--dump-outputs compares them)
+        opt = task.optimizer
+        state = [task._flat.theta, opt.exp_avg, opt.exp_avg_sq, opt.step_count]
+        saved = [t.clone() for t in state]
         barrier()
         t0 = time.perf_counter()
         chunk()
@@ -183,6 +203,9 @@ def run_steps(task, X, Wt, B, steps, warmup, tag, world, dev, max_batches=8, pre
             n_pre = int(t)
         for _ in range(n_pre):
             chunk()
+        for t, s in zip(state, saved):
+            t.copy_(s)
+        task._flat.repack()
         # (the first graph launch after a long queue has drained costs the host 0.1-0.4 ms of clean-up - tools/timing_probe.py -
         # which must not land inside a 1.5 ms timed region: drain, replay once more, drain)
         barrier()
@@ -254,7 +277,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other global batches, K1 rooflines)")
     ap.add_argument("--workload", choices=["c3", "c5", "c2", "regae", "transfer"], default="c3",
                     help="c3 = the benchmark line; c5 = config-5 shape, c2 = config-2 AutoEncoderTask (extra measurements)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss vector) and left in the model (parameters) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.workload != "c3":
+        ap.error("--dump-outputs is implemented for the benchmark line (--workload c3)")
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args.gpus)
     if args.workload == "transfer":
@@ -314,6 +343,9 @@ def main():
     preheat_steps = run_steps.preheat_steps
     graphs = task._use_graphs
     final_loss = float(loss_vec[0])
+    if args.dump_outputs is not None and rank == 0:   # (before the per-call pass below trains on)
+        dump_outputs(args.dump_outputs, loss_vector=loss_vec,
+                     parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
 
     # ---- per-kernel durations: HIP events around every C-ABI call over a second, eager pass of the same steps (not part
     # of `value`); the GPU is parked while the host queues each step, so the events bracket back-to-back executions
