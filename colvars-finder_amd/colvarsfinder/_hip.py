@@ -25,7 +25,7 @@ def ef_widths(n_hidden):
 
 
 FEAT_ANGLE, FEAT_BOND, FEAT_DIHEDRAL, FEAT_POSITION = 0, 1, 2, 3
-PP_IDENTITY, PP_ALIGN = 0, 1
+PP_IDENTITY, PP_ALIGN, PP_FACTORED = 0, 1, 2
 PP_ALIGN_CONTIG, PP_PURE_POSITION, PP_SLOT_BATCHED = 1, 2, 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

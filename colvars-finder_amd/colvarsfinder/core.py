@@ -40,7 +40,7 @@ import ctypes
 
 from . import _dist, _hip
 from .nn import AutoEncoder, EigenFunctions, RegAutoEncoder, RegModel, mlp_layout  # noqa: F401
-from .pp import AlignFeatureLayer, identity_desc
+from .pp import AlignFeatureLayer, FactoredMetric, identity_desc, module_features
 
 try:  # logging sink of the reference (core.py:50,143); optional here
     from tensorboardX import SummaryWriter as _SummaryWriter
@@ -588,9 +588,6 @@ class EigenFunctionTask(TrainingTask):
         self._traj_host = _HostFrames(traj_obj.trajectory)
         self._n_frames = int(self._traj_host.shape[0])
         self._sharded = _dist.world() > 1
-        self._traj = None if self._sharded else _hip.upload_f32(self._traj_host.all(), self.device)
-        self._weights = torch.as_tensor(np.asarray(traj_obj.weights)).to(device=self.device, dtype=torch.float32).contiguous()
-        self.resident_bytes = 0 if self._sharded else self._traj.numel() * 4    # frames held in HBM (train() adds its gathers)
         self.tot_dim = int(np.prod(self._traj_host.shape[1:]))
         self._beta = beta
         if self.lag_idx == 0:
@@ -600,8 +597,29 @@ class EigenFunctionTask(TrainingTask):
                 self._diag_coeff = diag_coeff.detach().to(device=self.device, dtype=torch.float32).contiguous()
             else:
                 self._diag_coeff = torch.ones(self.tot_dim, device=self.device, dtype=torch.float32)
-
-        self._pp = self._pp_desc(self.tot_dim)
+        # pp_layer may be ANY torch module (core.py:65,122,403): `_frames` maps the trajectory's frames to what the kernels take -
+        # the frames themselves (Identity, AlignFeatureLayer), the feature rows r(x) (transfer operator: run on identity_desc) or,
+        # in generator mode, one record [r(x) | L] per frame with L L^T = J A J^T (pp.FactoredMetric, CVF_PP_FACTORED)
+        self._foreign_pp = not isinstance(self.preprocessing_layer, (torch.nn.Identity, AlignFeatureLayer))
+        self._fm = None
+        if self._foreign_pp:
+            if self._sharded:
+                raise NotImplementedError("EigenFunctionTask with a preprocessing module other than Identity / AlignFeatureLayer "
+                                          "runs in single-process jobs only (the per-rank record building is not there)")
+            probe = self._traj_host.rows(np.arange(min(2, self._n_frames)))
+            if self.lag_idx == 0:
+                self._fm = FactoredMetric(self.preprocessing_layer, self._traj_host.shape[1:], self._diag_coeff, self.device, probe)
+                self._pp = self._fm.desc()
+                self._check_record_memory(self._fm.record_bytes(self._n_frames))
+            else:
+                with torch.no_grad():
+                    y = self.preprocessing_layer(torch.as_tensor(np.asarray(probe)).to(device=self.device, dtype=torch.float32))
+                self._pp = identity_desc(int(y.reshape(y.shape[0], -1).shape[1]))
+        else:
+            self._pp = self._pp_desc(self.tot_dim)
+        self._traj = None if self._sharded else self._frames(self._traj_host.all())
+        self._weights = torch.as_tensor(np.asarray(traj_obj.weights)).to(device=self.device, dtype=torch.float32).contiguous()
+        self.resident_bytes = 0 if self._sharded else self._traj.numel() * 4    # frames (or records) held in HBM (train() adds its gathers)
         assert self._pp.d_r == self._flat.desc.dims[0], \
             f'preprocessing layer emits {self._pp.d_r} features but the networks take {self._flat.desc.dims[0]}'
         cfg = _hip.EFCfg()
@@ -652,6 +670,29 @@ class EigenFunctionTask(TrainingTask):
 
     def reg_model(self):
         return None
+
+    # share of the free device memory the resident records and train()'s gathered copy of them may take
+    RECORD_MEMORY_FRACTION = 0.8
+
+    def _check_record_memory(self, nbytes):
+        """Records of every frame stay resident and train() gathers one epoch's copy of them: both must fit."""
+        free, _ = torch.cuda.mem_get_info(self.device)
+        need = 2 * int(nbytes)
+        if need > self.RECORD_MEMORY_FRACTION * free:
+            raise NotImplementedError(
+                f"EigenFunctionTask (generator mode) with a {type(self.preprocessing_layer).__name__} preprocessing module: the "
+                f"per-frame records take {int(nbytes)} bytes, {need} with train()'s gathered copy, more than "
+                f"{self.RECORD_MEMORY_FRACTION:.0%} of the {int(free)} bytes free on the device. Use lag_tau > 0 (features only) or "
+                "fewer features.")
+
+    def _frames(self, X):
+        """What the kernels take for the frames ``X`` (host or device, ``[B, *frame_shape]``): the frames themselves, or - with a
+        foreign preprocessing module - records (generator mode) or feature rows (transfer operator), on the device."""
+        if not self._foreign_pp:
+            return _hip.upload_f32(X, self.device)
+        if self._fm is not None:
+            return self._fm.records(X)
+        return module_features(self.preprocessing_layer, X, self._pp.d_r, self.device)
 
     # ---------------------------------------------------------------- GPU step
     def _workspace(self, B):
@@ -916,6 +957,9 @@ class EigenFunctionTask(TrainingTask):
         gradient of ``loss`` is obtained with :meth:`backward` (there is no autograd graph)."""
         X, weight = self._dev(X), self._dev(weight)
         X_lagged, weight_lagged = self._dev(X_lagged), self._dev(weight_lagged)
+        if self._foreign_pp:   # coordinates, as in the reference: this batch's records / features, then the same kernels
+            X = self._frames(X)
+            X_lagged = None if X_lagged is None else self._frames(X_lagged)
         self._flat.repack()  # the caller may have modified the parameters through the nn.Module
         ws = self._forward(X, weight, X_lagged, weight_lagged)
         self._last = (ws, weight, weight_lagged)
@@ -1507,6 +1551,8 @@ class _RegGenerator:
 
         if isinstance(task.preprocessing_layer, AlignFeatureLayer):   # (a frame the alignment accepts: the reference itself)
             _Tok.trajectory = np.zeros_like(tok) + np.random.RandomState(0).normal(size=tok.shape[1:]).astype(np.float32)
+        elif task._foreign_pp:   # (frames the module is defined on: the trajectory's own)
+            _Tok.trajectory = np.asarray(task._traj_host[np.arange(4) % len(task._traj_host)], dtype=np.float32)
         g0, g1 = float(task.gamma[0]), float(task.gamma[1])
         import tempfile
         # (its own scratch log directory: a second SummaryWriter must not open event files in the user's model_path)
@@ -1625,7 +1671,20 @@ class RegAutoEncoderTask(TrainingTask):
         traj = _HostFrames(traj_obj.trajectory).all()
         self.tot_dim = int(np.prod(traj.shape[1:]))
         self._weights = torch.as_tensor(np.asarray(traj_obj.weights)).to(device=self.device, dtype=torch.float32).contiguous()
-        self._pp = self._pp_desc(self.tot_dim)
+        # pp_layer may be any torch module (core.py:65,122,635): its feature trajectory is computed once with torch
+        self._foreign_pp = not isinstance(self.preprocessing_layer, (torch.nn.Identity, AlignFeatureLayer))
+        if self._foreign_pp:
+            if _dist.world() > 1:
+                raise NotImplementedError("RegAutoEncoderTask with a preprocessing module other than Identity / AlignFeatureLayer "
+                                          "runs in single-process jobs only")
+            if self.eta[0] > self._eps:
+                raise NotImplementedError("RegAutoEncoderTask on MI355X: the gradient-norm penalty eta[0] needs features = coordinates "
+                                          "(Identity or AlignFeatureLayer), not a foreign preprocessing module")
+            with torch.no_grad():
+                y = self.preprocessing_layer(torch.as_tensor(traj[:1]).to(device=self.device, dtype=torch.float32))
+            self._pp = types.SimpleNamespace(d_r=int(y.reshape(1, -1).shape[1]))
+        else:
+            self._pp = self._pp_desc(self.tot_dim)
         self._feature_traj = self._features(torch.as_tensor(traj))
         d = self._flat.desc
         assert self._pp.d_r == d.dims[0] and d.dims[d.n_layers] == d.dims[0] + self.num_reg, \
@@ -1649,7 +1708,8 @@ class RegAutoEncoderTask(TrainingTask):
         # generator-mode regulariser (lag_tau_reg = 0): needs the coordinates themselves (its derivative runs through r(x))
         self._traj_host = traj
         self._gen = _RegGenerator(self, beta) if self._use_reg and self.lag_idx == 0 else None
-        self._traj = _hip.upload_f32(traj, self.device) if self._gen is not None else None
+        # (with a foreign module the inner task takes its records [r | L] instead: pp.FactoredMetric, CVF_PP_FACTORED)
+        self._traj = None if self._gen is None else self._gen.inner._frames(traj)
 
     # -- the base class builds the flat buffer from mlp_layout(); this model needs the side-by-side chain
     def init_model_and_optimizer(self):
@@ -1664,6 +1724,8 @@ class RegAutoEncoderTask(TrainingTask):
         self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
 
     def _features(self, X):
+        if self._foreign_pp:
+            return module_features(self.preprocessing_layer, torch.as_tensor(X).detach(), self._pp.d_r, self.device)
         X = _hip.upload_f32(torch.as_tensor(X).detach(), self.device)
         n = X.shape[0]
         out = torch.empty(n, self._pp.d_r, device=self.device, dtype=torch.float32)
@@ -1811,7 +1873,7 @@ class RegAutoEncoderTask(TrainingTask):
         assert self.num_reg > 0, 'needs regularisers'
         if self.lag_idx == 0:   # generator mode (core.py:990,1008-1022): X_lagged / weight_lagged are not used
             assert self._gen is not None, 'generator-mode regulariser needs gamma at construction'
-            Xd = _hip.upload_f32(torch.as_tensor(X).detach(), self.device)
+            Xd = self._gen.inner._frames(torch.as_tensor(X).detach())
             lv = self._gen.forward(Xd, self._dev(weight), False)
             dt, K = torch.get_default_dtype(), self.num_reg
             return lv[3:3 + K].to(dt).cpu(), lv[1].to(dt), lv[2].to(dt), lv[3 + K:3 + 2 * K].cpu().to(torch.long).numpy()
@@ -1833,6 +1895,8 @@ class RegAutoEncoderTask(TrainingTask):
 
     def reg_enc_grad_loss(self, X, weight):
         """core.py:887-910 (forward value)."""
+        if self._foreign_pp:
+            raise NotImplementedError("reg_enc_grad_loss needs features = coordinates (Identity or AlignFeatureLayer)")
         if self._enc_grad is None:
             self._enc_grad = _EncGradPenalty(self)
         return self._enc_grad.run(self._features(X), self._dev(weight), 1.0, False).to(torch.get_default_dtype())

@@ -14,6 +14,8 @@ coordinates (atom-major), ``bond`` -> distance, ``angle`` -> cos (or value), ``d
 (cos, sin) (or value).
 """
 
+import copy
+
 import numpy as np
 import torch
 
@@ -291,3 +293,134 @@ def identity_desc(n_coord):
     d = _hip.PPDesc()
     d.mode, d.n_coord, d.d_r = _hip.PP_IDENTITY, int(n_coord), int(n_coord)
     return d
+
+
+def factored_desc(d_r, rho):
+    """Descriptor of CVF_PP_FACTORED records ``[r (d_r) | L (d_r x rho)]`` (include/cvf.h)."""
+    d = _hip.PPDesc()
+    d.mode, d.n_coord, d.d_r = _hip.PP_FACTORED, int(d_r) * (1 + int(rho)), int(d_r)
+    return d
+
+
+class FactoredMetric:
+    """Per-frame records of an arbitrary preprocessing module for the generator loss (include/cvf.h, CVF_PP_FACTORED).
+
+    The reference differentiates through ``pp_layer`` at every step (core.py:418-426).  Neither the module (never trained:
+    the optimiser takes ``model.parameters()`` only, core.py:164-166) nor the frames change, so everything the step needs from
+    the module is computed once per frame: the features ``r(x)`` and a factor ``L`` of the feature-space metric
+    ``M(x) = J A J^T`` (``J = dr/dx``, ``d_r x n``; ``A = diag(diag_coeff)``), ``M = L L^T``:
+
+    * ``n <= d_r``: ``L = J diag(sqrt(a))`` (``rho = n`` columns, exact);
+    * ``n > d_r``: ``M`` in fp64, ``L = V diag(sqrt(max(lambda, 0)))`` from ``eigh(M)`` (``rho = d_r``).
+
+    ``J`` is taken on a float64 deep copy of the module when the copy runs in fp64 (else on an fp32 copy); ``M`` and ``L`` are
+    formed in fp64 and stored fp32.  The caller's module is never modified.
+
+    Args:
+        module: any ``torch.nn.Module`` mapping ``[B, *frame_shape]`` to ``[B, d_r]``, frame by frame.
+        frame_shape: shape of one frame (``n = prod(frame_shape)`` floats, the reference's ``tot_dim``).
+        diag_coeff: ``[n]`` non-negative coefficients, or None (ones).
+        device: where the records are built and kept.
+        probe: two or more frames for the checks (frame-locality of the module, output shape).
+    """
+
+    def __init__(self, module, frame_shape, diag_coeff, device, probe):
+        self.frame_shape = tuple(int(v) for v in frame_shape)
+        self.n = int(np.prod(self.frame_shape))
+        self.device = torch.device(device)
+        if diag_coeff is None:
+            a = torch.ones(self.n, dtype=torch.float64)
+        else:
+            a = torch.as_tensor(diag_coeff).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+        if a.numel() != self.n:
+            raise ValueError(f"diag_coeff has {a.numel()} entries, the frames have {self.n} coordinates")
+        if bool((a < 0).any()) or not bool(torch.isfinite(a).all()):
+            raise ValueError("diag_coeff entries must be finite and >= 0 (A = diag(diag_coeff) is a metric)")
+        self._sqrt_a = a.sqrt().to(self.device)
+        self._a = a.to(self.device)
+        X0 = torch.as_tensor(np.asarray(probe) if not torch.is_tensor(probe) else probe).to(self.device)
+        if X0.shape[0] == 1:
+            X0 = torch.cat([X0, X0 + 0.01], 0)
+        X0 = X0[:2].reshape((2,) + self.frame_shape)
+        try:   # fp64 when the module runs in fp64 (parameters, buffers and operators), else fp32
+            self.module, self.dtype = copy.deepcopy(module).to(torch.float64), torch.float64
+            X = X0.to(torch.float64)
+            with torch.no_grad():
+                y = self.module(X)
+        except Exception:
+            self.module, self.dtype = copy.deepcopy(module).to(torch.float32), torch.float32
+            X = X0.to(torch.float32)
+            with torch.no_grad():
+                y = self.module(X)
+        if y.dim() != 2 or y.shape[0] != 2:
+            raise ValueError(f"the preprocessing module must map [B, {', '.join(map(str, self.frame_shape))}] to [B, d_r]; "
+                             f"it returned shape {tuple(y.shape)} for two frames (1-D or 3-D outputs are not taken)")
+        self.d_r = int(y.shape[1])
+        self.rho = min(self.n, self.d_r)
+        self.width = self.d_r * (1 + self.rho)
+        # frame-locality: the reference's autograd.grad(y.sum(), X) (core.py:418-424) silently assumes that frame b's features
+        # depend on frame b alone; a module that mixes frames (batch statistics, say) has no per-frame metric
+        Jp = torch.autograd.functional.jacobian(lambda x: self.module(x), X).reshape(2, self.d_r, 2, self.n)
+        if not bool(torch.isfinite(Jp).all()):
+            raise ValueError("the preprocessing module's Jacobian is not finite on the first two frames of the trajectory")
+        if bool((Jp[0, :, 1] != 0).any()) or bool((Jp[1, :, 0] != 0).any()):
+            raise ValueError("the preprocessing module is not frame-local: features of one frame depend on another frame "
+                             "of the batch (e.g. batch statistics); the generator loss needs a per-frame Jacobian")
+
+    def record_bytes(self, n_frames):
+        return int(n_frames) * self.width * 4
+
+    def _chunk(self):
+        per = 8 * self.d_r * (self.n + self.d_r) * 3 + 8 * self.n * 4   # J, M / L and their temporaries per frame, fp64
+        return max(1, min(8192, (256 << 20) // per))
+
+    def jacobian(self, X):
+        """``(r, J)`` of the frames ``X`` ``[B, *frame_shape]`` in the builder's precision: ``[B, d_r]``, ``[B, d_r, n]``."""
+        X = X.detach().to(device=self.device, dtype=self.dtype).reshape((-1,) + self.frame_shape).requires_grad_(True)
+        with torch.enable_grad():
+            y = self.module(X)
+            J = torch.empty(X.shape[0], self.d_r, self.n, device=self.device, dtype=self.dtype)
+            for i in range(self.d_r):
+                g, = torch.autograd.grad(y[:, i].sum(), X, retain_graph=i + 1 < self.d_r, allow_unused=True)
+                J[:, i] = 0.0 if g is None else g.reshape(X.shape[0], self.n)
+        return y.detach(), J
+
+    def factor(self, J):
+        """``L`` (fp64, ``[B, d_r, rho]``) with ``L L^T = J A J^T``."""
+        J = J.to(torch.float64)
+        if self.n <= self.d_r:
+            return J * self._sqrt_a
+        M = torch.einsum("bin,n,bjn->bij", J, self._a, J)
+        M = 0.5 * (M + M.transpose(1, 2))
+        lam, V = torch.linalg.eigh(M)
+        return V * lam.clamp_min(0.0).sqrt().unsqueeze(1)
+
+    def records(self, frames, out=None):
+        """fp32 records ``[B, d_r * (1 + rho)]`` of the frames (host or device array ``[B, *frame_shape]``), on the device,
+        built ``_chunk()`` frames at a time (``out``: a preallocated destination)."""
+        frames = torch.as_tensor(np.asarray(frames) if not torch.is_tensor(frames) else frames)
+        B = frames.shape[0]
+        if out is None:
+            out = torch.empty(B, self.width, device=self.device, dtype=torch.float32)
+        c = self._chunk()
+        for s0 in range(0, B, c):
+            r, J = self.jacobian(frames[s0:s0 + c].to(self.device))
+            L = self.factor(J)
+            out[s0:s0 + c, :self.d_r] = r.to(torch.float32)
+            out[s0:s0 + c, self.d_r:] = L.reshape(L.shape[0], -1).to(torch.float32)
+        return out
+
+    def desc(self):
+        return factored_desc(self.d_r, self.rho)
+
+
+def module_features(module, frames, d_r, device, chunk=65536):
+    """``module(frames)`` as fp32 rows ``[B, d_r]`` on the device, in chunks, without autograd (the transfer-operator loss and the
+    autoencoders need the features only)."""
+    frames = torch.as_tensor(np.asarray(frames) if not torch.is_tensor(frames) else frames)
+    B = frames.shape[0]
+    out = torch.empty(B, d_r, device=device, dtype=torch.float32)
+    with torch.no_grad():
+        for s0 in range(0, B, chunk):
+            out[s0:s0 + chunk] = module(frames[s0:s0 + chunk].to(device=device, dtype=torch.float32)).reshape(-1, d_r)
+    return out

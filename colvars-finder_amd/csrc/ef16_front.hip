@@ -697,6 +697,7 @@ extern "C" int cvf_ef16_front(const cvf_mlp_desc* mlp, const float* theta, const
                               const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, float* y_tiled, float* saved,
                               float* q_tiled, float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats,
                               double* loss_vec, double* coef, void* stream) {
+  CVF_REQUIRE(pp && pp->mode != CVF_PP_FACTORED, "cvf_ef16_front: takes coordinates, not CVF_PP_FACTORED records");
   CVF_REQUIRE(cvf_ef16_supported(mlp, pp), "cvf_ef16_front: shape not covered (cvf_ef16_supported() == 0)");
   CVF_REQUIRE(theta && packed && feat_tiled && x && a && y_tiled && saved && q_tiled && e_tiled && cfg && w && scratch && B > 0,
               "cvf_ef16_front: bad argument");
@@ -755,6 +756,7 @@ extern "C" int cvf_ef16_front(const cvf_mlp_desc* mlp, const float* theta, const
 static int ef16_front_transfer_impl(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
                                     const cvf_pp_desc* pp, const float* x, const float* x_lag, int64_t B, float* y_tiled, float* saved,
                                     const float* w, const float* w_lag, double* rows_out, void* stream, const char* what) {
+  CVF_REQUIRE(pp && pp->mode != CVF_PP_FACTORED, "%s: takes coordinates, not CVF_PP_FACTORED records", what);
   CVF_REQUIRE(cvf_ef16_supported(mlp, pp), "%s: shape not covered (cvf_ef16_supported() == 0)", what);
   CVF_REQUIRE(theta && packed && feat_tiled && x && x_lag && y_tiled && saved && B > 0, "%s: bad argument", what);
   int H, NH;

@@ -1740,6 +1740,8 @@ static int fwd_metric_launch(bool with_k1, const cvf_mlp_desc* mlp, const float*
                              const cvf_pp_desc* pp, const float* x, int64_t B, float* aux_tiled, const float* a, float* y_tiled,
                              float* saved, float* q_tiled, float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch,
                              double* stats, double* loss_vec, double* coef, void* stream) {
+  CVF_REQUIRE(pp && pp->mode != CVF_PP_FACTORED, "cvf_ef_[align_]fwd_metric_stats: takes coordinates, not CVF_PP_FACTORED records "
+              "(run cvf_ef_mlp_fwd and cvf_metric_apply_stats)");
   CVF_REQUIRE(cvf_ef_fwd_metric_supported(mlp, pp), "cvf_ef_fwd_metric_stats: shape not covered (cvf_ef_fwd_metric_supported() == 0)");
   CVF_REQUIRE(theta && packed && feat_tiled && x && a && y_tiled && q_tiled && e_tiled && cfg && w && scratch && B > 0,
               "cvf_ef_fwd_metric_stats: bad argument");
@@ -1793,6 +1795,8 @@ extern "C" int cvf_ef_fwd_metric_stats(const cvf_mlp_desc* mlp, const float* the
 extern "C" int cvf_ef_align_fwd(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
                                 const cvf_pp_desc* pp, const float* x, const float* x_lag, int64_t B, float* y_tiled, float* saved,
                                 void* stream) {
+  CVF_REQUIRE(pp && pp->mode != CVF_PP_FACTORED, "cvf_ef_align_fwd: takes coordinates, not CVF_PP_FACTORED records "
+              "(run cvf_align_feature_fwd and cvf_ef_mlp_fwd)");
   CVF_REQUIRE(cvf_ef_align_fwd_metric_supported(mlp, pp), "cvf_ef_align_fwd: shape not covered (cvf_ef_align_fwd_metric_supported() == 0)");
   CVF_REQUIRE(theta && packed && feat_tiled && x && y_tiled && B > 0, "cvf_ef_align_fwd: bad argument");
   int H, NH;
@@ -1817,7 +1821,8 @@ extern "C" int cvf_ef_align_fwd(const cvf_mlp_desc* mlp, const float* theta, con
 // Rows of per-tile partial sums the fused launches leave in `scratch` (0: the batch is too large for the fused sums and
 // the launch must be given `stats` so that it runs the two-stage reduction itself), and the launch that adds them.
 extern "C" int64_t cvf_ef_fused_stats_rows(const cvf_mlp_desc* mlp, const cvf_pp_desc* pp, int64_t B, int with_align) {
-  (void)mlp; (void)pp; (void)with_align;   // one row per tile for every fused launch at present
+  (void)mlp; (void)with_align;   // one row per tile for every fused launch at present
+  if (pp && pp->mode == CVF_PP_FACTORED) return 0;   // (no fused launch takes records)
   return cvf_ntiles(B) <= kFuseMaxTiles ? cvf_ntiles(B) : 0;
 }
 extern "C" int cvf_ef_stats_finish_rows(const cvf_ef_cfg* cfg, int64_t n_rows, const double* partial, double* stats,

@@ -724,6 +724,9 @@ __global__ __launch_bounds__(64) void metric_identity_kernel(int d, const float*
 
 int cvf_k1_large_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows,
                         float* aux_tiled, float* slot_xyz, hipStream_t s);
+int cvf_factor_feature_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows, hipStream_t s);
+int cvf_metric_factor_launch(const cvf_pp_desc* pp, const float* x, int64_t B, int k, const float* g_tiled, float* q_tiled,
+                             float* e_tiled, hipStream_t s);
 size_t cvf_k1_large_scratch_bytes(const cvf_pp_desc* pp, int64_t B);
 size_t cvf_metric_large_lds(const cvf_pp_desc* pp);
 int cvf_ef_stats_finish(const cvf_ef_cfg* cfg, int n_rows, const double* partial, double* stats, double* loss_vec, double* coef,
@@ -755,6 +758,7 @@ extern "C" int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int6
     hipLaunchKernelGGL(k1_identity_kernel, dim3((unsigned)T), dim3(64), 0, s, pp->n_coord, x, B, feat_tiled, feat_rows);
     return cvf_check_launch("k1_identity_kernel");
   }
+  if (pp->mode == CVF_PP_FACTORED) return cvf_factor_feature_launch(pp, x, B, feat_tiled, feat_rows, s);   // (csrc/metric_factor.hip)
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
               "cvf_align_feature_fwd: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
@@ -845,7 +849,7 @@ static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, c
                              const double* dense, const MetricFuse& fuse, bool* fused, void* stream, int* major_rows = nullptr) {
   if (fused) *fused = false;
   if (major_rows) *major_rows = 0;   // > 0: the launch left that many rows of [statistic][row] partial sums (large molecules)
-  CVF_REQUIRE(pp && a && g_tiled && q_tiled && e_tiled && B > 0 && k >= 1 && k <= CVF_MAX_NETS,
+  CVF_REQUIRE(pp && (a || pp->mode == CVF_PP_FACTORED) && g_tiled && q_tiled && e_tiled && B > 0 && k >= 1 && k <= CVF_MAX_NETS,
               "cvf_metric_apply: bad argument (B=%lld k=%d)", (long long)B, k);
   const int64_t T = cvf_ntiles(B);
   hipStream_t s = (hipStream_t)stream;
@@ -854,6 +858,9 @@ static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, c
                        e_tiled);
     return cvf_check_launch("metric_identity_kernel");
   }
+  if (pp->mode == CVF_PP_FACTORED)   // t = L^T g, q = L t, E = |t|^2 from the records (csrc/metric_factor.hip); stats: two-stage path
+    return cvf_metric_factor_launch(pp, x, B, k, g_tiled, q_tiled, e_tiled, s);
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(aux_tiled, "cvf_metric_apply: align mode needs aux");
   CVF_REQUIRE(!pp->align_w || (pp->flags == 0 && pp->n_coord <= kLanePerFrameMaxCoord),
               "cvf_metric_apply: per-atom alignment weights need flags == 0 and at most %d coordinates per frame",

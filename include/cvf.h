@@ -35,7 +35,13 @@ extern "C" {
 /* feature record types: molann's ids (examples/dipeptide/main.ipynb:306-307 prints
  * "position ... type_id 3") */
 enum { CVF_FEAT_ANGLE = 0, CVF_FEAT_BOND = 1, CVF_FEAT_DIHEDRAL = 2, CVF_FEAT_POSITION = 3 };
-enum { CVF_PP_IDENTITY = 0, CVF_PP_ALIGN = 1 };
+/* CVF_PP_FACTORED: r(x) is any torch module, evaluated on the host once per frame (colvarsfinder/pp.py: FactoredMetric).  A
+ * "frame" is then one fp32 RECORD [r(x) (d_r) | L (d_r x rho, row-major)] with L L^T = J A J^T (J = dr/dx, A = diag(diag_coeff)):
+ * n_coord = d_r * (1 + rho), 1 <= rho <= d_r, d_r * rho <= 65536; every other descriptor field is ignored.
+ * cvf_align_feature_fwd copies r(x) out of the records; cvf_metric_apply[_stats] computes t = L^T g, q = L t, E = |t|^2 from them
+ * (csrc/metric_factor.hip; `a` and `aux_tiled` are ignored: diag_coeff is folded into L).  The fused and 16-frame launches
+ * (cvf_ef16_*, cvf_ef_[align_]fwd_metric_*, cvf_ef_align_fwd) take coordinates and refuse this mode; their predicates answer 0. */
+enum { CVF_PP_IDENTITY = 0, CVF_PP_ALIGN = 1, CVF_PP_FACTORED = 2 };
 /* cvf_mlp_desc.act[l]: what follows Linear layer l (nn.py:29-59 takes any torch activation module).  The chain kernels
  * (cvf_ae_*, cvf_regae_*, cvf_mlp_eval_rows) and the eigenfunction kernels on 64-frame tiles (cvf_ef_*: they use the
  * activation's first TWO derivatives, expressed through its output) take all of these, one code for every hidden layer of a
@@ -62,7 +68,7 @@ enum {
  * (examples/dipeptide/main.ipynb:333-348; consumed at core.py:403,414,635). */
 typedef struct cvf_pp_desc {
   int32_t mode;            /* CVF_PP_* */
-  int32_t n_coord;         /* floats per frame: 3*N (align) or d (identity) */
+  int32_t n_coord;         /* floats per frame: 3*N (align), d (identity) or d_r*(1+rho) (factored record) */
   int32_t n_align;         /* number of align atoms */
   int32_t n_rec;           /* number of feature records */
   int32_t d_r;             /* output dimension */
