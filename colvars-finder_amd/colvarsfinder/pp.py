@@ -209,16 +209,23 @@ class AlignFeatureLayer(torch.nn.Module):
     def forward(self, x):
         """``[B, N, 3]`` -> ``[B, d_r]``.  The reference calls this layer (through ``colvar_model()``) on CPU tensors
         made from the trajectory (2d.ipynb:437-446, main.ipynb:561-562): the frames are moved to the layer's GPU, run
-        through kernel K1 and the features come back on the input's device in the input's floating-point type.  No
-        autograd: the training tasks use the analytic derivative kernels instead of differentiating through this call."""
+        through kernel K1 and the features come back on the input's device in the input's floating-point type.
+
+        Differentiable in ``x`` to first order, like molann's layer: when ``x`` requires grad (and grad mode is on) the call
+        records a graph whose backward runs the HIP vector-Jacobian product ``cvf_align_feature_vjp`` and returns ``dL/dx`` in
+        ``x``'s type and on ``x``'s device.  Second derivatives are not built (the backward raises under ``create_graph=True``):
+        ``colvar_model()`` with a grad-requiring input and ``export.ScriptableAlignFeature`` have them.  The training tasks
+        use the analytic derivative kernels and call this layer without a graph."""
         x = torch.as_tensor(x)
         dev = _hip.require_gpu(self.rec.device)   # raises when the layer was never moved to a GPU: there is no CPU path
         assert x.dim() == 3 and x.shape[1] == self.n_atoms and x.shape[2] == 3, \
             f"expected [B,{self.n_atoms},3], got {tuple(x.shape)}"
-        if x.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("AlignFeatureLayer.forward is not differentiable through autograd; "
-                               "EigenFunctionTask applies its analytic Jacobian on the GPU instead (detach the input)")
         src_dev, src_dt = x.device, (x.dtype if x.dtype.is_floating_point else torch.float32)
+        if x.requires_grad and torch.is_grad_enabled():
+            # the conversions stay on the graph: a CPU fp64 input receives a CPU fp64 gradient
+            xd = x.to(device=dev, dtype=torch.float32).contiguous()
+            out = _AlignFeatureFn.apply(xd, self)
+            return out.to(device=src_dev, dtype=src_dt)
         x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
         B = x.shape[0]
         out = torch.empty(B, self.d_r, device=dev, dtype=torch.float32)
@@ -229,6 +236,46 @@ class AlignFeatureLayer(torch.nn.Module):
                 _hip.check(_hip.lib().cvf_align_feature_fwd(desc, _hip.ptr(x), B, None, _hip.ptr(out), None, _hip.ptr(scratch),
                                                             _hip.stream()), "cvf_align_feature_fwd")
         return out.to(device=src_dev, dtype=src_dt)
+
+
+_NO_DOUBLE_BACKWARD = ("AlignFeatureLayer: second derivatives through the HIP alignment + feature layer are not built (its "
+                       "backward ran with create_graph=True); differentiate twice through colvar_model() called with a "
+                       "grad-requiring input, or through export.ScriptableAlignFeature(layer), which are written with torch "
+                       "operators")
+
+
+class _AlignFeatureFn(torch.autograd.Function):
+    """``r(x)`` with its first derivative: forward = ``cvf_align_feature_fwd`` (features as rows, plus the per-frame aux rows
+    R / centroid / Kinv), backward = ``cvf_align_feature_vjp`` on those aux rows.  ``x``: fp32, contiguous, on the layer's GPU."""
+
+    @staticmethod
+    def forward(ctx, x, layer):
+        dev, B = x.device, x.shape[0]
+        out = torch.empty(B, layer.d_r, device=dev, dtype=torch.float32)
+        aux = torch.empty(_hip.ntiles(B), _hip.AUX_ROWS, _hip.TILE, device=dev, dtype=torch.float32)   # padded frame count
+        if B > 0:
+            with torch.cuda.device(dev):
+                desc = layer.pp_desc()
+                scratch = _hip.align_scratch(desc, B, dev)
+                _hip.check(_hip.lib().cvf_align_feature_fwd(desc, _hip.ptr(x), B, None, _hip.ptr(out), _hip.ptr(aux),
+                                                            _hip.ptr(scratch), _hip.stream()), "cvf_align_feature_fwd")
+        ctx.save_for_backward(x, aux)
+        ctx.layer = layer
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_NO_DOUBLE_BACKWARD)
+        x, aux = ctx.saved_tensors
+        layer, B = ctx.layer, x.shape[0]
+        gx = torch.empty_like(x)
+        if B > 0:
+            g = grad_out.to(device=x.device, dtype=torch.float32).contiguous()
+            with torch.cuda.device(x.device):
+                _hip.check(_hip.lib().cvf_align_feature_vjp(layer.pp_desc(), _hip.ptr(x), B, _hip.ptr(aux), _hip.ptr(g),
+                                                            _hip.ptr(gx), _hip.stream()), "cvf_align_feature_vjp")
+        return gx, None
 
 
 class FeatureLayer:

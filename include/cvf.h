@@ -170,6 +170,18 @@ int64_t cvf_align_feature_scratch_bytes(const cvf_pp_desc* pp, int64_t B); /* 0 
 int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows,
                           float* aux_tiled, void* scratch, void* stream);
 
+/* --- VJP of K1: dL/dx of the alignment + feature map, gx_rows[b] = J(x_b)^T g_rows[b] (csrc/k1_vjp.hip).  What autograd
+ * computes through pp_layer when the reference differentiates a loss or a CV with respect to the coordinates (core.py:418-426).
+ * x [B, n_coord] and aux_tiled [T][18][64] exactly as passed to / written by cvf_align_feature_fwd for the same frames;
+ * g_rows [B][d_r]; gx_rows [B][n_coord], fully written (0 for atoms no feature reads and the alignment does not use).
+ *   CVF_PP_ALIGN: every descriptor cvf_align_feature_fwd takes (any flags, partial alignment sets, all feature types, both
+ *     use_angle_value modes, align_w); frames of more than 192 coordinates also need the slot tables and mrec / slot_row, with
+ *     n_ref * 12 bytes within the LDS.  CVF_PP_IDENTITY: a copy.  CVF_PP_FACTORED: refused (the records come from a torch
+ *     module, which has its own autograd).
+ * No atomics: two calls on the same inputs give the same bits. */
+int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
+                          const float* g_rows, float* gx_rows, void* stream);
+
 /* --- K2+K3: per frame and net, q = J A J^T g and E = g^T J A J^T g with J the Jacobian
  * of r at the frame and A = diag(a).  Replaces the k autograd.grad calls through
  * pp_layer at core.py:424 and the a-weighted square sums at core.py:426,438; the
