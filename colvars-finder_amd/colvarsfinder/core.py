@@ -155,6 +155,180 @@ class _CVModel(torch.nn.Sequential):
             out = super().forward(x.detach().to(device=dev, dtype=torch.float32))
         return out.to(device=src_dev, dtype=src_dt)
 
+    # ---------------------------------------------------------------- derivatives of the CVs in the coordinates
+    # share of the free device memory the default chunk's workspace may take
+    JACOBIAN_MEMORY_FRACTION = 0.25
+
+    def jacobian(self, X, chunk=None):
+        """``(xi, J)`` of the frames ``X`` ``[B, *frame_shape]`` (CPU or device tensor or numpy array, fp32 or fp64):
+        ``xi [B, k]`` and ``J [B, k, *frame_shape]``, ``J[b, i] = d xi_i / d x`` at frame ``b``, on ``X``'s device and in its
+        floating-point type, without an autograd graph.  Columns follow the model's outputs (EigenFunctionTask: ``cvec``).
+
+        ``Identity`` and ``AlignFeatureLayer`` preprocessing: the nets' part ``d xi / d r`` by ``torch.func`` (fp32, on the
+        device), the coordinate part by the HIP kernel ``cvf_align_feature_vjp_rows`` (all k rows of a frame in one pass).
+        Any other preprocessing module, and alignment layers whose tables exceed the derivative kernels' limits
+        (``AlignFeatureLayer.derivative_table_limits()``), take the slow route: torch autograd through the whole map, one
+        backward per CV.  ``chunk`` bounds the device workspace in frames (default: from the free device memory)."""
+        return self._derivatives(X, chunk, want_m=False)
+
+    def metric_tensor(self, X, diag_coeff=None, chunk=None):
+        """``(xi, M)``: ``M [B, k, k] = J A J^T`` per frame with ``J`` as in :meth:`jacobian` and ``A = diag(diag_coeff)``
+        (``[tot_dim]``, non-negative and finite; ones by default) - the CV metric tensor (diffusion matrix of the effective
+        dynamics along xi, and the per-frame form of the generator's Rayleigh quotient).  ``J`` is never formed on the HIP
+        routes: ``q_j = J A J^T g_j`` comes from ``cvf_metric_apply`` (the generator step's kernel) and
+        ``M_ij = g_i . q_j`` from ``cvf_metric_gram``.  Alignment layers past ``derivative_table_limits()`` raise
+        ``NotImplementedError``; :meth:`jacobian` still takes them."""
+        X = self._frames_in(X)
+        tot_dim = int(np.prod(X.shape[1:]))
+        a = self._check_diag_coeff(diag_coeff, tot_dim)
+        return self._derivatives(X, chunk, want_m=True, a=a)
+
+    @staticmethod
+    def _frames_in(X):
+        return torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
+
+    @staticmethod
+    def _check_diag_coeff(diag_coeff, tot_dim):
+        """``diag_coeff`` as an fp64 CPU vector of length ``tot_dim`` (None: ones); ValueError when it is not a metric."""
+        if diag_coeff is None:
+            return torch.ones(tot_dim, dtype=torch.float64)
+        a = torch.as_tensor(np.asarray(diag_coeff) if not torch.is_tensor(diag_coeff) else diag_coeff)
+        a = a.detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+        if a.numel() != tot_dim:
+            raise ValueError(f"diag_coeff has {a.numel()} entries, the frames have {tot_dim} coordinates")
+        if not bool(torch.isfinite(a).all()) or bool((a < 0).any()):
+            raise ValueError("diag_coeff entries must be finite and >= 0 (A = diag(diag_coeff) is a metric)")
+        return a
+
+    def _pp_and_nets(self):
+        mods = list(self.children())
+        return mods[0], (mods[1] if len(mods) == 2 else torch.nn.Sequential(*mods[1:]))
+
+    def _derivatives(self, X, chunk, want_m, a=None):
+        X = self._frames_in(X)
+        dev = _hip.require_gpu(self._compute_device())
+        src_dev, src_dt = X.device, (X.dtype if X.dtype.is_floating_point else torch.float32)
+        B, frame_shape = int(X.shape[0]), tuple(X.shape[1:])
+        n = int(np.prod(frame_shape))
+        pp, nets = self._pp_and_nets()
+        large = isinstance(pp, AlignFeatureLayer) and _hip.lib().cvf_align_feature_scratch_bytes(pp.pp_desc(), 64) > 0
+        why = pp.derivative_table_limits() if large else None
+        if want_m and why is not None:
+            raise NotImplementedError(f"metric_tensor on MI355X: the feature list has {why} (csrc/metric_large.hip); "
+                                      "jacobian() takes this layer (slow route, torch autograd through the whole map)")
+        hip_route = isinstance(pp, torch.nn.Identity) or (isinstance(pp, AlignFeatureLayer) and why is None)
+        with torch.cuda.device(dev):
+            k = self._n_cv(X[:1], dev) if B > 0 else 0
+            if hip_route and not 1 <= k <= _hip.MAX_NETS:
+                raise NotImplementedError(f"jacobian / metric_tensor on MI355X: {k} CVs; the kernels take 1 to {_hip.MAX_NETS}")
+            xi = torch.empty(B, k, device=dev, dtype=torch.float32)
+            D = torch.empty((B, k, k) if want_m else (B, k, n), device=dev,
+                            dtype=torch.float32 if hip_route else self._slow_dtype(pp))
+            if B == 0:
+                return xi.to(device=src_dev, dtype=src_dt), D.reshape((0, k) + ((k,) if want_m else frame_shape)).to(
+                    device=src_dev, dtype=src_dt)
+            a_dev = None if a is None else a.to(device=dev, dtype=torch.float32).contiguous()
+            dense = None
+            if hip_route and want_m and large:
+                desc = pp.pp_desc()
+                dense = torch.zeros(_hip.lib().cvf_metric_dense_doubles(desc), device=dev, dtype=torch.float64)
+                _hip.check(_hip.lib().cvf_metric_dense_tensors(desc, _hip.ptr(a_dev), _hip.ptr(dense), _hip.stream()),
+                           "cvf_metric_dense_tensors")
+            c = self._chunk_frames(chunk, B, n, k, pp, dev)
+            for s0 in range(0, B, c):
+                xs = X[s0:s0 + c]
+                if hip_route:
+                    xi[s0:s0 + xs.shape[0]], D[s0:s0 + xs.shape[0]] = self._hip_chunk(xs, pp, nets, k, want_m, a_dev, dense, dev)
+                else:
+                    twin = self._autograd_twin() if isinstance(pp, AlignFeatureLayer) else self
+                    xi[s0:s0 + xs.shape[0]], D[s0:s0 + xs.shape[0]] = self._slow_chunk(xs, twin, k, want_m, a, dev)
+        D = D if want_m else D.reshape((B, k) + frame_shape)
+        return xi.to(device=src_dev, dtype=src_dt), D.to(device=src_dev, dtype=src_dt)
+
+    def _n_cv(self, x1, dev):
+        with torch.no_grad():
+            return int(self.forward(x1.to(dtype=torch.float32)).reshape(1, -1).shape[1])
+
+    @staticmethod
+    def _slow_dtype(pp):
+        for t in list(pp.parameters()) + list(pp.buffers()):
+            if t.is_floating_point():
+                return t.dtype
+        return torch.float32
+
+    def _chunk_frames(self, chunk, B, n, k, pp, dev):
+        if chunk is not None:
+            if int(chunk) < 1:
+                raise ValueError(f"chunk must be a positive number of frames, got {chunk}")
+            return int(chunk)
+        d_r = pp.d_r if isinstance(pp, AlignFeatureLayer) else n
+        # fp32 per frame: x, features, aux, d xi / d r (rows, padded tiles, q), J rows or M, and torch.func's temporaries
+        per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 6 * k * d_r + k * n + k * k) + 64 * k * d_r
+        free, _ = torch.cuda.mem_get_info(dev)
+        c = int(self.JACOBIAN_MEMORY_FRACTION * free) // per // _hip.TILE * _hip.TILE
+        return max(_hip.TILE, min(c, B))
+
+    def _hip_chunk(self, xs, pp, nets, k, want_m, a_dev, dense, dev):
+        """One chunk on the HIP route: (xi [c, k], J rows [c, k, n] or M [c, k, k]), fp32 on the device."""
+        lib, P, s = _hip.lib(), _hip.ptr, _hip.stream()
+        c = int(xs.shape[0])
+        x = xs.detach().to(device=dev, dtype=torch.float32).reshape(c, -1).contiguous()
+        n = x.shape[1]
+        T = _hip.ntiles(c)
+        if isinstance(pp, AlignFeatureLayer):
+            assert n == 3 * pp.n_atoms, f"frames have {n} coordinates, the layer expects {3 * pp.n_atoms}"
+            desc = pp.pp_desc()
+            r = torch.empty(c, pp.d_r, device=dev, dtype=torch.float32)
+            aux = torch.empty(T, _hip.AUX_ROWS, _hip.TILE, device=dev, dtype=torch.float32)   # padded frame count
+            scratch = _hip.align_scratch(desc, c, dev)
+            _hip.check(lib.cvf_align_feature_fwd(desc, P(x), c, None, P(r), P(aux), P(scratch), s), "cvf_align_feature_fwd")
+        else:
+            desc, r, aux, scratch = identity_desc(n), x, None, None
+        d_r = r.shape[1]
+
+        def f(v):
+            y = nets(v.unsqueeze(0)).reshape(-1)
+            return y, y
+
+        G, xi = torch.func.vmap(torch.func.jacrev(f, has_aux=True))(r)   # [c, k, d_r], [c, k]
+        G = G.detach().contiguous()
+        if not want_m:
+            J = torch.empty(c, k, n, device=dev, dtype=torch.float32)
+            _hip.check(lib.cvf_align_feature_vjp_rows(desc, P(x), c, P(aux), k, P(G), P(J), s), "cvf_align_feature_vjp_rows")
+            return xi.detach(), J
+        g_t = torch.zeros(T * _hip.TILE, k, d_r, device=dev, dtype=torch.float32)
+        g_t[:c] = G
+        g_t = g_t.reshape(T, _hip.TILE, k, d_r).permute(0, 2, 3, 1).contiguous()   # [T][k][d_r][64]
+        q_t = torch.empty_like(g_t)
+        e_t = torch.empty(T, k, _hip.TILE, device=dev, dtype=torch.float32)
+        _hip.check(lib.cvf_metric_apply(desc, P(x), c, P(aux), P(a_dev), k, P(g_t), P(q_t), P(e_t), P(scratch), P(dense), s),
+                   "cvf_metric_apply")
+        M = torch.empty(c, k, k, device=dev, dtype=torch.float32)
+        _hip.check(lib.cvf_metric_gram(k, c, d_r, P(g_t), P(q_t), P(M), s), "cvf_metric_gram")
+        return xi.detach(), M
+
+    @staticmethod
+    def _slow_chunk(xs, model, k, want_m, a, dev):
+        """The slow route on one chunk: torch autograd through ``model`` (the preprocessing module in its own precision, the
+        nets in fp32), one backward per CV.  Frame-local maps only, as the generator loss assumes (pp.FactoredMetric)."""
+        pp, nets = list(model.children())[0], list(model.children())[1:]
+        dt = _CVModel._slow_dtype(pp)
+        c = int(xs.shape[0])
+        x = xs.detach().to(device=dev, dtype=dt).requires_grad_(True)
+        with torch.enable_grad():
+            y = pp(x)
+            y = y.to(torch.float32)
+            for m in nets:
+                y = m(y)
+            y = y.reshape(c, k)
+            J = torch.empty(c, k, x[0].numel(), device=dev, dtype=dt)
+            for i in range(k):
+                g, = torch.autograd.grad(y[:, i].sum(), x, retain_graph=i + 1 < k, allow_unused=True)
+                J[:, i] = 0.0 if g is None else g.reshape(c, -1)
+        if not want_m:
+            return y.detach(), J
+        return y.detach(), torch.einsum("bin,n,bjn->bij", J, a.to(device=dev, dtype=dt), J)
+
 
 class _FlatParams:
     """The model's parameters as views of one fp32 device buffer (+ gradient and Adam moments)."""

@@ -329,3 +329,465 @@ extern "C" int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int6
   else launch(vjp_large_kernel<false>);
   return cvf_check_launch("vjp_large_kernel");
 }
+
+// ====================================================================================
+// k cotangents per frame in one launch (cvf_align_feature_vjp_rows): gx_rows[b][i] = J(x_b)^T g_rows[b][i], i < k.
+// The per-frame work is shared by the rows: the x tile / gathers, the tables, the aux rows (R, centroid, Kinv) and every
+// record's geometry (the gradient vectors of bond_eval / angle_eval / dihedral_eval) are taken once per frame and group of
+// rows; only the products with the cotangents are per row.  Row i sums in the single-cotangent kernels' order (records in
+// order into the gradient image, M and sum_p over the position records in order, the workgroup sums in wave order, every
+// slot's rows in order), so it equals cvf_align_feature_vjp on g_rows[:, i] bit for bit.  No atomics.
+// ====================================================================================
+namespace {
+
+// small frames: one lane per frame, as vjp_align_kernel, with `kg` gradient images side by side.
+// LDS: x tile [64][stride] | G [kg][64][stride] | acc [kg][12][64] (M, sum_p of each row and lane) | (TABLES_LDS) tables.
+template <bool TABLES_LDS>
+__global__ __launch_bounds__(64) void vjp_rows_small_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B,
+                                                             const float* __restrict__ aux_tiled, int k, int kg,
+                                                             const float* __restrict__ g_rows, float* __restrict__ gx_rows) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = threadIdx.x;
+  const int64_t tile = blockIdx.x;
+  const int nc = pp.n_coord, stride = x_tile_stride(nc), img = CVF_TILE * stride;
+  load_x_tile(x, B, nc, tile, lds, lane);
+  float* Gt = lds + img;
+  float* acc = Gt + kg * img;
+  const int32_t* rec = pp.rec;
+  const int32_t* al_idx = pp.align_idx;
+  const float* ref = pp.ref_c;
+  if (TABLES_LDS) {
+    int32_t* L = reinterpret_cast<int32_t*>(acc + kg * 12 * CVF_TILE);
+    const int n1 = 6 * pp.n_rec, n2 = n1 + pp.n_align, n3 = n2 + 3 * pp.n_align;
+    for (int i = lane; i < n3; i += CVF_WAVE)
+      L[i] = i < n1 ? pp.rec[i] : (i < n2 ? pp.align_idx[i - n1] : reinterpret_cast<const int32_t*>(pp.ref_c)[i - n2]);
+    rec = L;
+    al_idx = L + n1;
+    ref = reinterpret_cast<const float*>(L + n2);
+  }
+  __syncthreads();
+  const float* my = lds + lane * stride;
+  const int64_t frame = tile * CVF_TILE + lane;
+  const float* gf = g_rows + (frame < B ? frame : B - 1) * (int64_t)k * pp.d_r;   // tail lanes repeat the last frame
+  const float* ax = aux_tiled + tile * CVF_AUX_ROWS * CVF_TILE + lane;
+  float R[9], Kinv[6];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = ax[i * CVF_TILE];
+  const Centre c = centre_of(ax[9 * CVF_TILE], ax[10 * CVF_TILE], ax[11 * CVF_TILE]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) Kinv[i] = ax[(12 + i) * CVF_TILE];
+  const int64_t f0 = tile * CVF_TILE;
+  const int nvalid = (int)(B - f0 < CVF_TILE ? B - f0 : CVF_TILE);
+  for (int i0 = 0; i0 < k; i0 += kg) {
+    const int ng = k - i0 < kg ? k - i0 : kg;
+    for (int j = 0; j < ng * stride; ++j) Gt[(j / stride) * img + lane * stride + (j % stride)] = 0.0f;   // this lane's rows
+    for (int j = 0; j < ng * 12; ++j) acc[j * CVF_TILE + lane] = 0.0f;
+    auto addG = [&](int ii, int atm, V3 v) {
+      float* Gl = Gt + ii * img + lane * stride;
+      Gl[3 * atm] += v.x;
+      Gl[3 * atm + 1] += v.y;
+      Gl[3 * atm + 2] += v.z;
+    };
+    for (int r = 0; r < pp.n_rec; ++r) {
+      const int32_t* p = rec + 6 * r;
+      const int type = p[0], out = p[5];
+      if (type == CVF_FEAT_POSITION) {
+        const V3 xc = centred(my, p[1], c);
+        for (int ii = 0; ii < ng; ++ii) {
+          const float* gr = gf + (i0 + ii) * pp.d_r;
+          const V3 g = v3(gr[out], gr[out + 1], gr[out + 2]);
+          const V3 pr = mat_times(R, g);
+          addG(ii, p[1], pr);
+          float* A = acc + ii * 12 * CVF_TILE + lane;
+          A[0 * CVF_TILE] += xc.x * g.x; A[1 * CVF_TILE] += xc.x * g.y; A[2 * CVF_TILE] += xc.x * g.z;
+          A[3 * CVF_TILE] += xc.y * g.x; A[4 * CVF_TILE] += xc.y * g.y; A[5 * CVF_TILE] += xc.y * g.z;
+          A[6 * CVF_TILE] += xc.z * g.x; A[7 * CVF_TILE] += xc.z * g.y; A[8 * CVF_TILE] += xc.z * g.z;
+          A[9 * CVF_TILE] = A[9 * CVF_TILE] + pr.x;
+          A[10 * CVF_TILE] = A[10 * CVF_TILE] + pr.y;
+          A[11 * CVF_TILE] = A[11 * CVF_TILE] + pr.z;
+        }
+      } else if (type == CVF_FEAT_BOND) {
+        const BondG e = bond_eval(atom_at(my, p[1]), atom_at(my, p[2]));
+        for (int ii = 0; ii < ng; ++ii) {
+          const float gs = gf[(i0 + ii) * pp.d_r + out];
+          addG(ii, p[1], gs * e.ga);
+          addG(ii, p[2], gs * e.gb);
+        }
+      } else if (type == CVF_FEAT_ANGLE) {
+        const AngleG e = angle_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]));
+        for (int ii = 0; ii < ng; ++ii) {
+          float gs = gf[(i0 + ii) * pp.d_r + out];
+          if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
+          addG(ii, p[1], gs * e.ga);
+          addG(ii, p[2], gs * e.gb);
+          addG(ii, p[3], gs * e.gc);
+        }
+      } else {
+        const DihedralG e = dihedral_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]), atom_at(my, p[4]));
+        for (int ii = 0; ii < ng; ++ii) {
+          const float* gr = gf + (i0 + ii) * pp.d_r;
+          const float gs = pp.use_angle_value ? gr[out] : (gr[out + 1] * e.cs - gr[out] * e.sn);
+          addG(ii, p[1], gs * e.g1);
+          addG(ii, p[2], gs * e.g2);
+          addG(ii, p[3], gs * e.g3);
+          addG(ii, p[4], gs * e.g4);
+        }
+      }
+    }
+    if (pp.has_position) {
+      for (int ii = 0; ii < ng; ++ii) {
+        const float* A = acc + ii * 12 * CVF_TILE + lane;
+        float M[9], Z[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) M[j] = A[j * CVF_TILE];
+        rotation_term(R, Kinv, M, Z);
+        const V3 shift = (1.0f / (float)pp.n_align) * v3(A[9 * CVF_TILE], A[10 * CVF_TILE], A[11 * CVF_TILE]);
+        for (int b = 0; b < pp.n_align; ++b) {
+          const V3 rf = v3(ref[3 * b], ref[3 * b + 1], ref[3 * b + 2]);
+          const float wb = pp.align_w ? pp.align_w[b] : 1.0f;
+          addG(ii, al_idx[b], mat_times(Z, rf) - wb * shift);
+        }
+      }
+    }
+    lds_barrier();
+    // copy-out: rows i0 .. i0+ng-1 of a frame are one contiguous run of ng * nc floats in gx_rows [B][k][nc]
+    const int run = ng * nc, total = nvalid * run;
+    for (int e = lane; e < total; e += CVF_WAVE) {
+      const int fr = e / run, rem = e - fr * run, ii = rem / nc, j = rem - ii * nc;
+      gx_rows[((f0 + fr) * k + i0) * nc + rem] = Gt[ii * img + fr * stride + j];
+    }
+    lds_barrier();   // (the next group zeroes the images this copy-out reads)
+  }
+}
+
+// large frames: one workgroup per frame, as vjp_large_kernel, for rows i0 .. i0+ng-1 of the k, their contribution rows side
+// by side.  LDS: rows [ng][n_ref * 3] | red [ng][4][12] | zs [ng][12] (Z, shift of each row).
+template <bool VEC4>
+__global__ __launch_bounds__(kLargeThreads) void vjp_rows_large_kernel(cvf_pp_desc pp, const float* __restrict__ x,
+                                                                        const float* __restrict__ aux_tiled, int k, int i0, int ng,
+                                                                        const float* __restrict__ g_rows,
+                                                                        float* __restrict__ gx_rows) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int kWaves = kLargeThreads / CVF_WAVE;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t frame = blockIdx.x;
+  const int nc = pp.n_coord, nrow = 3 * pp.n_ref;
+  float* red = lds + ng * nrow;
+  float* zs = red + ng * kWaves * 12;
+  const float* xf = x + frame * nc;
+  const float* gf = g_rows + frame * (int64_t)k * pp.d_r;
+  const float* ax = aux_tiled + (frame / CVF_TILE) * CVF_AUX_ROWS * CVF_TILE + (frame % CVF_TILE);
+  // (R, the centroid and Kinv are read where they are used, per group of rows: the uniform values live across the whole
+  //  kernel are what the scalar registers hold)
+  auto load_R = [&](float* R) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = ax[i * CVF_TILE];
+  };
+  auto at = [&](int slot) {
+    const int a = pp.slot_atom[slot];
+    return V3{xf[3 * a], xf[3 * a + 1], xf[3 * a + 2]};
+  };
+  auto put = [&](int ii, int row, V3 v) {
+    float* rows = lds + ii * nrow;
+    rows[3 * row] = v.x;
+    rows[3 * row + 1] = v.y;
+    rows[3 * row + 2] = v.z;
+  };
+  struct Rec {
+    int type, out, s0, s1, s2, s3, r0, r1, r2, r3;
+  };
+  auto decode = [&](int r) {
+    const int4 m0 = reinterpret_cast<const int4*>(pp.mrec)[2 * r];
+    const int4 m1 = reinterpret_cast<const int4*>(pp.mrec)[2 * r + 1];
+    Rec d;
+    d.type = (m0.x & 7) - 1;
+    d.out = (int)((unsigned)m0.x >> 3);
+    d.s0 = m0.y & 0xffff; d.s1 = (int)((unsigned)m0.y >> 16); d.s2 = m0.z & 0xffff; d.s3 = (int)((unsigned)m0.z >> 16);
+    const int off = m1.y;
+    d.r0 = (m0.w & 0xffff) + (off & 0xff);
+    d.r1 = (int)((unsigned)m0.w >> 16) + ((off >> 8) & 0xff);
+    d.r2 = (m1.x & 0xffff) + ((off >> 16) & 0xff);
+    d.r3 = (int)((unsigned)m1.x >> 16) + (int)((unsigned)off >> 24);
+    return d;
+  };
+  {
+    // ---- phase A, position records: row by row (M and sum_p are per-thread register sums, in the records' order)
+    float R[9];
+    load_R(R);
+    const V3 c = v3(ax[9 * CVF_TILE], ax[10 * CVF_TILE], ax[11 * CVF_TILE]);
+    for (int ii = 0; ii < ng; ++ii) {
+      const float* gr = gf + (i0 + ii) * pp.d_r;
+      float acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      if (pp.has_position) {
+        for (int r = tid; r < pp.n_mrec; r += kLargeThreads) {
+          const Rec d = decode(r);
+          if (d.type != CVF_FEAT_POSITION) continue;
+          const V3 g = v3(gr[d.out], gr[d.out + 1], gr[d.out + 2]);
+          const V3 pr = mat_times(R, g);
+          put(ii, d.r0, pr);
+          const V3 xc = at(d.s0) - c;
+          acc[0] += xc.x * g.x; acc[1] += xc.x * g.y; acc[2] += xc.x * g.z;
+          acc[3] += xc.y * g.x; acc[4] += xc.y * g.y; acc[5] += xc.y * g.z;
+          acc[6] += xc.z * g.x; acc[7] += xc.z * g.y; acc[8] += xc.z * g.z;
+          acc[9] += pr.x; acc[10] += pr.y; acc[11] += pr.z;
+        }
+      }
+      // (each wave sum is stored as soon as it is formed: twelve uniform sums alive at once overflow the scalar registers)
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        const float v = wave_sumf(acc[i]);
+        if (lane == 0) red[(ii * kWaves + wave) * 12 + i] = v;
+      }
+    }
+    // ---- phase A, the other records: geometry once, then one product per row
+    for (int r = tid; r < pp.n_mrec; r += kLargeThreads) {
+      const Rec d = decode(r);
+      if (d.type == CVF_FEAT_BOND) {
+        const BondG e = bond_eval(at(d.s0), at(d.s1));
+        for (int ii = 0; ii < ng; ++ii) {
+          const float gs = gf[(i0 + ii) * pp.d_r + d.out];
+          put(ii, d.r0, gs * e.ga);
+          put(ii, d.r1, gs * e.gb);
+        }
+      } else if (d.type == CVF_FEAT_ANGLE) {
+        const AngleG e = angle_eval(at(d.s0), at(d.s1), at(d.s2));
+        for (int ii = 0; ii < ng; ++ii) {
+          float gs = gf[(i0 + ii) * pp.d_r + d.out];
+          if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
+          put(ii, d.r0, gs * e.ga);
+          put(ii, d.r1, gs * e.gb);
+          put(ii, d.r2, gs * e.gc);
+        }
+      } else if (d.type == CVF_FEAT_DIHEDRAL) {
+        const DihedralG e = dihedral_eval(at(d.s0), at(d.s1), at(d.s2), at(d.s3));
+        for (int ii = 0; ii < ng; ++ii) {
+          const float* gr = gf + (i0 + ii) * pp.d_r;
+          const float gs = pp.use_angle_value ? gr[d.out] : (gr[d.out + 1] * e.cs - gr[d.out] * e.sn);
+          put(ii, d.r0, gs * e.g1);
+          put(ii, d.r1, gs * e.g2);
+          put(ii, d.r2, gs * e.g3);
+          put(ii, d.r3, gs * e.g4);
+        }
+      }
+    }
+    __syncthreads();
+    // ---- phase B: every slot of every row sums its rows in order into its first row; thread ii < ng forms Z, shift of row ii
+    for (int ii = 0; ii < ng; ++ii) {
+      float* rows = lds + ii * nrow;
+      for (int t = tid; t < pp.n_slot; t += kLargeThreads) {
+        const int q0 = pp.slot_row[t], q1 = pp.slot_row[t + 1];
+        V3 s = v3(rows[3 * q0], rows[3 * q0 + 1], rows[3 * q0 + 2]);
+        for (int q = q0 + 1; q < q1; ++q) s = s + v3(rows[3 * q], rows[3 * q + 1], rows[3 * q + 2]);
+        put(ii, q0, s);
+      }
+    }
+    if (tid < ng) {
+      float tot[12];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        float v = red[(tid * kWaves) * 12 + i];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) v += red[(tid * kWaves + w) * 12 + i];
+        tot[i] = v;
+      }
+      float Z[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      V3 shift = v3(0, 0, 0);
+      if (pp.has_position) {
+        float R[9], Kinv[6];
+        load_R(R);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Kinv[i] = ax[(12 + i) * CVF_TILE];
+        rotation_term(R, Kinv, tot, Z);
+        shift = (1.0f / (float)pp.n_align) * v3(tot[9], tot[10], tot[11]);
+      }
+#pragma unroll
+      for (int i = 0; i < 9; ++i) zs[tid * 12 + i] = Z[i];
+      zs[tid * 12 + 9] = shift.x;
+      zs[tid * 12 + 10] = shift.y;
+      zs[tid * 12 + 11] = shift.z;
+    }
+    __syncthreads();
+    // ---- phase 2: the dense rows; an atom's table entries are read once for all rows of the group
+    struct AtomRef {
+      int b, q;
+      V3 rf;
+    };
+    auto lookup = [&](int a) {
+      AtomRef u;
+      u.b = pp.atom_align[a];
+      u.rf = u.b >= 0 ? v3(pp.ref_c[3 * u.b], pp.ref_c[3 * u.b + 1], pp.ref_c[3 * u.b + 2]) : v3(0, 0, 0);
+      const int t = pp.atom_slot[a];
+      u.q = t >= 0 ? pp.slot_row[t] : -1;
+      return u;
+    };
+    auto grad_of = [&](int ii, const AtomRef& u) {
+      V3 v = v3(0, 0, 0);
+      if (u.b >= 0) {
+        const float* Z = zs + ii * 12;
+        v = mat_times(Z, u.rf) - v3(Z[9], Z[10], Z[11]);
+      }
+      if (u.q >= 0) {
+        const float* rows = lds + ii * nrow;
+        v = v + v3(rows[3 * u.q], rows[3 * u.q + 1], rows[3 * u.q + 2]);
+      }
+      return v;
+    };
+    float* gx0 = gx_rows + (frame * k + i0) * (int64_t)nc;
+    if (VEC4) {
+      for (int v = tid; v < nc / 4; v += kLargeThreads) {
+        const int j0 = 4 * v, A = j0 / 3, k0 = j0 - 3 * A;
+        const AtomRef ua = lookup(A), ub = lookup(A + 1);
+        float4* dst = reinterpret_cast<float4*>(gx0) + v;
+#pragma unroll 1
+        for (int ii = 0; ii < ng; ++ii, dst += nc / 4) {
+          const V3 u = grad_of(ii, ua), w = grad_of(ii, ub);
+          float4 o;
+          o.x = k0 == 0 ? u.x : (k0 == 1 ? u.y : u.z);
+          o.y = k0 == 0 ? u.y : (k0 == 1 ? u.z : w.x);
+          o.z = k0 == 0 ? u.z : (k0 == 1 ? w.x : w.y);
+          o.w = k0 == 0 ? w.x : (k0 == 1 ? w.y : w.z);
+          *dst = o;
+        }
+      }
+    } else {
+      for (int j = tid; j < nc; j += kLargeThreads) {
+        const int A = j / 3, kk = j - 3 * A;
+        const AtomRef ua = lookup(A);
+        for (int ii = 0; ii < ng; ++ii) {
+          const V3 u = grad_of(ii, ua);
+          gx0[ii * (int64_t)nc + j] = kk == 0 ? u.x : (kk == 1 ? u.y : u.z);
+        }
+      }
+    }
+  }
+}
+
+// M = G Q^T per frame: m[b][i][j] = sum_r g[b][i][r] q[b][j][r] for i <= j, r in order, mirrored below the diagonal.
+// One lane per frame; every (i, j) sum lives in a register while g and q stream through once (coalesced tiled rows).
+template <int K>
+__global__ __launch_bounds__(64) void metric_gram_kernel(int64_t B, int d_r, const float* __restrict__ g_tiled,
+                                                          const float* __restrict__ q_tiled, float* __restrict__ m_rows) {
+  const int lane = threadIdx.x;
+  const int64_t tile = blockIdx.x, frame = tile * CVF_TILE + lane;
+  const float* g = g_tiled + tile * K * d_r * CVF_TILE + lane;
+  const float* q = q_tiled + tile * K * d_r * CVF_TILE + lane;
+  float s[K * (K + 1) / 2];
+#pragma unroll
+  for (int p = 0; p < K * (K + 1) / 2; ++p) s[p] = 0.0f;
+  for (int r = 0; r < d_r; ++r) {
+    float gv[K], qv[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      gv[i] = g[(i * d_r + r) * CVF_TILE];
+      qv[i] = q[(i * d_r + r) * CVF_TILE];
+    }
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+      for (int j = i; j < K; ++j) s[p++] += gv[i] * qv[j];
+  }
+  if (frame >= B) return;
+  float* m = m_rows + frame * K * K;
+  int p = 0;
+#pragma unroll
+  for (int i = 0; i < K; ++i)
+#pragma unroll
+    for (int j = i; j < K; ++j) {
+      m[i * K + j] = s[p];
+      m[j * K + i] = s[p];
+      ++p;
+    }
+}
+
+}  // namespace
+
+extern "C" int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, int k,
+                                          const float* g_rows, float* gx_rows, void* stream) {
+  CVF_REQUIRE(pp && g_rows && gx_rows && B > 0 && k >= 1 && k <= CVF_MAX_NETS,
+              "cvf_align_feature_vjp_rows: null argument, empty batch or k outside 1..%d (B=%lld k=%d)", CVF_MAX_NETS,
+              (long long)B, k);
+  hipStream_t s = (hipStream_t)stream;
+  if (pp->mode == CVF_PP_IDENTITY) {
+    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+    const hipError_t e = hipMemcpyAsync(gx_rows, g_rows, (size_t)B * k * pp->n_coord * sizeof(float), hipMemcpyDeviceToDevice, s);
+    CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_vjp_rows: identity copy: %s", hipGetErrorString(e));
+    return 0;
+  }
+  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
+              "cvf_align_feature_vjp_rows: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own "
+              "autograd");
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  CVF_REQUIRE(x && aux_tiled, "cvf_align_feature_vjp_rows: align mode needs x and the forward's aux rows");
+  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
+              "cvf_align_feature_vjp_rows: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
+  CVF_REQUIRE(!pp->align_w || (pp->flags == 0 && pp->n_coord <= kLanePerFrameMaxCoord),
+              "cvf_align_feature_vjp_rows: per-atom alignment weights need flags == 0 and at most %d coordinates per frame",
+              kLanePerFrameMaxCoord);
+  if (pp->n_coord <= kLanePerFrameMaxCoord) {
+    // images per launch: as many rows as keep the LDS within 40 KB (four workgroups per CU, as the single-cotangent kernel
+    // at config 3 - one row per pass there), at least one
+    const size_t img = (size_t)CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
+    const size_t per_row = img + (size_t)12 * CVF_TILE * sizeof(float);
+    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
+    const size_t budget = 40 * 1024;
+    bool tables_lds = img + per_row + tables <= 160 * 1024;
+    const size_t fixed = img + (tables_lds ? tables : 0);
+    int kg = fixed + per_row * k <= budget ? k : (int)((budget > fixed + per_row ? budget - fixed : per_row) / per_row);
+    kg = kg < 1 ? 1 : kg;
+    const size_t lds = fixed + per_row * kg;
+    CVF_REQUIRE(lds <= 160 * 1024, "cvf_align_feature_vjp_rows: frames of %d coordinates do not fit the LDS", pp->n_coord);
+    auto launch = [&](auto kernel) {
+      if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)cvf_ntiles(B)), dim3(64), lds, s, *pp, x, B, aux_tiled, k, kg, g_rows, gx_rows);
+    };
+    if (tables_lds) launch(vjp_rows_small_kernel<true>);
+    else launch(vjp_rows_small_kernel<false>);
+    return cvf_check_launch("vjp_rows_small_kernel");
+  }
+  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot && pp->n_slot > 0 && pp->n_ref > 0,
+              "cvf_align_feature_vjp_rows: frames of more than %d coordinates need the slot and contribution-row tables "
+              "(atom_align, atom_slot, slot_atom, mrec, slot_row)", kLanePerFrameMaxCoord);
+  CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "cvf_align_feature_vjp_rows: mrec must be 16-byte aligned");
+  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_vjp_rows: at most 2^31 - 1 frames per call");
+  const size_t per_row = ((size_t)pp->n_ref * 3 + (size_t)12 * (kLargeThreads / CVF_WAVE) + 12) * sizeof(float);
+  CVF_REQUIRE(per_row <= 160 * 1024,
+              "cvf_align_feature_vjp_rows: %d contribution rows (atoms summed over the features) do not fit the LDS", pp->n_ref);
+  const size_t budget = 64 * 1024;
+  int kg = per_row * k <= budget ? k : (int)(budget / per_row);
+  kg = kg < 1 ? 1 : kg;
+  const bool vec4 = pp->n_coord % 4 == 0 && ((uintptr_t)gx_rows & 15) == 0;
+  // one launch per group of kg rows (at config 5 all k rows fit one launch)
+  for (int i0 = 0; i0 < k; i0 += kg) {
+    const int ng = k - i0 < kg ? k - i0 : kg;
+    const size_t lds = per_row * ng;
+    auto launch = [&](auto kernel) {
+      if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, k, i0, ng, g_rows, gx_rows);
+    };
+    if (vec4) launch(vjp_rows_large_kernel<true>);
+    else launch(vjp_rows_large_kernel<false>);
+    const int rc = cvf_check_launch("vjp_rows_large_kernel");
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+extern "C" int cvf_metric_gram(int k, int64_t B, int d_r, const float* g_tiled, const float* q_tiled, float* m_rows,
+                               void* stream) {
+  CVF_REQUIRE(g_tiled && q_tiled && m_rows && B > 0 && d_r > 0 && k >= 1 && k <= CVF_MAX_NETS,
+              "cvf_metric_gram: bad argument (B=%lld k=%d d_r=%d)", (long long)B, k, d_r);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)cvf_ntiles(B)), block(64);
+  switch (k) {
+    case 1: hipLaunchKernelGGL(metric_gram_kernel<1>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 2: hipLaunchKernelGGL(metric_gram_kernel<2>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 3: hipLaunchKernelGGL(metric_gram_kernel<3>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 4: hipLaunchKernelGGL(metric_gram_kernel<4>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 5: hipLaunchKernelGGL(metric_gram_kernel<5>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 6: hipLaunchKernelGGL(metric_gram_kernel<6>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    case 7: hipLaunchKernelGGL(metric_gram_kernel<7>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+    default: hipLaunchKernelGGL(metric_gram_kernel<8>, grid, block, 0, s, B, d_r, g_tiled, q_tiled, m_rows); break;
+  }
+  return cvf_check_launch("metric_gram_kernel");
+}

@@ -181,6 +181,12 @@ int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int64_t B, floa
  * No atomics: two calls on the same inputs give the same bits. */
 int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
                           const float* g_rows, float* gx_rows, void* stream);
+/* k cotangents per frame in one launch, 1 <= k <= CVF_MAX_NETS: gx_rows[b][i] = J(x_b)^T g_rows[b][i]  (g_rows [B][k][d_r],
+ * gx_rows [B][k][n_coord]; the Jacobian of a k-vector CV when g_rows holds d xi_i / d r).  Same descriptors, inputs and
+ * refusals as cvf_align_feature_vjp; row i equals cvf_align_feature_vjp on g_rows[:, i] bit for bit.  The x tile / gathers,
+ * the tables, the aux rows and every record's geometry are taken once per frame, not once per row.  No atomics. */
+int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, int k,
+                               const float* g_rows, float* gx_rows, void* stream);
 
 /* --- K2+K3: per frame and net, q = J A J^T g and E = g^T J A J^T g with J the Jacobian
  * of r at the frame and A = diag(a).  Replaces the k autograd.grad calls through
@@ -205,6 +211,10 @@ int cvf_metric_apply_stats(const cvf_pp_desc* pp, const float* x, int64_t B, con
  * (a, ref, align flag, rows of the slot) for the derivative kernel. */
 int64_t cvf_metric_dense_doubles(const cvf_pp_desc* pp);
 int cvf_metric_dense_tensors(const cvf_pp_desc* pp, const float* a, double* dense, void* stream);
+/* The CV metric tensor per frame from cvf_metric_apply's input and output: m_rows[b][i][j] = g_i . q_j = (J A J^T)_ij in CV
+ * space (g_tiled, q_tiled [T][k][d_r][64] as cvf_metric_apply takes / writes them; m_rows [B][k][k]).  Each sum over the d_r
+ * features runs in order for i <= j; the lower triangle mirrors it, so M is exactly symmetric.  1 <= k <= CVF_MAX_NETS. */
+int cvf_metric_gram(int k, int64_t B, int d_r, const float* g_tiled, const float* q_tiled, float* m_rows, void* stream);
 
 /* --- packed MFMA weight fragments of the nets (a second copy of the weights in the order the
  * matrix-core kernels consume them; see csrc/cvf_pack.hpp).  cvf_ef_pack rebuilds it from theta;
