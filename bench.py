@@ -10,9 +10,13 @@ Adam (K6).  With N > 1 (one process per GPU, launched by torch.distributed.run) 
 block of the frames and the two all-reduces of SURVEY.md section 8e (batch sums before the backward pass, flat gradient
 after it) run over RCCL.  N > 1 defaults to STRONG scaling on BASELINE config 4: 1 M frames in all (1/N resident per GPU), a
 fixed global batch (--global-batch, default 800 000 frames per step of the whole job = the whole training split of the
-1 M-frame set at the reference's test_ratio 0.2, one step per epoch); --scaling weak keeps --batch frames per GPU.  Every line also carries `scaling_table`: the same job at global batches 20 000 / 160 000 / 800 000 and the weak line.
+1 M-frame set at the reference's test_ratio 0.2, one step per epoch); --scaling weak keeps --batch frames per GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = frames of all ranks / second.
+Prints ONE JSON line on rank 0 (contract in the task statement): value = frames of all ranks / second.  A plain run does only
+what that line needs: set-up, the W warm-up steps and the preheat, the K timed steps, --dump-outputs, the line.  --full adds the
+measurements that take runs of their own: the per-call HIP-event pass (`kernel_avg_us`, `roofline`, `launches_per_step`), and
+unless --no-extras `scaling_table` (the same job at global batches 20 000 / 160 000 / 800 000 and the weak line),
+`roofline_align_feature` and `other_configs`, and unless --cpu-seconds 0 `cpu_baseline` - several minutes in all.
 """
 
 import argparse
@@ -271,10 +275,13 @@ def main():
     ap.add_argument("--frames-total", type=int, default=1_000_000, help="config 4: frames of the whole job")
     ap.add_argument("--global-batch", type=int, default=800_000,
                     help="strong scaling: frames per step of the whole job (default: the training split of the 1 M-frame set)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 disables it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also run the per-call pass, the secondary measurements and the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline leg (0 disables it)")
     ap.add_argument("--preheat-ms", type=float, default=75.0,
                     help="untimed steps run for about this long after the W warm-up steps, before the clock starts (GPU frequency ramp; 0 = off)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other global batches, K1 rooflines)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the secondary measurements (other global batches, K1 rooflines, other configurations)")
     ap.add_argument("--workload", choices=["c3", "c5", "c2", "regae", "transfer"], default="c3",
                     help="c3 = the benchmark line; c5 = config-5 shape, c2 = config-2 AutoEncoderTask (extra measurements)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -343,13 +350,45 @@ def main():
     preheat_steps = run_steps.preheat_steps
     graphs = task._use_graphs
     final_loss = float(loss_vec[0])
-    if args.dump_outputs is not None and rank == 0:   # (before the per-call pass below trains on)
+    if args.dump_outputs is not None and rank == 0:   # (before the per-call pass of --full trains on)
         dump_outputs(args.dump_outputs, loss_vector=loss_vec,
                      parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+    note(f"timed region done: {elapsed / args.steps * 1e3:.4f} ms/step")
 
-    # ---- per-kernel durations: HIP events around every C-ABI call over a second, eager pass of the same steps (not part
-    # of `value`); the GPU is parked while the host queues each step, so the events bracket back-to-back executions
-    note(f"timed region done: {elapsed / args.steps * 1e3:.4f} ms/step; per-call HIP-event pass")
+    line = {
+        "metric": "MD frames/sec through EigenFunctionTask train step",
+        "value": world * B * args.steps / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "preheat_steps": preheat_steps,
+        "preheat_note": "untimed steps of the same kind run after the W warm-up steps (--preheat-ms) so that the timed K steps see the "
+                        "GPU clock of a long training run; --preheat-ms 0 turns it off",
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": workload, "frames_per_gpu": frames_rank, "batch_per_gpu": B, "global_batch": world * B,
+                   "parallelism": f"dp{world} (frames sharded; all-reduce of batch sums + flat gradient)"},
+        "hip_graph": bool(graphs),
+        "graph_granularity": "one hipGraph replay per chunk of the resident static batches (as train() replays one per epoch)",
+        "final_loss": final_loss,
+    }
+    if scaling == "strong":
+        line["strong_scaling_note"] = (f"this line is the {args.frames_total}-frame job at a global batch of {world * B} frames per step on {world} GPU(s); "
+                                       f"its one-GPU reference is scaling_table.rows['strong:{world * B}'] of the N = 1 --full line (the same job), not "
+                                       "the N = 1 headline, which is BASELINE config 3 (100 000 frames, 20 000 per step)")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        return
+
+    # ---- --full: per-kernel durations: HIP events around every C-ABI call over a second, eager pass of the same steps (not
+    # part of `value`); the GPU is parked while the host queues each step, so the events bracket back-to-back executions
+    note("per-call HIP-event pass")
     task._use_graphs, task._events, task._last_call = False, {}, {}
     for i in range(min(args.steps, 50)):
         torch.cuda._sleep(2_000_000)
@@ -446,23 +485,7 @@ def main():
         roof = dict(kernel=dom, bound="hbm", achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
                     traffic=pmc_traffic(dom), avg_launch_us=kern_ms[dom] * 1e3)
     out = {
-        "metric": "MD frames/sec through EigenFunctionTask train step",
-        "value": world * B * args.steps / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "preheat_steps": preheat_steps,
-        "preheat_note": "untimed steps of the same kind run after the W warm-up steps (--preheat-ms) so that the timed K steps see the "
-                        "GPU clock of a long training run; --preheat-ms 0 turns it off",
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": workload, "frames_per_gpu": frames_rank, "batch_per_gpu": B, "global_batch": world * B,
-                   "parallelism": f"dp{world} (frames sharded; all-reduce of batch sums + flat gradient)"},
+        **line,
         "roofline": roof,
         "kernel_avg_us": {n: v * 1e3 for n, v in sorted(kern_ms.items(), key=lambda kv: -kv[1])},
         "kernel_timing": ("HIP events around each C-ABI call over a second, eager pass of the same steps (the timed region "
@@ -475,16 +498,9 @@ def main():
                                                   "inside cvf_ef16_finish_dp / cvf_slab_reduce_dp (peer-to-peer windows, csrc/cvf_p2p.hpp)"
                                                   if _dist.fused_comm() is not None else "separate all-reduce launches"),
                               "comm_mode": _dist.comm_mode()},
-        "hip_graph": bool(graphs),
-        "graph_granularity": "one hipGraph replay per chunk of the resident static batches (as train() replays one per epoch)",
         "traffic_note": (f"roofline.traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 B per launch from profiles/{prof}_pmc_traffic.json "
                          "(separate rocprofv3 --pmc passes of this command; gfx950 FETCH_SIZE halving corrected)"),
-        "final_loss": final_loss,
     }
-    if scaling == "strong":
-        out["strong_scaling_note"] = (f"this line is the {args.frames_total}-frame job at a global batch of {world * B} frames per step on {world} GPU(s); "
-                                      f"its one-GPU reference is scaling_table.rows['strong:{world * B}'] of the N = 1 line (the same job), not the "
-                                      "N = 1 headline, which is BASELINE config 3 (100 000 frames, 20 000 per step)")
     out.update(extras)
     if world == 1 and not args.no_extras:
         del X, Wt

@@ -1130,6 +1130,38 @@ def test_bench_gpus2_entry_point_on_one_gpu(dev):
     assert np.isfinite(out["final_loss"])
 
 
+def test_bench_full_adds_measurements_after_the_same_timed_steps(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` prints the headline line alone (no per-call pass, no secondary
+    measurements, no CPU baseline); `--full` adds the per-call figures.  What --full adds runs after the timed steps, so both runs
+    dump the same last timed step bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-extras", "--cpu-seconds", "0"])):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        found = [ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(found) == 1, res.stdout[-2000:]
+        lines[name] = json.loads(found[0])
+    plain, full = lines["plain"], lines["full"]
+    for out in (plain, full):
+        assert out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 7
+        assert out["value"] > 0 and np.isclose(out["value"], 20000 * 1e3 / out["ms_per_step"], rtol=1e-9)
+    full_only = ("kernel_avg_us", "roofline", "launches_per_step", "scaling_table", "roofline_align_feature", "other_configs",
+                 "cpu_baseline")
+    assert not any(k_ in plain for k_ in full_only), sorted(plain)
+    assert {"kernel_avg_us", "roofline", "launches_per_step"} <= set(full)
+    assert set(plain) <= set(full)
+    for name in ("loss_vector", "parameters"):
+        a_, b_ = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a_.dtype == b_.dtype and np.array_equal(a_, b_), name
+    assert plain["final_loss"] == full["final_loss"] == float(np.load(tmp_path / "plain" / "loss_vector.npy")[0])
+
+
 @pytest.mark.parametrize("world", [2, 4])
 def test_one_shot_p2p_reduce_between_processes_on_one_gpu(dev, world):
     """SURVEY section 5 / VERDICT r2 item 8b: the one-shot peer-to-peer reduce behind cvf_p2p_* with `world` processes on the one GPU

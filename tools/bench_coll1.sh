@@ -11,7 +11,7 @@ for b in 20000 100000; do
     [ $mode = abi ] && export CVF_COMM=abi
     [ $mode = p2p ] && export CVF_COMM=p2p CVF_FUSED_COMM=0
     [ $mode = fused ] && export CVF_COMM=p2p
-    python bench.py --steps 40 --warmup 5 --no-extras --cpu-seconds 0 --batch $b --frames $((b*5)) 2>/dev/null | tail -1 > /tmp/line.json
+    python bench.py --full --steps 40 --warmup 5 --no-extras --cpu-seconds 0 --batch $b --frames $((b*5)) 2>/dev/null | tail -1 > /tmp/line.json
     python3 -c "import json; d=json.load(open('/tmp/line.json')); print('$mode', $b, 'us/step', round(d['ms_per_step']*1000,2), 'graphs', d['hip_graph'], 'launches', d['launches_per_step']['total'])"
   done
 done

@@ -5,7 +5,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"; O="$R/gpurun_out/${CV
 for mode in fused separate group; do
   export CVF_BENCH_ONE_GPU=1 CVF_BENCH_BACKEND=gloo
   case $mode in fused) export CVF_COMM=p2p CVF_FUSED_COMM=1;; separate) export CVF_COMM=p2p CVF_FUSED_COMM=0;; group) export CVF_COMM=rccl;; esac
-  timeout -k 10 300 python bench.py --gpus 2 --steps 20 --warmup 5 --frames-total 200000 --global-batch 40000 --no-extras --cpu-seconds 0 2> "$O/bench_dp2_$mode.err" | tail -1 > "$O/bench_dp2_$mode.log" || { tail -5 "$O/bench_dp2_$mode.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --frames-total 200000 --global-batch 40000 --no-extras --cpu-seconds 0 2> "$O/bench_dp2_$mode.err" | tail -1 > "$O/bench_dp2_$mode.log" || { tail -5 "$O/bench_dp2_$mode.err"; exit 1; }
   python - "$O/bench_dp2_$mode.log" $mode <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())

@@ -11,7 +11,7 @@ cat "$O/ef16_time_$TAG.log"
 timeout -k 10 120 tools/build/ef16_probe > "$O/ef16_probe_$TAG.log" 2>&1 || { echo "probe failed"; tail -5 "$O/ef16_probe_$TAG.log"; exit 1; }
 sed -n 6,32p "$O/ef16_probe_$TAG.log"
 if [ "$2" != "nobench" ]; then
-timeout -k 10 500 python bench.py --cpu-seconds 0 > "$O/bench_$TAG.log" 2> "$O/bench_$TAG.err" || { echo "bench failed"; tail -5 "$O/bench_$TAG.err"; exit 1; }
+timeout -k 10 500 python bench.py --full --cpu-seconds 0 > "$O/bench_$TAG.log" 2> "$O/bench_$TAG.err" || { echo "bench failed"; tail -5 "$O/bench_$TAG.err"; exit 1; }
 python - "$O/bench_$TAG.log" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

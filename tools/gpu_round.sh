@@ -14,7 +14,7 @@ timeout -k 10 600 python tools/parity_errors.py "$TAG" > "$O/parity_$TAG.log" 2>
 tail -2 "$O/parity_$TAG.log"
 cp "$R/gpurun_out/${TAG}_parity_errors.json" "$O/" 2>/dev/null
 if [ -x tools/build/ef16_probe ]; then timeout -k 10 120 tools/build/ef16_probe > "$O/ef16_probe_$TAG.log" 2>&1 || { echo "probe failed"; tail -5 "$O/ef16_probe_$TAG.log"; exit 1; }; head -12 "$O/ef16_probe_$TAG.log"; fi
-timeout -k 10 500 python bench.py > "$O/bench_$TAG.log" 2> "$O/bench_$TAG.err" || { echo "bench failed"; tail -5 "$O/bench_$TAG.err"; exit 1; }
+timeout -k 10 500 python bench.py --full > "$O/bench_$TAG.log" 2> "$O/bench_$TAG.err" || { echo "bench failed"; tail -5 "$O/bench_$TAG.err"; exit 1; }
 python - "$O/bench_$TAG.log" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ cp gpurun_out/$TAG/kt/bench_kernel_stats.csv profiles/${TAG}_bench_kernel_stats.
 [ -f gpurun_out/$TAG/kt_k1/k1_kernel_stats.csv ] && cp gpurun_out/$TAG/kt_k1/k1_kernel_stats.csv profiles/${TAG}_k1_roofline_kernel_stats.csv
 for b in 2000 16000; do [ -f gpurun_out/$TAG/kt_c5_$b/c5_kernel_stats.csv ] && cp gpurun_out/$TAG/kt_c5_$b/c5_kernel_stats.csv profiles/${TAG}_c5_batch${b}_kernel_stats.csv; done
 (cd gpurun_out/$TAG && {
-  echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0   (avg us per launch, first 30 launches skipped)"
+  echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0   (avg us per launch, first 30 launches skipped)"
   python3 ../../tools/kstats.py kt/bench_kernel_trace.csv 30; echo
   echo "# rocprofv3 --kernel-trace --pmc FETCH_SIZE  (separate pass; KB per launch, uncorrected: gfx950 reports 1/2 of wide streaming reads)"
   python3 ../../tools/pmc_summary.py pmc_fetch/bench_counter_collection.csv; echo
@@ -23,7 +23,7 @@ for b in 2000 16000; do [ -f gpurun_out/$TAG/kt_c5_$b/c5_kernel_stats.csv ] && c
       python3 ../../tools/kstats.py kt_c5_$b/c5_kernel_trace.csv 10; echo
     fi
   done
-  echo "# python bench.py (full line incl. cpu_baseline)"; tail -1 bench_full.log
+  echo "# python bench.py --full (full line incl. cpu_baseline)"; tail -1 bench_full.log
 } > ../../profiles/${TAG}_bench_summary.txt)
 CVF_TAG=$TAG python3 - <<'PY'
 import csv, json, collections, re, os
@@ -37,7 +37,7 @@ def mean_counter(path, counter):
     return {k: sum(v)/len(v) for k, v in d.items()}
 f = mean_counter(f"gpurun_out/{TAG}/pmc_fetch/bench_counter_collection.csv", "FETCH_SIZE")
 w = mean_counter(f"gpurun_out/{TAG}/pmc_write/bench_counter_collection.csv", "WRITE_SIZE")
-out = {"_source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes) -- python3 bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-extras; mean per launch, KiB",
+out = {"_source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes) -- python3 bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --no-extras; mean per launch, KiB",
        "_correction": "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024: gfx950 FETCH_SIZE counts 128-B read requests as 64 B for 16-B-per-lane streaming loads (MI355X_MICROARCH.md, HBM); other access widths are uncalibrated, Infinity-Cache hits are included",
        "kernels": {k: {"FETCH_SIZE_KiB": f[k], "WRITE_SIZE_KiB": w.get(k, 0.0)} for k in f if not k.startswith("at::") and not k.startswith("__amd") and not k.startswith("Cijk")}}
 # the align+feature kernel alone at the config-5 shape (tools/bench_k1_c5.py 20000: two launch flavours per pass - features only,
