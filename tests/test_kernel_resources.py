@@ -6,38 +6,15 @@ did not notice for most of the round - the kernel kept its results and lost 7 % 
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "colvars-finder_amd", "csrc")
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def kernels_of(obj, tmp_path):
-    """{mangled kernel name: {vgpr_count, private_segment_fixed_size, ...}} of the gfx950 code object inside a host object file."""
-    fat, co = str(tmp_path / "x.fatbin"), str(tmp_path / "x.co")
-    subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-    out = {}
-    for block in re.split(r"\n\s+- \.agpr_count:|\n\s+- \.args:", notes)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if name is None:
-            continue
-        out[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|agpr_count|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count):\s+(\d+)", block)}
-    return out
+from tests.codeobj import CSRC, LLVM, built_objects, kernels_of  # noqa: F401  (the other resource tests import them from here)
 
 
 @pytest.fixture(scope="module")
 def built():
-    subprocess.run(["make", "-C", CSRC, "-j4"], check=True, capture_output=True)
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
-        if not os.path.exists(f"{LLVM}/{tool}"):
-            pytest.skip(f"{tool} not in this image")
-    return os.path.join(CSRC, "build")
+    return built_objects()
 
 
 def test_alignment_kernels_keep_their_occupancy(built, tmp_path):
