@@ -658,7 +658,7 @@ class TrainingTask(ABC):
 class _EFWorkspace:
     """Device buffers of one batch size (all sizes follow include/cvf.h)."""
 
-    def __init__(self, B, k, d_r, n_params, lag, mlp_desc, device, ef16=False):
+    def __init__(self, B, k, d_r, n_params, lag, mlp_desc, device, ef16=False, general=False):
         lib = _hip.lib()
         T = _hip.ntiles(B)
         Tt = 2 * T if lag > 0 else T
@@ -685,9 +685,11 @@ class _EFWorkspace:
         self.coef = torch.empty(4 * k + k * k, **f64)
         self._k1_scratch, self.k1_scratch_checked = [None, None], False   # large-molecule alignment scratch, sized on first use
         # hidden activations handed from the forward kernel to the backward kernel (0 floats: shape without hand-off)
-        n_saved = lib.cvf_ef16_saved_floats(mlp_desc, Tt) if ef16 else lib.cvf_ef_saved_floats(mlp_desc, Tt)
+        # (the general route, csrc/ef_general.hip: activations, the sweep of g, the tangent chain and the adjoints of every layer)
+        n_saved = (lib.cvf_ef_general_saved_floats(mlp_desc, Tt, lag) if general else
+                   lib.cvf_ef16_saved_floats(mlp_desc, Tt) if ef16 else lib.cvf_ef_saved_floats(mlp_desc, Tt))
         self.saved = torch.empty(n_saved, **f32) if n_saved > 0 else None
-        self.slab_rows = lib.cvf_ef_backward_slab_rows(Tt)
+        self.slab_rows = lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt)
         self.slab = torch.empty(self.slab_rows * n_params, **f32)
 
     feat = property(lambda self: self._feat[self.slot])
@@ -725,7 +727,8 @@ class EigenFunctionTask(TrainingTask):
     def __init__(self, traj_obj, pp_layer, model, model_path, alpha, eig_weights, diag_coeff=None, beta=1.0, lag_tau=0,
                  learning_rate=0.01, load_model_filename=None, save_model_every_step=10, sort_eigvals_in_training=True,
                  k=1, batch_size=1000, num_epochs=10, test_ratio=0.2, optimizer_name='Adam',
-                 device=torch.device('cuda'), plot_class=None, plot_frequency=0, verbose=True, debug_mode=True):
+                 device=torch.device('cuda'), plot_class=None, plot_frequency=0, verbose=True, debug_mode=True,
+                 general_nets=False):
         super().__init__(traj_obj, pp_layer, model, model_path, learning_rate, load_model_filename, save_model_every_step,
                          k, batch_size, num_epochs, test_ratio, optimizer_name, device, plot_class, plot_frequency,
                          verbose, debug_mode)
@@ -745,7 +748,15 @@ class EigenFunctionTask(TrainingTask):
         if self.verbose:
             print('\nEigenfunctions:\n', self.model, flush=True)
         self.init_model_and_optimizer()
-        if self._flat.packed is None:   # no matrix-core kernel instance for this architecture: say so here, not at the first step
+        # general_nets: shapes without a kernel instance run the per-layer launches of csrc/ef_general.hip (shapes WITH an
+        # instance, padded layouts included, keep their kernels: the option changes nothing for them)
+        self._general = False
+        if self._flat.packed is None and general_nets:
+            if not _hip.lib().cvf_ef_general_supported(self._flat.desc):
+                raise NotImplementedError(f"EigenFunctionTask(general_nets=True) on MI355X: {_hip.lib().cvf_last_error().decode()} "
+                                          "(csrc/ef_general.hip: cvf_ef_general_supported)")
+            self._general = True
+        if self._flat.packed is None and not self._general:   # no matrix-core kernel instance: say so here, not at the first step
             d = self._flat.desc
             raise NotImplementedError(
                 "EigenFunctionTask on MI355X: no kernel instance for nets with layer widths "
@@ -754,7 +765,8 @@ class EigenFunctionTask(TrainingTask):
                 f"(kernel widths {_hip.EF_HIDDEN_WIDTHS}, for 4 or 5 hidden layers 20 and 32; "
                 f"other widths are zero-padded to the next one - not with Sigmoid / Softplus, whose padding would not stay zero), "
                 f"scalar output, ONE activation of include/cvf.h after every hidden layer, k <= {_hip.MAX_NETS} "
-                "(csrc/ef_mfma.hip: ef_shape / ef_dispatch).")
+                "(csrc/ef_mfma.hip: ef_shape / ef_dispatch). Pass general_nets=True to run other shapes on the per-layer "
+                "kernels of csrc/ef_general.hip.")
 
         # The frames stay resident in HBM (core.py:343-344 keeps CPU copies and moves every batch, core.py:500).  One process:
         # the whole trajectory.  Data-parallel job (one process per GPU): NOT here - train() uploads only the rows of this
@@ -873,7 +885,7 @@ class EigenFunctionTask(TrainingTask):
         ws = self._ws.get(B)
         if ws is None:
             ws = self._ws[B] = _EFWorkspace(B, self.k, self._pp.d_r, self._flat.n, self.lag_idx, self._flat.desc, self.device,
-                                            ef16=self._use_ef16())
+                                            ef16=self._use_ef16(), general=self._general)
         return ws
 
     def _use_ef16(self):
@@ -995,6 +1007,9 @@ class EigenFunctionTask(TrainingTask):
         if with_tr:
             self._call("cvf_ef_align_fwd", lib.cvf_ef_align_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X),
                        P(X_lag), B, P(ws.y), P(ws.saved), s)
+        elif self._general:
+            self._call("cvf_ef_general_fwd", lib.cvf_ef_general_fwd, fl.desc, P(fl.theta), P(ws.feat), ws.Tt, P(ws.y),
+                       P(ws.g) if lag == 0 else None, P(ws.saved), s)
         else:
             self._call("cvf_ef_mlp_fwd", lib.cvf_ef_mlp_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), ws.Tt, P(ws.y),
                        P(ws.g) if lag == 0 else None, P(ws.saved), s)
@@ -1023,12 +1038,17 @@ class EigenFunctionTask(TrainingTask):
             self._call("cvf_ef16_backward", lib.cvf_ef16_backward, self._cfg, fl.desc, P(fl.theta), P(fl.packed), ws.B, P(w),
                        P(ws.feat), P(ws.y), P(ws.q), P(ws.coef), P(ws.slab),
                        P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
+        elif self._general:
+            self._call("cvf_ef_general_backward", lib.cvf_ef_general_backward, self._cfg, fl.desc, P(fl.theta), ws.B, P(w), P(w_lag),
+                       P(ws.feat), P(ws.y), P(ws.q) if self.lag_idx == 0 else None, P(ws.coef), P(ws.slab),
+                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
         else:
             self._call("cvf_ef_backward", lib.cvf_ef_backward, self._cfg, fl.desc, P(fl.theta), P(fl.packed), ws.B, P(w), P(w_lag),
                        P(ws.feat), P(ws.y), P(ws.q) if self.lag_idx == 0 else None, P(ws.coef), P(ws.slab),
                        P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
         local = self._local_only or self._grad_local
-        comm = None if local else _dist.fused_comm()
+        # (the general route's gradient exceeds the peer-to-peer window of cvf_slab_reduce_dp: slab reduction + all-reduce)
+        comm = None if local or self._general else _dist.fused_comm()
         if comm is not None:   # sum of the slab rows -> collective #2 -> (train_step) the identical Adam update: one launch
             adam = self.optimizer.fused_args() if advance else None
             self._call("cvf_slab_reduce_dp", lib.cvf_slab_reduce_dp, P(ws.slab), ws.slab_rows, fl.n, P(fl.grad), adam, comm, _hip.stream())

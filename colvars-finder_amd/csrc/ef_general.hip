@@ -1,0 +1,555 @@
+// K4a / K4b for eigenfunction nets of ANY shape (cvf_ef_general_*): 1 to 11 hidden layers of any widths, one of the
+// activation codes of include/cvf.h after each hidden layer, scalar output, k <= CVF_MAX_NETS nets side by side
+// (colvarsfinder.nn.EigenFunctions, nn.py:242-293).  The instance kernels of ef_mfma.hip keep a whole 64-frame chain in
+// registers, which ties them to compiled widths; here every product of the step is ONE launch over all tiles and nets:
+//
+//   efg_layer_kernel  [M x K] x [K x 64 frames] per (tile, 64-row block, net) with the weights W (or W^T) as the A operand
+//                     and the activations as the B operand, an elementwise transform of B on its way to LDS (sigma'(h) .* x)
+//                     and the activation or the adjoint's combination fused into the epilogue;
+//   efg_wgrad_kernel  the weight-gradient products, K = frames: [zbar_l | d_l] x [h_{l-1} ; 1 | tdot_{l-1} ; 0]^T, the
+//                     tiles split over a fixed number of slab rows (row rho sums tiles rho, rho + R, ... in that order);
+//   efg_coef_kernel   the per-frame adjoints of y (alpha) and of q.g (gamma) from the loss coefficients;
+//   efg_top_kernel    the adjoints of the last hidden layer (its "incoming" product W_NH^T is a broadcast).
+//
+// Mathematics (net i, hidden layers l = 0..NH-1, output layer NH, h_{-1} = r, sigma' / sigma'' through the output h):
+//   forward     z_l = W_l h_{l-1} + b_l, h_l = sigma(z_l), y = W_NH h_{NH-1} + b_NH
+//   g = dy/dr   u_{NH-1} = W_NH^T, delta_l = sigma'_l .* u_l, u_{l-1} = W_l^T delta_l, g = u_{-1}
+//   tangent     zdot_0 = W_0 q, zdot_l = W_l (sigma'_{l-1} .* zdot_{l-1})            (tdot_l = sigma'_l .* zdot_l)
+//   adjoints    zbar_{NH-1} = sigma'_{NH-1} .* (alpha W_NH^T) + gamma sigma''_{NH-1} .* zdot_{NH-1} .* u_{NH-1}
+//               zbar_{l-1}  = sigma'_{l-1} .* (W_l^T zbar_l) + gamma sigma''_{l-1} .* zdot_{l-1} .* u_{l-1},  d_l = gamma sigma'_l .* u_l
+//   gradient    dW_l = sum_frames zbar_l (x) h_{l-1} + d_l (x) tdot_{l-1},  db_l = sum_frames zbar_l   (zbar_NH = alpha, d_NH = gamma)
+// (the formula of ef_mfma.hip's header; transfer mode has gamma = 0 and no g / tangent).
+//
+// All products run on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation.  The hand-off between layers goes through
+// the `saved` buffer in HBM (layout: efg_layout).  No atomics: every slab entry is written by one thread, and the sum order
+// of every entry is fixed by the grid, so two runs on the same inputs give the same bits.
+#include "cvf_common.hpp"
+#include <stdio.h>
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+constexpr int kMaxWidth = 4096;     // widest layer cvf_ef_general_supported() accepts (d0 up to kMaxD0)
+constexpr int kMaxD0 = 65536;
+constexpr int64_t kSlabBytes = 128ll << 20;   // slab budget: rows = 128 MiB / (4 n_params), at least 1, at most kMaxRows
+constexpr int kMaxRows = 256;
+
+// a tiled tensor over (net, tile, row, lane): element = p[net * ns + tile * ts + row * 64 + lane]
+struct EfgView {
+  float* p;
+  int64_t ts, ns;
+};
+
+__device__ __forceinline__ float* at(const EfgView& v, int net, int64_t tile, int row) {
+  return v.p + net * v.ns + tile * v.ts + (int64_t)row * CVF_TILE;
+}
+
+enum { EPI_STORE = 0, EPI_ACT = 1, EPI_BWD_GEN = 2, EPI_BWD_TR = 3 };
+
+struct EfgLayerArgs {
+  int layer;     // Linear layer whose weights form the A operand
+  int trans;     // 0: A = W_layer [M = dims[layer+1]][K = dims[layer]];  1: A = W_layer^T [M = dims[layer]][K = dims[layer+1]]
+  int M, K;
+  int bias;      // add b_layer in the epilogue (EPI_STORE / EPI_ACT)
+  int epi;
+  int act_x;     // B operand = sigma'(xh) .* x with this activation's sigma' (xh.p != NULL)
+  int act_e;     // activation of the epilogue (EPI_ACT: sigma; EPI_BWD_*: sigma', sigma'' of eh)
+  int x_bcast;   // B operand row k = W_{n_layers-1}[0][k] for every frame (u_{NH-1} = W_NH^T) instead of x
+  EfgView x, xh, out, eh, eu, gam;
+};
+
+// out[m][frame] (64 x 64 block) = A[m][:] . op(B)[:][frame] for one (tile, row block, net); 4 waves of 32 x 32
+constexpr int kKC = 32;          // K per LDS stage
+constexpr int kPitch = 80;       // LDS pitch of the k-major images (a fragment read spans 4 k-rows of 16 consecutive words)
+__global__ __launch_bounds__(256) void efg_layer_kernel(cvf_mlp_desc mlp, const float* __restrict__ theta, EfgLayerArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[kKC * kPitch];   // [k][m]
+  __shared__ __attribute__((aligned(16))) float Bs[kKC * kPitch];   // [k][frame]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t tile = blockIdx.x;
+  const int m0 = blockIdx.y * 64, net = blockIdx.z;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int col = lane & 15, kq = lane >> 4;
+  const float* W = theta + mlp.w_off[net][a.layer];
+  const int ldw = mlp.dims[a.layer];
+  const float* xb = a.x_bcast ? theta + mlp.w_off[net][mlp.n_layers - 1] : nullptr;
+  const float* xp = a.x_bcast ? nullptr : at(a.x, net, tile, 0);
+  const float* hp = a.xh.p != nullptr ? at(a.xh, net, tile, 0) : nullptr;
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  for (int k0 = 0; k0 < a.K; k0 += kKC) {
+    // stage A (weights; m runs over the lanes) and B (activations; frames run over the lanes)
+#pragma unroll
+    for (int it = 0; it < kKC / 4; ++it) {
+      const int kk = wave + 4 * it, k = k0 + kk, m = m0 + lane;
+      float av = 0.0f;
+      if (m < a.M && k < a.K) av = a.trans ? W[(int64_t)k * ldw + m] : W[(int64_t)m * ldw + k];
+      As[kk * kPitch + lane] = av;
+      float bv = 0.0f;
+      if (k < a.K) {
+        bv = xb != nullptr ? xb[k] : xp[(int64_t)k * CVF_TILE + lane];
+        if (hp != nullptr) bv *= cvf_act_d1(a.act_x, hp[(int64_t)k * CVF_TILE + lane]);
+      }
+      Bs[kk * kPitch + lane] = bv;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < kKC; ks += 4) {
+      const int kr = (ks + kq) * kPitch;
+      const float a0 = As[kr + wm + col], a1 = As[kr + wm + 16 + col];
+      const float b0 = Bs[kr + wn + col], b1 = Bs[kr + wn + 16 + col];
+      acc[0][0] = mfma4(a0, b0, acc[0][0]);
+      acc[0][1] = mfma4(a0, b1, acc[0][1]);
+      acc[1][0] = mfma4(a1, b0, acc[1][0]);
+      acc[1][1] = mfma4(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: C row = 4 * (lane >> 4) + r of each 16 x 16 block, column (frame) = lane & 15
+  const float* bias = a.bias ? theta + mlp.b_off[net][a.layer] : nullptr;
+  const float* gp = a.epi == EPI_BWD_GEN ? at(a.gam, net, tile, 0) : nullptr;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm + 16 * i + 4 * kq + r;
+        const int f = wn + 16 * j + col;
+        if (m >= a.M) continue;
+        float v = acc[i][j][r];
+        float* o = at(a.out, net, tile, m) + f;
+        if (a.epi == EPI_STORE || a.epi == EPI_ACT) {
+          if (bias != nullptr) v += bias[m];
+          *o = a.epi == EPI_ACT ? cvf_act(a.act_e, v) : v;
+        } else {
+          const float h = at(a.eh, net, tile, m)[f];
+          const float s1 = cvf_act_d1(a.act_e, h);
+          if (a.epi == EPI_BWD_TR) {
+            *o = s1 * v;
+          } else {   // o holds zdot (read, then overwritten by zbar); eu holds u (overwritten by d)
+            float* up = at(a.eu, net, tile, m) + f;
+            const float g = gp[f], u = *up, zd = *o;
+            *o = s1 * v + g * cvf_act_d2(a.act_e, h) * zd * u;
+            *up = g * s1 * u;
+          }
+        }
+      }
+}
+
+struct EfgGradArgs {
+  int layer;        // Linear layer whose gradient this launch forms: C [Mo = dims[layer+1]][Ki + 1 = dims[layer] + 1]
+  int Mo, Ki;
+  int64_t n_tiles, T, B;
+  int rows;         // slab rows R: row rho sums tiles rho, rho + R, ... in that order
+  int act_b2;       // b2h.p != NULL: second B operand = sigma'(b2h) .* b2
+  int64_t n_params;
+  EfgView a1, b1, a2, b2, b2h;   // a2.p == NULL: one part (transfer mode)
+};
+
+constexpr int kGP = 68;   // LDS pitch of the [row][frame] images (a fragment read spans 16 rows x 4 consecutive frames)
+__global__ __launch_bounds__(256) void efg_wgrad_kernel(const cvf_mlp_desc mlp, EfgGradArgs a, float* __restrict__ slab) {
+  __shared__ __attribute__((aligned(16))) float As[64 * kGP];   // [out row][frame]
+  __shared__ __attribute__((aligned(16))) float Bs[64 * kGP];   // [in column][frame]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int rho = blockIdx.x, net = blockIdx.z;
+  const int nbn = (a.Ki + 1 + 63) / 64;
+  const int o0 = (blockIdx.y / nbn) * 64, i0 = (blockIdx.y % nbn) * 64;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int col = lane & 15, kq = lane >> 4;
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  const int parts = a.a2.p != nullptr ? 2 : 1;
+  for (int64_t tile = rho; tile < a.n_tiles; tile += a.rows) {
+    const int64_t t0 = tile >= a.T ? tile - a.T : tile;
+    const bool valid = t0 * CVF_TILE + lane < a.B;   // padded frames contribute nothing
+    for (int part = 0; part < parts; ++part) {
+      const EfgView& av = part == 0 ? a.a1 : a.a2;
+      const EfgView& bv = part == 0 ? a.b1 : a.b2;
+      const float* ap = at(av, net, tile, 0);
+      const float* bp = at(bv, net, tile, 0);
+      const float* hp = part == 1 && a.b2h.p != nullptr ? at(a.b2h, net, tile, 0) : nullptr;
+#pragma unroll 4
+      for (int it = 0; it < 16; ++it) {
+        const int rr = wave + 4 * it;
+        const int o = o0 + rr, i = i0 + rr;
+        As[rr * kGP + lane] = valid && o < a.Mo ? ap[(int64_t)o * CVF_TILE + lane] : 0.0f;
+        float x = 0.0f;
+        if (valid) {
+          if (i < a.Ki) {
+            x = bp[(int64_t)i * CVF_TILE + lane];
+            if (hp != nullptr) x *= cvf_act_d1(a.act_b2, hp[(int64_t)i * CVF_TILE + lane]);
+          } else if (i == a.Ki && part == 0) {
+            x = 1.0f;   // the bias column: [h ; 1] (the tangent part has [tdot ; 0])
+          }
+        }
+        Bs[rr * kGP + lane] = x;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int ks = 0; ks < 64; ks += 4) {
+        const int kf = ks + kq;
+        const float a0 = As[(wm + col) * kGP + kf], a1 = As[(wm + 16 + col) * kGP + kf];
+        const float b0 = Bs[(wn + col) * kGP + kf], b1 = Bs[(wn + 16 + col) * kGP + kf];
+        acc[0][0] = mfma4(a0, b0, acc[0][0]);
+        acc[0][1] = mfma4(a0, b1, acc[0][1]);
+        acc[1][0] = mfma4(a1, b0, acc[1][0]);
+        acc[1][1] = mfma4(a1, b1, acc[1][1]);
+      }
+      __syncthreads();
+    }
+  }
+
+  float* row = slab + (int64_t)rho * a.n_params;
+  const int wo = mlp.w_off[net][a.layer], bo = mlp.b_off[net][a.layer];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = o0 + wm + 16 * i + 4 * kq + r;
+        const int c = i0 + wn + 16 * j + col;
+        if (o >= a.Mo || c > a.Ki) continue;
+        if (c < a.Ki) row[wo + (int64_t)o * a.Ki + c] = acc[i][j][r];
+        else row[bo + o] = acc[i][j][r];
+      }
+}
+
+// alpha = d loss / d y per frame (and gamma = d loss / d (q . g) in generator mode); the layout of `coef` as cvf_ef_backward
+// reads it (ef_mfma.hip: gS1, gS2, gEt, gS1', gS2')
+struct EfgCoefArgs {
+  int k, lag_idx;
+  int64_t B, T, n_tiles;
+  EfgView alpha, gamma;
+};
+
+__global__ __launch_bounds__(64) void efg_coef_kernel(EfgCoefArgs a, const float* __restrict__ w, const float* __restrict__ w_lag,
+                                                      const float* __restrict__ y_tiled, const double* __restrict__ coef,
+                                                      int32_t* __restrict__ step) {
+  const int lane = threadIdx.x, net = blockIdx.y, k = a.k;
+  const int64_t tile = blockIdx.x;
+  const int pass = tile >= a.T ? 1 : 0;
+  const int64_t t0 = pass ? tile - a.T : tile;
+  const int64_t frame = t0 * CVF_TILE + lane;
+  const bool valid = frame < a.B;
+  const int64_t fc = valid ? frame : a.B - 1;
+  const float wb = valid ? w[fc] : 0.0f;
+  const double* gS1 = coef;
+  const double* gS2 = coef + k;
+  const double* gEt = coef + k + k * k;
+  const double* gS1l = coef + 2 * k + k * k;
+  const double* gS2l = coef + 3 * k + k * k;
+  const float* yb = y_tiled + t0 * k * CVF_TILE + lane;
+  float alpha, gamma = 0.0f;
+  if (a.lag_idx == 0) {
+    double s = gS1[net];
+    for (int j = 0; j < k; ++j) s += (j == net ? 2.0 : 1.0) * gS2[net * k + j] * (double)yb[j * CVF_TILE];
+    alpha = (float)((double)wb * s);
+    gamma = (float)(2.0 * (double)wb * gEt[net]);
+  } else {
+    const float* yl = y_tiled + (a.T + t0) * k * CVF_TILE + lane;
+    const double diff = (double)yl[net * CVF_TILE] - (double)yb[net * CVF_TILE];
+    const double tterm = 2.0 * (double)wb * gEt[net] * diff;
+    if (pass == 0) {
+      double s = gS1[net];
+      for (int j = 0; j < k; ++j) s += (j == net ? 2.0 : 1.0) * gS2[net * k + j] * (double)yb[j * CVF_TILE];
+      alpha = (float)((double)wb * s - tterm);
+    } else {
+      const float wlg = valid ? w_lag[fc] : 0.0f;
+      alpha = (float)((double)wlg * (gS1l[net] + 2.0 * gS2l[net] * (double)yl[net * CVF_TILE]) + tterm);
+    }
+  }
+  at(a.alpha, net, tile, 0)[lane] = alpha;
+  if (a.lag_idx == 0) at(a.gamma, net, tile, 0)[lane] = gamma;
+  if (step != nullptr && blockIdx.x == 0 && net == 0 && lane == 0) *step += 1;
+}
+
+// zbar_{NH-1} (in place of zdot_{NH-1} in generator mode) and d_{NH-1}: the incoming product W_NH^T is a broadcast
+struct EfgTopArgs {
+  int H, act, gen;
+  EfgView h, z, u, alpha, gamma;
+};
+
+__global__ __launch_bounds__(256) void efg_top_kernel(const cvf_mlp_desc mlp, const float* __restrict__ theta, EfgTopArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, net = blockIdx.y;
+  const int64_t tile = blockIdx.x;
+  const float* wl = theta + mlp.w_off[net][mlp.n_layers - 1];
+  const float al = at(a.alpha, net, tile, 0)[lane];
+  const float ga = a.gen ? at(a.gamma, net, tile, 0)[lane] : 0.0f;
+  for (int j = wave; j < a.H; j += 4) {
+    const float h = at(a.h, net, tile, j)[lane];
+    const float s1 = cvf_act_d1(a.act, h), wj = wl[j];
+    float* zp = at(a.z, net, tile, j) + lane;
+    if (a.gen) {
+      *zp = s1 * (al * wj) + ga * cvf_act_d2(a.act, h) * *zp * wj;
+      at(a.u, net, tile, j)[lane] = ga * s1 * wj;
+    } else {
+      *zp = s1 * (al * wj);
+    }
+  }
+}
+
+// ---- the `saved` buffer.  Generator mode (n_tiles = T): per hidden layer h_l, u_l (-> d_l), zdot_l (-> zbar_l), then alpha,
+// gamma.  Transfer mode (n_tiles = 2T): h_l per hidden layer, two ping-pong images of zbar (widest layer), alpha.
+// Every image is [net][tile][width][64].
+struct EfgLayout {
+  int64_t h[CVF_MAX_LAYERS], u[CVF_MAX_LAYERS], z[CVF_MAX_LAYERS], zb[2], alpha, gamma, total;
+};
+
+EfgLayout efg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles, bool gen) {
+  EfgLayout L = {};
+  const int NH = mlp->n_layers - 1;
+  const int64_t per = n_tiles * CVF_TILE * mlp->n_nets;   // floats of one row of every (net, tile)
+  int64_t pos = 0;
+  int maxH = 1;
+  for (int l = 0; l < NH; ++l) {
+    L.h[l] = pos;
+    pos += per * mlp->dims[l + 1];
+    maxH = mlp->dims[l + 1] > maxH ? mlp->dims[l + 1] : maxH;
+  }
+  if (gen) {
+    for (int l = 0; l < NH; ++l) {
+      L.u[l] = pos;
+      pos += per * mlp->dims[l + 1];
+      L.z[l] = pos;
+      pos += per * mlp->dims[l + 1];
+    }
+  } else {
+    for (int i = 0; i < 2; ++i) {
+      L.zb[i] = pos;
+      pos += per * maxH;
+    }
+  }
+  L.alpha = pos;
+  pos += per;
+  L.gamma = pos;
+  if (gen) pos += per;
+  L.total = pos;
+  return L;
+}
+
+EfgView img(float* saved, int64_t off, int64_t n_tiles, int width) {
+  return EfgView{saved + off, (int64_t)width * CVF_TILE, n_tiles * width * CVF_TILE};
+}
+
+const char* efg_why(const cvf_mlp_desc* mlp) {
+  static thread_local char buf[160];
+  if (mlp == nullptr) return "no net description";
+  if (mlp->n_nets < 1 || mlp->n_nets > CVF_MAX_NETS) {
+    snprintf(buf, sizeof buf, "%d nets: 1 to %d are supported", mlp->n_nets, CVF_MAX_NETS);
+    return buf;
+  }
+  if (mlp->n_layers < 2 || mlp->n_layers > CVF_MAX_LAYERS) {
+    snprintf(buf, sizeof buf, "%d hidden layers: 1 to %d are supported", mlp->n_layers - 1, CVF_MAX_LAYERS - 1);
+    return buf;
+  }
+  if (mlp->dims[mlp->n_layers] != 1) return "the nets' output must be a scalar";
+  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
+    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
+    return buf;
+  }
+  for (int l = 1; l < mlp->n_layers; ++l)
+    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
+      snprintf(buf, sizeof buf, "hidden layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
+      return buf;
+    }
+  for (int l = 0; l < mlp->n_layers; ++l) {
+    const int act = mlp->act[l];
+    if (act < CVF_ACT_NONE || act > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
+    if (l == mlp->n_layers - 1 && act != CVF_ACT_NONE) return "an activation after the output layer";
+  }
+  int64_t n = 0;
+  for (int l = 0; l < mlp->n_layers; ++l) n += (int64_t)mlp->dims[l + 1] * (mlp->dims[l] + 1);
+  if (n * mlp->n_nets != mlp->n_params) return "the flat buffer holds parameters outside the nets";
+  return nullptr;
+}
+
+int64_t efg_rows(const cvf_mlp_desc* mlp, int64_t n_tiles) {
+  int64_t r = kSlabBytes / (4 * (int64_t)(mlp->n_params > 0 ? mlp->n_params : 1));
+  r = r < 1 ? 1 : r > kMaxRows ? kMaxRows : r;
+  return n_tiles < r ? (n_tiles < 1 ? 1 : n_tiles) : r;
+}
+
+int launch_layer(const cvf_mlp_desc* mlp, const float* theta, const EfgLayerArgs& a, int64_t n_tiles, hipStream_t s) {
+  dim3 grid((unsigned)n_tiles, (unsigned)((a.M + 63) / 64), (unsigned)mlp->n_nets);
+  hipLaunchKernelGGL(efg_layer_kernel, grid, dim3(256), 0, s, *mlp, theta, a);
+  return cvf_check_launch("efg_layer_kernel");
+}
+
+EfgLayerArgs layer_args(int layer, int trans, int M, int K, int bias, int epi) {
+  EfgLayerArgs a = {};
+  a.layer = layer;
+  a.trans = trans;
+  a.M = M;
+  a.K = K;
+  a.bias = bias;
+  a.epi = epi;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int cvf_ef_general_supported(const cvf_mlp_desc* mlp) {
+  const char* why = efg_why(mlp);
+  if (why != nullptr) {
+    cvf_set_error("cvf_ef_general: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_ef_general_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles) {
+  if (efg_why(mlp) != nullptr) return 0;
+  return efg_rows(mlp, n_tiles);
+}
+
+extern "C" int64_t cvf_ef_general_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int lag_idx) {
+  if (efg_why(mlp) != nullptr || n_tiles < 1) return 0;
+  return efg_layout(mlp, n_tiles, lag_idx == 0).total;
+}
+
+extern "C" int cvf_ef_general_fwd(const cvf_mlp_desc* mlp, const float* theta, const float* feat_tiled, int64_t n_tiles,
+                                  float* y_tiled, float* g_tiled, float* saved, void* stream) {
+  const char* why = efg_why(mlp);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_fwd: %s", why);
+  CVF_REQUIRE(theta && feat_tiled && y_tiled && saved && n_tiles > 0, "cvf_ef_general_fwd: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const bool gen = g_tiled != nullptr;
+  const int NH = mlp->n_layers - 1, k = mlp->n_nets, D = mlp->dims[0];
+  const EfgLayout L = efg_layout(mlp, n_tiles, gen);
+  const EfgView feat{(float*)feat_tiled, (int64_t)D * CVF_TILE, 0};
+  // hidden layers: h_l = sigma(W_l h_{l-1} + b_l)
+  for (int l = 0; l < NH; ++l) {
+    EfgLayerArgs a = layer_args(l, 0, mlp->dims[l + 1], mlp->dims[l], 1, EPI_ACT);
+    a.act_e = mlp->act[l];
+    a.x = l == 0 ? feat : img(saved, L.h[l - 1], n_tiles, mlp->dims[l]);
+    a.out = img(saved, L.h[l], n_tiles, mlp->dims[l + 1]);
+    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+  }
+  {  // y = W_NH h_{NH-1} + b_NH  -> y_tiled [tile][net][64]
+    EfgLayerArgs a = layer_args(NH, 0, 1, mlp->dims[NH], 1, EPI_STORE);
+    a.x = img(saved, L.h[NH - 1], n_tiles, mlp->dims[NH]);
+    a.out = EfgView{y_tiled, (int64_t)k * CVF_TILE, CVF_TILE};
+    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+  }
+  if (!gen) return 0;
+  // g = dy/dr: u_{l-1} = W_l^T (sigma'(h_l) .* u_l), u_{NH-1} = W_NH^T (a broadcast); u_{-1} = g -> g_tiled [tile][net][d0][64]
+  for (int l = NH - 1; l >= 0; --l) {
+    EfgLayerArgs a = layer_args(l, 1, mlp->dims[l], mlp->dims[l + 1], 0, EPI_STORE);
+    a.act_x = mlp->act[l];
+    a.x_bcast = l == NH - 1;
+    if (l < NH - 1) a.x = img(saved, L.u[l], n_tiles, mlp->dims[l + 1]);
+    a.xh = img(saved, L.h[l], n_tiles, mlp->dims[l + 1]);
+    a.out = l > 0 ? img(saved, L.u[l - 1], n_tiles, mlp->dims[l]) : EfgView{g_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
+    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+  }
+  return 0;
+}
+
+extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float* theta, int64_t B,
+                                       const float* w, const float* w_lag, const float* feat_tiled, const float* y_tiled,
+                                       const float* q_tiled, const double* coef, float* slab, int32_t* step_count,
+                                       float* saved, void* stream) {
+  const char* why = efg_why(mlp);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_backward: %s", why);
+  CVF_REQUIRE(cfg && theta && w && feat_tiled && y_tiled && coef && slab && saved && B > 0, "cvf_ef_general_backward: bad argument");
+  CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_backward: cfg.k != number of nets");
+  const bool gen = cfg->lag_idx == 0;
+  CVF_REQUIRE(!gen || q_tiled, "cvf_ef_general_backward: generator mode needs q");
+  CVF_REQUIRE(gen || w_lag, "cvf_ef_general_backward: transfer mode needs w_lag");
+  hipStream_t s = (hipStream_t)stream;
+  const int NH = mlp->n_layers - 1, k = mlp->n_nets, D = mlp->dims[0];
+  const int64_t T = cvf_ntiles(B), nt = gen ? T : 2 * T;
+  const EfgLayout L = efg_layout(mlp, nt, gen);
+  const int R = (int)efg_rows(mlp, nt);
+  const EfgView feat{(float*)feat_tiled, (int64_t)D * CVF_TILE, 0};
+  const EfgView qv{(float*)q_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
+  auto H = [&](int l) { return img(saved, L.h[l], nt, mlp->dims[l + 1]); };
+  auto U = [&](int l) { return img(saved, L.u[l], nt, mlp->dims[l + 1]); };
+  auto Z = [&](int l) { return gen ? img(saved, L.z[l], nt, mlp->dims[l + 1]) : img(saved, L.zb[l & 1], nt, mlp->dims[l + 1]); };
+  const EfgView alpha = img(saved, L.alpha, nt, 1), gamma = img(saved, L.gamma, nt, 1);
+
+  // the tangent chain along q: zdot_0 = W_0 q, zdot_l = W_l (sigma'(h_{l-1}) .* zdot_{l-1})
+  if (gen)
+    for (int l = 0; l < NH; ++l) {
+      EfgLayerArgs a = layer_args(l, 0, mlp->dims[l + 1], mlp->dims[l], 0, EPI_STORE);
+      if (l == 0) {
+        a.x = qv;
+      } else {
+        a.x = Z(l - 1);
+        a.xh = H(l - 1);
+        a.act_x = mlp->act[l - 1];
+      }
+      a.out = Z(l);
+      if (launch_layer(mlp, theta, a, nt, s)) return -1;
+    }
+  {
+    EfgCoefArgs c = {k, cfg->lag_idx, B, T, nt, alpha, gamma};
+    hipLaunchKernelGGL(efg_coef_kernel, dim3((unsigned)nt, k), dim3(64), 0, s, c, w, w_lag, y_tiled, coef, step_count);
+    if (cvf_check_launch("efg_coef_kernel")) return -1;
+  }
+  // layer l's gradient from zbar_l, d_l (alpha, gamma for the output layer), h_{l-1} and tdot_{l-1} - before the adjoint of
+  // layer l-1 overwrites zdot_{l-1}
+  auto wgrad = [&](int l) {
+    EfgGradArgs g = {};
+    g.layer = l;
+    g.Mo = mlp->dims[l + 1];
+    g.Ki = mlp->dims[l];
+    g.n_tiles = nt;
+    g.T = T;
+    g.B = B;
+    g.rows = R;
+    g.n_params = mlp->n_params;
+    g.a1 = l == NH ? alpha : Z(l);
+    g.b1 = l == 0 ? feat : H(l - 1);
+    if (gen) {
+      g.a2 = l == NH ? gamma : U(l);
+      if (l == 0) {
+        g.b2 = qv;
+      } else {
+        g.b2 = Z(l - 1);
+        g.b2h = H(l - 1);
+        g.act_b2 = mlp->act[l - 1];
+      }
+    }
+    const int nb = ((g.Mo + 63) / 64) * ((g.Ki + 1 + 63) / 64);
+    hipLaunchKernelGGL(efg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb, k), dim3(256), 0, s, *mlp, g, slab);
+    return cvf_check_launch("efg_wgrad_kernel");
+  };
+  if (wgrad(NH)) return -1;
+  {
+    EfgTopArgs t = {mlp->dims[NH], mlp->act[NH - 1], gen ? 1 : 0, H(NH - 1), Z(NH - 1), gen ? U(NH - 1) : EfgView{}, alpha, gamma};
+    hipLaunchKernelGGL(efg_top_kernel, dim3((unsigned)nt, k), dim3(256), 0, s, *mlp, theta, t);
+    if (cvf_check_launch("efg_top_kernel")) return -1;
+  }
+  for (int l = NH - 1; l >= 0; --l) {
+    if (wgrad(l)) return -1;
+    if (l == 0) break;
+    // zbar_{l-1} = sigma'(h_{l-1}) .* (W_l^T zbar_l) [+ gamma sigma''(h_{l-1}) .* zdot_{l-1} .* u_{l-1};  d_{l-1}]
+    EfgLayerArgs a = layer_args(l, 1, mlp->dims[l], mlp->dims[l + 1], 0, gen ? EPI_BWD_GEN : EPI_BWD_TR);
+    a.x = Z(l);
+    a.out = Z(l - 1);
+    a.eh = H(l - 1);
+    a.act_e = mlp->act[l - 1];
+    if (gen) {
+      a.eu = U(l - 1);
+      a.gam = gamma;
+    }
+    if (launch_layer(mlp, theta, a, nt, s)) return -1;
+  }
+  return 0;
+}

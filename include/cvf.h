@@ -340,6 +340,28 @@ int cvf_ef_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float*
 int cvf_slab_reduce(const float* slab, int64_t n_rows, int64_t n_params, float* grad, const cvf_adam_args* adam,
                     void* stream); /* adam (may be NULL): apply the update in the same launch */
 
+/* --- K4a / K4b for nets of ANY shape (csrc/ef_general.hip; the reference takes any layer_dims, nn.py:29-59,242-293): one
+ * launch per layer and pass over all tiles and nets instead of a compiled chain per (width, depth) - 1 to CVF_MAX_LAYERS - 1
+ * hidden layers of 1 to 4096 units each (widths free to differ), d0 <= 65536, any act code of this header after each hidden
+ * layer, scalar output, 1 <= n_nets <= CVF_MAX_NETS, nets that fill the flat buffer.  Same inputs and outputs as
+ * cvf_ef_mlp_fwd / cvf_ef_backward (no fragment copy); `saved` is required and holds the activations, the backward sweep of g,
+ * the tangent chain and the adjoints (opaque layout).  No atomics: the same inputs give the same gradient bit for bit.
+ *  cvf_ef_general_supported   : 1, or 0 with the reason in cvf_last_error().
+ *  cvf_ef_general_slab_rows   : rows of the gradient slab [rows][n_params] (128 MiB at most unless one row is larger).
+ *  cvf_ef_general_saved_floats: floats of `saved`; n_tiles = T (lag_idx == 0) or 2T (transfer mode), as the two calls take.
+ *  cvf_ef_general_fwd         : replaces self.model(...) at core.py:403,414 and the autograd.grad of core.py:424: y_tiled
+ *                               [n_tiles][k][64] and, when g_tiled != NULL (generator mode), g_tiled [n_tiles][k][d0][64].
+ *  cvf_ef_general_backward    : replaces loss.backward() at core.py:517: slab rows of the flat gradient (follow with
+ *                               cvf_slab_reduce); step_count as cvf_ef_backward. */
+int cvf_ef_general_supported(const cvf_mlp_desc* mlp);
+int64_t cvf_ef_general_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles);
+int64_t cvf_ef_general_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int lag_idx);
+int cvf_ef_general_fwd(const cvf_mlp_desc* mlp, const float* theta, const float* feat_tiled, int64_t n_tiles, float* y_tiled,
+                       float* g_tiled, float* saved, void* stream);
+int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float* theta, int64_t B, const float* w,
+                            const float* w_lag, const float* feat_tiled, const float* y_tiled, const float* q_tiled,
+                            const double* coef, float* slab, int32_t* step_count, float* saved, void* stream);
+
 /* --- AutoEncoder: weighted reconstruction loss and its parameter gradient in one pass
  * (core.py:664-666,708).  feat_rows [n][d0] row-major (the precomputed feature
  * trajectory of core.py:635); idx NULL or [B] frame indices into it; w [B]; inv_wsum =
