@@ -1,5 +1,4 @@
-// Per-lane Kabsch rotation (fp32 guess + fp64 polish) and the feature map + its derivatives.
-// One lane = one frame; the frame's coordinates sit in LDS (load_x_tile layout).
+// Per-lane Kabsch rotation (fp32 guess + fp64 polish) and the K^-1 of its derivative.  (The feature map: cvf_features.hpp.)
 #pragma once
 #include "cvf_common.hpp"
 
@@ -294,66 +293,4 @@ CVF_HD void kabsch_from_H(const double (&H)[3][3], KabschOut& out) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) out.Kinv[i] = (float)Kinv[i];
   }
-}
-
-// ------------------------------------------------------------------------------------
-// Invariant features on raw coordinates.  `at(a)` returns atom a of this lane's frame.
-// grad_* return the gradient vectors w.r.t. each atom of the *scalar(s)* the feature
-// emits; for the dihedral in (cos,sin) mode the two outputs share dphi: d cos = -sin dphi,
-// d sin = cos dphi.
-// ------------------------------------------------------------------------------------
-struct BondG {
-  float val;
-  V3 ga, gb;
-};
-__device__ __forceinline__ BondG bond_eval(V3 xa, V3 xb) {
-  V3 r = xb - xa;
-  float d = sqrtf(dot(r, r));
-  float inv = 1.0f / d;
-  BondG o;
-  o.val = d;
-  o.gb = inv * r;
-  o.ga = (-inv) * r;
-  return o;
-}
-
-struct AngleG {
-  float cs;  // cos of the angle at b
-  V3 ga, gb, gc;  // gradient of cos
-};
-__device__ __forceinline__ AngleG angle_eval(V3 xa, V3 xb, V3 xc) {
-  V3 r1 = xa - xb, r2 = xc - xb;
-  float l1 = sqrtf(dot(r1, r1)), l2 = sqrtf(dot(r2, r2));
-  float inv12 = 1.0f / (l1 * l2);
-  float cs = dot(r1, r2) * inv12;
-  AngleG o;
-  o.cs = cs;
-  o.ga = inv12 * r2 - (cs / (l1 * l1)) * r1;
-  o.gc = inv12 * r1 - (cs / (l2 * l2)) * r2;
-  o.gb = (-1.0f) * (o.ga + o.gc);
-  return o;
-}
-
-struct DihedralG {
-  float cs, sn;
-  V3 g1, g2, g3, g4;  // gradient of phi
-  float p, q;         // g2 = (-1 - p) g1 + q g4,  g3 = p g1 + (-1 - q) g4
-};
-__device__ __forceinline__ DihedralG dihedral_eval(V3 x1, V3 x2, V3 x3, V3 x4) {
-  V3 b1 = x2 - x1, b2 = x3 - x2, b3 = x4 - x3;
-  V3 n1 = cross(b1, b2), n2 = cross(b2, b3);
-  float n1sq = dot(n1, n1), n2sq = dot(n2, n2), b2sq = dot(b2, b2);
-  float l2 = sqrtf(b2sq);
-  float inv = 1.0f / sqrtf(n1sq * n2sq);
-  DihedralG o;
-  o.cs = dot(n1, n2) * inv;
-  o.sn = dot(n1, b3) * l2 * inv;
-  o.g1 = (-l2 / n1sq) * n1;
-  o.g4 = (l2 / n2sq) * n2;
-  float p = dot(b1, b2) / b2sq, q = dot(b3, b2) / b2sq;
-  o.g2 = (-1.0f - p) * o.g1 + q * o.g4;
-  o.g3 = p * o.g1 + (-1.0f - q) * o.g4;
-  o.p = p;
-  o.q = q;
-  return o;
 }

@@ -3,18 +3,11 @@
 // once into LDS with coalesced 16-byte global loads (HBM traffic = 12 B/atom/frame in,
 // 4 B/feature/frame out); the 3x3 covariance, its eigen-decomposition and the small
 // solves run per lane in fp64, so all 64 lanes stay busy for small molecules.
+#include "cvf_features.hpp"
 #include "cvf_kabsch.hpp"
 #include "cvf_metric.hpp"
 
 namespace {
-
-struct Rec {
-  int type, a0, a1, a2, a3, out;
-};
-__device__ __forceinline__ Rec load_rec(const int32_t* rec, int r) {
-  const int32_t* p = rec + 6 * r;
-  return Rec{p[0], p[1], p[2], p[3], p[4], p[5]};
-}
 
 // The layer's small tables (feature records, align indices, reference coordinates) are copied to LDS once
 // per block: with one wave per SIMD a scalar-cache miss per loop iteration (~200+ cycles, nothing to overlap
@@ -60,7 +53,6 @@ __device__ __forceinline__ Tables tables_commit(const cvf_pp_desc& pp, const Tab
   int32_t* alL = L + 6 * pp.n_rec;
   return Tables{L, alL, reinterpret_cast<const float*>(alL + pp.n_align)};
 }
-__device__ __forceinline__ V3 atom(const float* my, int a) { return V3{my[3 * a], my[3 * a + 1], my[3 * a + 2]}; }
 
 // per-lane alignment: centroid (fp64), covariance (fp64), rotation, Kinv
 // CONTIG: align atom b is frame atom b (CVF_PP_ALIGN_CONTIG): every LDS address is affine in the loop
@@ -157,23 +149,13 @@ __global__ __launch_bounds__(64) void k1_align_kernel(cvf_pp_desc pp, const floa
   for (int r = 0; r < pp.n_rec; ++r) {
     const Rec rc = load_rec(tb.rec, r);
     if (rc.type == CVF_FEAT_POSITION) {
-      const V3 al = row_times(centred(my, rc.a0, c), ko.R);
+      const V3 al = row_times(centred(my, rc.a[0], c), ko.R);
       emit(rc.out, al.x);
       emit(rc.out + 1, al.y);
       emit(rc.out + 2, al.z);
-    } else if (rc.type == CVF_FEAT_BOND) {
-      emit(rc.out, bond_eval(atom(my, rc.a0), atom(my, rc.a1)).val);
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const float cs = angle_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2)).cs;
-      emit(rc.out, pp.use_angle_value ? acosf(cs) : cs);
     } else {
-      const DihedralG dg = dihedral_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2), atom(my, rc.a3));
-      if (pp.use_angle_value) {
-        emit(rc.out, atan2f(dg.sn, dg.cs));
-      } else {
-        emit(rc.out, dg.cs);
-        emit(rc.out + 1, dg.sn);
-      }
+      invariant_values(rc.type, pp.use_angle_value, [&](int k) { return atom_xyz(my, rc.a[k]); },
+                       [&](int j, float v) { emit(rc.out + j, v); });
     }
   }
 }
@@ -510,51 +492,19 @@ __global__ __launch_bounds__(64) void metric_align_kernel(cvf_pp_desc pp, const 
     if (rc.type == CVF_FEAT_POSITION) {
       const V3 g = v3(gt[rc.out * CVF_TILE], gt[(rc.out + 1) * CVF_TILE], gt[(rc.out + 2) * CVF_TILE]);
       const V3 p = mat_times(R, g);
-      addG(rc.a0, p);
+      addG(rc.a[0], p);
       sump = sump + p;
-      const V3 xc = centred(my, rc.a0, c);
-      M[0] += xc.x * g.x; M[1] += xc.x * g.y; M[2] += xc.x * g.z;
-      M[3] += xc.y * g.x; M[4] += xc.y * g.y; M[5] += xc.y * g.z;
-      M[6] += xc.z * g.x; M[7] += xc.z * g.y; M[8] += xc.z * g.z;
-    } else if (rc.type == CVF_FEAT_BOND) {
-      const BondG e = bond_eval(atom(my, rc.a0), atom(my, rc.a1));
-      const float gs = gt[rc.out * CVF_TILE];
-      addG(rc.a0, gs * e.ga);
-      addG(rc.a1, gs * e.gb);
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const AngleG e = angle_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2));
-      float gs = gt[rc.out * CVF_TILE];
-      if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
-      addG(rc.a0, gs * e.ga);
-      addG(rc.a1, gs * e.gb);
-      addG(rc.a2, gs * e.gc);
+      outer_add(M, centred(my, rc.a[0], c), g);
     } else {
-      const DihedralG e = dihedral_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2), atom(my, rc.a3));
-      const float gs = pp.use_angle_value ? gt[rc.out * CVF_TILE]
-                                          : (gt[(rc.out + 1) * CVF_TILE] * e.cs - gt[rc.out * CVF_TILE] * e.sn);
-      addG(rc.a0, gs * e.g1);
-      addG(rc.a1, gs * e.g2);
-      addG(rc.a2, gs * e.g3);
-      addG(rc.a3, gs * e.g4);
+      invariant_vjp(rc.type, pp.use_angle_value, 1, [&](int k) { return atom_xyz(my, rc.a[k]); },
+                    [&](int, int j) { return gt[(rc.out + j) * CVF_TILE]; }, [&](int, int k, V3 v) { addG(rc.a[k], v); });
     }
   }
   const float inv_nal = 1.0f / (float)pp.n_align;
   if (pp.has_position) {
-    // s = Kinv ax(R^T M);  Z = R [s]x;  G_b += Z ref_b - sum_p / n_align   (b over align atoms)
-    float T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * M[j] + R[3 + i] * M[3 + j] + R[6 + i] * M[6 + j];
-    const V3 s = sym_times(Kinv, v3(T[7] - T[5], T[2] - T[6], T[3] - T[1]));
-    // [s]x rows: (0,-sz,sy), (sz,0,-sx), (-sy,sx,0)
+    // G_b += Z ref_b - sum_p / n_align   (b over align atoms)
     float Z[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      Z[3 * i + 0] = R[3 * i + 1] * s.z - R[3 * i + 2] * s.y;
-      Z[3 * i + 1] = -R[3 * i + 0] * s.z + R[3 * i + 2] * s.x;
-      Z[3 * i + 2] = R[3 * i + 0] * s.y - R[3 * i + 1] * s.x;
-    }
+    rotation_term(R, Kinv, M, Z);
     // (weighted alignment: atom b's share of the centroid is align_w[b] / n_align, and ref_c holds align_w[b] * ref_b)
     const V3 shift = inv_nal * sump;
     for (int b = 0; b < pp.n_align; ++b) {
@@ -587,43 +537,18 @@ __global__ __launch_bounds__(64) void metric_align_kernel(cvf_pp_desc pp, const 
       dH[3] += u.y * rf.x; dH[4] += u.y * rf.y; dH[5] += u.y * rf.z;
       dH[6] += u.z * rf.x; dH[7] += u.z * rf.y; dH[8] += u.z * rf.z;
     }
-    float T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * dH[j] + R[3 + i] * dH[3 + j] + R[6 + i] * dH[6 + j];
-    const V3 w = sym_times(Kinv, v3(T[7] - T[5], T[2] - T[6], T[3] - T[1]));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      dR[3 * i + 0] = R[3 * i + 1] * w.z - R[3 * i + 2] * w.y;
-      dR[3 * i + 1] = -R[3 * i + 0] * w.z + R[3 * i + 2] * w.x;
-      dR[3 * i + 2] = R[3 * i + 0] * w.y - R[3 * i + 1] * w.x;
-    }
+    rotation_term(R, Kinv, dH, dR);
   }
   for (int r = 0; r < pp.n_rec; ++r) {
     const Rec rc = load_rec(tb.rec, r);
     if (rc.type == CVF_FEAT_POSITION) {
-      const V3 qa = row_times(getU(rc.a0) - ubar, R) + row_times(centred(my, rc.a0, c), dR);
+      const V3 qa = position_jvp(R, dR, getU(rc.a[0]) - ubar, centred(my, rc.a[0], c));
       qt[rc.out * CVF_TILE] = qa.x;
       qt[(rc.out + 1) * CVF_TILE] = qa.y;
       qt[(rc.out + 2) * CVF_TILE] = qa.z;
-    } else if (rc.type == CVF_FEAT_BOND) {
-      const BondG e = bond_eval(atom(my, rc.a0), atom(my, rc.a1));
-      qt[rc.out * CVF_TILE] = dot(e.ga, getU(rc.a0)) + dot(e.gb, getU(rc.a1));
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const AngleG e = angle_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2));
-      float dv = dot(e.ga, getU(rc.a0)) + dot(e.gb, getU(rc.a1)) + dot(e.gc, getU(rc.a2));
-      if (pp.use_angle_value) dv = -dv / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
-      qt[rc.out * CVF_TILE] = dv;
     } else {
-      const DihedralG e = dihedral_eval(atom(my, rc.a0), atom(my, rc.a1), atom(my, rc.a2), atom(my, rc.a3));
-      const float dphi = dot(e.g1, getU(rc.a0)) + dot(e.g2, getU(rc.a1)) + dot(e.g3, getU(rc.a2)) + dot(e.g4, getU(rc.a3));
-      if (pp.use_angle_value) {
-        qt[rc.out * CVF_TILE] = dphi;
-      } else {
-        qt[rc.out * CVF_TILE] = -e.sn * dphi;
-        qt[(rc.out + 1) * CVF_TILE] = e.cs * dphi;
-      }
+      invariant_jvp(rc.type, pp.use_angle_value, [&](int k) { return atom_xyz(my, rc.a[k]); },
+                    [&](int k) { return getU(rc.a[k]); }, [&](int j, float v) { qt[(rc.out + j) * CVF_TILE] = v; });
     }
   }
 }

@@ -10,6 +10,7 @@
 //             touch were streamed microseconds ago and come from L2 / Infinity Cache, not HBM (a separate
 //             feature launch re-fetched more sectors from HBM than the frame itself holds).
 //   flush     features of the 16 frames are staged in LDS and leave as full 64-byte segments of the tiled layout.
+#include "cvf_features.hpp"
 #include "cvf_kabsch.hpp"
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,11 +26,6 @@ __device__ __forceinline__ int64_t k1_group_of_block(bool same_xcd) {
   const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7, ix = blockIdx.x >> 3;
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + ix;
 }
-
-struct Rec {
-  int type, a0, a1, a2, a3, out;
-};
-__device__ __forceinline__ V3 gatom(const float* __restrict__ xf, int a) { return V3{xf[3 * a], xf[3 * a + 1], xf[3 * a + 2]}; }
 
 template <bool CONTIG>
 __global__ __launch_bounds__(64 * kGroup) void k1_large_gather_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B,
@@ -117,28 +113,17 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_gather_kernel(cvf_pp_des
     if (fr) fr[o] = v;
   };
   for (int r = lane; r < pp.n_rec; r += 64) {
-    const int32_t* p = pp.rec + 6 * r;
-    const Rec rc{p[0], p[1], p[2], p[3], p[4], p[5]};
+    const Rec rc = load_rec(pp.rec, r);
     if (rc.type == CVF_FEAT_POSITION) {
-      const V3 xa = gatom(xf, rc.a0);
+      const V3 xa = atom_xyz(xf, rc.a[0]);
       const V3 xc = v3((float)((double)xa.x - cc0), (float)((double)xa.y - cc1), (float)((double)xa.z - cc2));
       const V3 al = row_times(xc, R);
       emit(rc.out, al.x);
       emit(rc.out + 1, al.y);
       emit(rc.out + 2, al.z);
-    } else if (rc.type == CVF_FEAT_BOND) {
-      emit(rc.out, bond_eval(gatom(xf, rc.a0), gatom(xf, rc.a1)).val);
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const float cs = angle_eval(gatom(xf, rc.a0), gatom(xf, rc.a1), gatom(xf, rc.a2)).cs;
-      emit(rc.out, pp.use_angle_value ? acosf(cs) : cs);
     } else {
-      const DihedralG dg = dihedral_eval(gatom(xf, rc.a0), gatom(xf, rc.a1), gatom(xf, rc.a2), gatom(xf, rc.a3));
-      if (pp.use_angle_value) {
-        emit(rc.out, atan2f(dg.sn, dg.cs));
-      } else {
-        emit(rc.out, dg.cs);
-        emit(rc.out + 1, dg.sn);
-      }
+      invariant_values(rc.type, pp.use_angle_value, [&](int k) { return atom_xyz(xf, rc.a[k]); },
+                       [&](int j, float v) { emit(rc.out + j, v); });
     }
   }
   // ---- flush the 16 frames' features as 64-byte segments
@@ -189,8 +174,7 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
 #pragma unroll
   for (int it = 0; it < kRecPre; ++it) {
     const int r = lane + 64 * it;
-    const int32_t* p = pp.rec_slot + 6 * (r < nrs ? r : nrs - 1);
-    pre[it] = Rec{p[0], p[1], p[2], p[3], p[4], p[5]};
+    pre[it] = load_rec(pp.rec_slot, r < nrs ? r : nrs - 1);
   }
   // ---- staging of the features (decided here: the invariant features below are emitted before the solve is known)
   // staged == 1: the features go through LDS as [feature][frame] for the tiled output (rows, if also wanted, straight from the lanes);
@@ -211,21 +195,8 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
   auto invariant = [&](const Rec& rc, int fs) {
     if (rc.type < 0 || rc.type == CVF_FEAT_POSITION) return;
     const float* cp = capBase + (size_t)fs * nslot * 3;
-    auto sat = [&](int sl) { return V3{cp[3 * sl], cp[3 * sl + 1], cp[3 * sl + 2]}; };
-    if (rc.type == CVF_FEAT_BOND) {
-      emit_to(fs, rc.out, bond_eval(sat(rc.a0), sat(rc.a1)).val);
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const float cs = angle_eval(sat(rc.a0), sat(rc.a1), sat(rc.a2)).cs;
-      emit_to(fs, rc.out, pp.use_angle_value ? acosf(cs) : cs);
-    } else {
-      const DihedralG dg = dihedral_eval(sat(rc.a0), sat(rc.a1), sat(rc.a2), sat(rc.a3));
-      if (pp.use_angle_value) {
-        emit_to(fs, rc.out, atan2f(dg.sn, dg.cs));
-      } else {
-        emit_to(fs, rc.out, dg.cs);
-        emit_to(fs, rc.out + 1, dg.sn);
-      }
-    }
+    invariant_values(rc.type, pp.use_angle_value, [&](int k) { return atom_xyz(cp, rc.a[k]); },
+                     [&](int j, float v) { emit_to(fs, rc.out + j, v); });
   };
   if (tid < kGroup) {  // the group's 3x3 problems, one per lane of one wave
     const double* t = sums[tid];
@@ -272,16 +243,14 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
     for (int it = 0; it < kRecPre; ++it)
       if (lane + 64 * it < nrs) invariant(pre[it], fi);
     for (int r = lane + 64 * kRecPre; r < nrs; r += 64) {
-      const int32_t* p = pp.rec_slot + 6 * r;
-      invariant(Rec{p[0], p[1], p[2], p[3], p[4], p[5]}, fi);
+      invariant(load_rec(pp.rec_slot, r), fi);
     }
 #pragma unroll
     for (int it = 0; it < kRecPre; ++it)
       if (it % (kGroup - 1) == fi - 1 && lane + 64 * it < nrs) invariant(pre[it], 0);
     for (int it = kRecPre; 64 * it < nrs; ++it)
       if (it % (kGroup - 1) == fi - 1 && lane + 64 * it < nrs) {
-        const int32_t* p = pp.rec_slot + 6 * (lane + 64 * it);
-        invariant(Rec{p[0], p[1], p[2], p[3], p[4], p[5]}, 0);
+        invariant(load_rec(pp.rec_slot, lane + 64 * it), 0);
       }
   }
   __syncthreads();
@@ -297,7 +266,7 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
   // ---- the position features (the only ones that need the rotation), every wave its own frame
   auto position = [&](const Rec& rc) {
     if (rc.type != CVF_FEAT_POSITION) return;
-    const V3 xa = V3{capL[3 * rc.a0], capL[3 * rc.a0 + 1], capL[3 * rc.a0 + 2]};
+    const V3 xa = atom_xyz(capL, rc.a[0]);
     const V3 xc = v3((float)((double)xa.x - cc0), (float)((double)xa.y - cc1), (float)((double)xa.z - cc2));
     const V3 al = row_times(xc, R);
     emit_to(fi, rc.out, al.x);
@@ -308,9 +277,7 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
   for (int it = 0; it < kRecPre; ++it)
     if (lane + 64 * it < nrs) position(pre[it]);
   for (int r = lane + 64 * kRecPre; r < nrs; r += 64) {
-    const int32_t* p = pp.rec_slot + 6 * r;   // like rec, atom fields hold slots
-    const Rec rc{p[0], p[1], p[2], p[3], p[4], p[5]};
-    position(rc);
+    position(load_rec(pp.rec_slot, r));   // like rec, atom fields hold slots
   }
   CVF_STAMP(7);
   if (staged == 1) {
@@ -817,18 +784,16 @@ __global__ __launch_bounds__(64 * (kStream + kTail)) void k1_large_pipe_kernel(c
   const int nb = (nrs + 63) >> 6;                     // batches of 64 records
   // one feature record of frame j of the group
   auto feature = [&](const float* capG, int64_t f0, int j, int r, bool positions) __attribute__((always_inline)) {
-    const int32_t* p = recL + 6 * r;   // like rec, atom fields hold slots
-    const Rec rc{p[0], p[1], p[2], p[3], p[4], p[5]};
+    const Rec rc = load_rec(recL, r);   // like rec, atom fields hold slots
     if (rc.type < 0 || (rc.type == CVF_FEAT_POSITION) != positions) return;   // (type < 0: padding entries of batched lists)
     const float* cp = capG + (size_t)j * ns3;
-    auto sat = [&](int s_) { return V3{cp[3 * s_], cp[3 * s_ + 1], cp[3 * s_ + 2]}; };
     auto emit = [&](int o, float v) {
       if (staged == 1) featL[o * kGroup + j] = v;
       else featL[j * pp.d_r + o] = v;
       if (staged == 1 && feat_rows != nullptr && f0 + j < B) feat_rows[(f0 + j) * pp.d_r + o] = v;
     };
     if (rc.type == CVF_FEAT_POSITION) {
-      const V3 xa = sat(rc.a0);
+      const V3 xa = atom_xyz(cp, rc.a[0]);
       const V3 xc = v3((float)((double)xa.x - cD[j][0]), (float)((double)xa.y - cD[j][1]), (float)((double)xa.z - cD[j][2]));
       float R[9];
 #pragma unroll
@@ -837,19 +802,9 @@ __global__ __launch_bounds__(64 * (kStream + kTail)) void k1_large_pipe_kernel(c
       emit(rc.out, al.x);
       emit(rc.out + 1, al.y);
       emit(rc.out + 2, al.z);
-    } else if (rc.type == CVF_FEAT_BOND) {
-      emit(rc.out, bond_eval(sat(rc.a0), sat(rc.a1)).val);
-    } else if (rc.type == CVF_FEAT_ANGLE) {
-      const float cs = angle_eval(sat(rc.a0), sat(rc.a1), sat(rc.a2)).cs;
-      emit(rc.out, pp.use_angle_value ? acosf(cs) : cs);
     } else {
-      const DihedralG dg = dihedral_eval(sat(rc.a0), sat(rc.a1), sat(rc.a2), sat(rc.a3));
-      if (pp.use_angle_value) {
-        emit(rc.out, atan2f(dg.sn, dg.cs));
-      } else {
-        emit(rc.out, dg.cs);
-        emit(rc.out + 1, dg.sn);
-      }
+      invariant_values(rc.type, pp.use_angle_value, [&](int k) { return atom_xyz(cp, rc.a[k]); },
+                       [&](int j, float v) { emit(rc.out + j, v); });
     }
   };
   if (tw == 0) {

@@ -12,30 +12,13 @@
 // every sum sequential per lane.  Larger frames: one workgroup per frame, the records over the threads; each (record, atom)
 // pair writes its own contribution row (the mrec / slot_row tables of cvf_pp_desc), each slot sums its rows in order, the dense
 // row of 3N floats leaves in 16-byte stores.  No atomics anywhere: two calls give the same bits.
+#include "cvf_features.hpp"
 #include "cvf_metric.hpp"
 
 namespace {
 
 constexpr int kLanePerFrameMaxCoord = 192;   // as cvf_align_feature_fwd (k1_align.hip): aux rows are the same on both paths
 constexpr int kLargeThreads = 256;
-
-__device__ __forceinline__ V3 atom_at(const float* my, int a) { return V3{my[3 * a], my[3 * a + 1], my[3 * a + 2]}; }
-
-// s = Kinv ax(R^T M);  Z = R [s]x   ([s]x rows: (0,-sz,sy), (sz,0,-sx), (-sy,sx,0))
-__device__ __forceinline__ void rotation_term(const float* R, const float* Kinv, const float* M, float* Z) {
-  float T[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * M[j] + R[3 + i] * M[3 + j] + R[6 + i] * M[6 + j];
-  const V3 s = sym_times(Kinv, v3(T[7] - T[5], T[2] - T[6], T[3] - T[1]));
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Z[3 * i + 0] = R[3 * i + 1] * s.z - R[3 * i + 2] * s.y;
-    Z[3 * i + 1] = -R[3 * i + 0] * s.z + R[3 * i + 2] * s.x;
-    Z[3 * i + 2] = R[3 * i + 0] * s.y - R[3 * i + 1] * s.x;
-  }
-}
 
 // ------------------------------------------------------------------------------------
 // small frames: one lane per frame.  LDS: x tile [64][stride] | G [64][stride] | (TABLES_LDS) rec, align_idx, ref_c.
@@ -85,36 +68,17 @@ __global__ __launch_bounds__(64) void vjp_align_kernel(cvf_pp_desc pp, const flo
   V3 sump = v3(0, 0, 0);
   float M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int r = 0; r < pp.n_rec; ++r) {
-    const int32_t* p = rec + 6 * r;
+    const int32_t* p = rec + 6 * r;   // (type, atoms 0..3, out) as Rec, read field by field
     const int type = p[0], out = p[5];
     if (type == CVF_FEAT_POSITION) {
       const V3 g = v3(gr[out], gr[out + 1], gr[out + 2]);
       const V3 pr = mat_times(R, g);
       addG(p[1], pr);
       sump = sump + pr;
-      const V3 xc = centred(my, p[1], c);
-      M[0] += xc.x * g.x; M[1] += xc.x * g.y; M[2] += xc.x * g.z;
-      M[3] += xc.y * g.x; M[4] += xc.y * g.y; M[5] += xc.y * g.z;
-      M[6] += xc.z * g.x; M[7] += xc.z * g.y; M[8] += xc.z * g.z;
-    } else if (type == CVF_FEAT_BOND) {
-      const BondG e = bond_eval(atom_at(my, p[1]), atom_at(my, p[2]));
-      const float gs = gr[out];
-      addG(p[1], gs * e.ga);
-      addG(p[2], gs * e.gb);
-    } else if (type == CVF_FEAT_ANGLE) {
-      const AngleG e = angle_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]));
-      float gs = gr[out];
-      if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));   // d acos(cs) = -dcs / sin
-      addG(p[1], gs * e.ga);
-      addG(p[2], gs * e.gb);
-      addG(p[3], gs * e.gc);
+      outer_add(M, centred(my, p[1], c), g);
     } else {
-      const DihedralG e = dihedral_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]), atom_at(my, p[4]));
-      const float gs = pp.use_angle_value ? gr[out] : (gr[out + 1] * e.cs - gr[out] * e.sn);
-      addG(p[1], gs * e.g1);
-      addG(p[2], gs * e.g2);
-      addG(p[3], gs * e.g3);
-      addG(p[4], gs * e.g4);
+      invariant_vjp(type, pp.use_angle_value, 1, [&](int k) { return atom_xyz(my, p[1 + k]); },
+                    [&](int, int j) { return gr[out + j]; }, [&](int, int k, V3 v) { addG(p[1 + k], v); });
     }
   }
   if (pp.has_position) {
@@ -165,10 +129,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_large_kernel(cvf_pp_desc pp
   const V3 c = v3(ax[9 * CVF_TILE], ax[10 * CVF_TILE], ax[11 * CVF_TILE]);
 #pragma unroll
   for (int i = 0; i < 6; ++i) Kinv[i] = ax[(12 + i) * CVF_TILE];
-  auto at = [&](int slot) {
-    const int a = pp.slot_atom[slot];
-    return V3{xf[3 * a], xf[3 * a + 1], xf[3 * a + 2]};
-  };
+  auto at = [&](int slot) { return atom_xyz(xf, pp.slot_atom[slot]); };
   auto put = [&](int row, V3 v) {
     rows[3 * row] = v.x;
     rows[3 * row + 1] = v.y;
@@ -188,10 +149,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_large_kernel(cvf_pp_desc pp
       const V3 g = v3(gf[out], gf[out + 1], gf[out + 2]);
       const V3 pr = mat_times(R, g);
       put(r0, pr);
-      const V3 xc = at(s0) - c;
-      acc[0] += xc.x * g.x; acc[1] += xc.x * g.y; acc[2] += xc.x * g.z;
-      acc[3] += xc.y * g.x; acc[4] += xc.y * g.y; acc[5] += xc.y * g.z;
-      acc[6] += xc.z * g.x; acc[7] += xc.z * g.y; acc[8] += xc.z * g.z;
+      outer_add(acc, at(s0) - c, g);
       acc[9] += pr.x; acc[10] += pr.y; acc[11] += pr.z;
     } else if (type == CVF_FEAT_BOND) {
       const BondG e = bond_eval(at(s0), at(s1));
@@ -201,7 +159,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_large_kernel(cvf_pp_desc pp
     } else if (type == CVF_FEAT_ANGLE) {
       const AngleG e = angle_eval(at(s0), at(s1), at(s2));
       float gs = gf[out];
-      if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
+      if (pp.use_angle_value) gs = -gs / acos_den(e.cs);
       put(r0, gs * e.ga);
       put(r1, gs * e.gb);
       put(r2, gs * e.gc);
@@ -389,49 +347,24 @@ __global__ __launch_bounds__(64) void vjp_rows_small_kernel(cvf_pp_desc pp, cons
       Gl[3 * atm + 2] += v.z;
     };
     for (int r = 0; r < pp.n_rec; ++r) {
-      const int32_t* p = rec + 6 * r;
-      const int type = p[0], out = p[5];
-      if (type == CVF_FEAT_POSITION) {
-        const V3 xc = centred(my, p[1], c);
+      const Rec rc = load_rec(rec, r);
+      if (rc.type == CVF_FEAT_POSITION) {
+        const V3 xc = centred(my, rc.a[0], c);
         for (int ii = 0; ii < ng; ++ii) {
           const float* gr = gf + (i0 + ii) * pp.d_r;
-          const V3 g = v3(gr[out], gr[out + 1], gr[out + 2]);
+          const V3 g = v3(gr[rc.out], gr[rc.out + 1], gr[rc.out + 2]);
           const V3 pr = mat_times(R, g);
-          addG(ii, p[1], pr);
+          addG(ii, rc.a[0], pr);
           float* A = acc + ii * 12 * CVF_TILE + lane;
-          A[0 * CVF_TILE] += xc.x * g.x; A[1 * CVF_TILE] += xc.x * g.y; A[2 * CVF_TILE] += xc.x * g.z;
-          A[3 * CVF_TILE] += xc.y * g.x; A[4 * CVF_TILE] += xc.y * g.y; A[5 * CVF_TILE] += xc.y * g.z;
-          A[6 * CVF_TILE] += xc.z * g.x; A[7 * CVF_TILE] += xc.z * g.y; A[8 * CVF_TILE] += xc.z * g.z;
+          outer_add<CVF_TILE>(A, xc, g);
           A[9 * CVF_TILE] = A[9 * CVF_TILE] + pr.x;
           A[10 * CVF_TILE] = A[10 * CVF_TILE] + pr.y;
           A[11 * CVF_TILE] = A[11 * CVF_TILE] + pr.z;
         }
-      } else if (type == CVF_FEAT_BOND) {
-        const BondG e = bond_eval(atom_at(my, p[1]), atom_at(my, p[2]));
-        for (int ii = 0; ii < ng; ++ii) {
-          const float gs = gf[(i0 + ii) * pp.d_r + out];
-          addG(ii, p[1], gs * e.ga);
-          addG(ii, p[2], gs * e.gb);
-        }
-      } else if (type == CVF_FEAT_ANGLE) {
-        const AngleG e = angle_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]));
-        for (int ii = 0; ii < ng; ++ii) {
-          float gs = gf[(i0 + ii) * pp.d_r + out];
-          if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
-          addG(ii, p[1], gs * e.ga);
-          addG(ii, p[2], gs * e.gb);
-          addG(ii, p[3], gs * e.gc);
-        }
       } else {
-        const DihedralG e = dihedral_eval(atom_at(my, p[1]), atom_at(my, p[2]), atom_at(my, p[3]), atom_at(my, p[4]));
-        for (int ii = 0; ii < ng; ++ii) {
-          const float* gr = gf + (i0 + ii) * pp.d_r;
-          const float gs = pp.use_angle_value ? gr[out] : (gr[out + 1] * e.cs - gr[out] * e.sn);
-          addG(ii, p[1], gs * e.g1);
-          addG(ii, p[2], gs * e.g2);
-          addG(ii, p[3], gs * e.g3);
-          addG(ii, p[4], gs * e.g4);
-        }
+        invariant_vjp(rc.type, pp.use_angle_value, ng, [&](int k) { return atom_xyz(my, rc.a[k]); },
+                      [&](int ii, int j) { return gf[(i0 + ii) * pp.d_r + rc.out + j]; },
+                      [&](int ii, int k, V3 v) { addG(ii, rc.a[k], v); });
       }
     }
     if (pp.has_position) {
@@ -483,10 +416,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_rows_large_kernel(cvf_pp_de
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = ax[i * CVF_TILE];
   };
-  auto at = [&](int slot) {
-    const int a = pp.slot_atom[slot];
-    return V3{xf[3 * a], xf[3 * a + 1], xf[3 * a + 2]};
-  };
+  auto at = [&](int slot) { return atom_xyz(xf, pp.slot_atom[slot]); };
   auto put = [&](int ii, int row, V3 v) {
     float* rows = lds + ii * nrow;
     rows[3 * row] = v.x;
@@ -525,10 +455,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_rows_large_kernel(cvf_pp_de
           const V3 g = v3(gr[d.out], gr[d.out + 1], gr[d.out + 2]);
           const V3 pr = mat_times(R, g);
           put(ii, d.r0, pr);
-          const V3 xc = at(d.s0) - c;
-          acc[0] += xc.x * g.x; acc[1] += xc.x * g.y; acc[2] += xc.x * g.z;
-          acc[3] += xc.y * g.x; acc[4] += xc.y * g.y; acc[5] += xc.y * g.z;
-          acc[6] += xc.z * g.x; acc[7] += xc.z * g.y; acc[8] += xc.z * g.z;
+          outer_add(acc, at(d.s0) - c, g);
           acc[9] += pr.x; acc[10] += pr.y; acc[11] += pr.z;
         }
       }
@@ -553,7 +480,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_rows_large_kernel(cvf_pp_de
         const AngleG e = angle_eval(at(d.s0), at(d.s1), at(d.s2));
         for (int ii = 0; ii < ng; ++ii) {
           float gs = gf[(i0 + ii) * pp.d_r + d.out];
-          if (pp.use_angle_value) gs = -gs / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
+          if (pp.use_angle_value) gs = -gs / acos_den(e.cs);
           put(ii, d.r0, gs * e.ga);
           put(ii, d.r1, gs * e.gb);
           put(ii, d.r2, gs * e.gc);
@@ -562,7 +489,7 @@ __global__ __launch_bounds__(kLargeThreads) void vjp_rows_large_kernel(cvf_pp_de
         const DihedralG e = dihedral_eval(at(d.s0), at(d.s1), at(d.s2), at(d.s3));
         for (int ii = 0; ii < ng; ++ii) {
           const float* gr = gf + (i0 + ii) * pp.d_r;
-          const float gs = pp.use_angle_value ? gr[d.out] : (gr[d.out + 1] * e.cs - gr[d.out] * e.sn);
+          const float gs = dihedral_adjoint(pp.use_angle_value, e.cs, e.sn, [&](int j) { return gr[d.out + j]; });
           put(ii, d.r0, gs * e.g1);
           put(ii, d.r1, gs * e.g2);
           put(ii, d.r2, gs * e.g3);

@@ -24,6 +24,7 @@
 //     row, phase C reads the u rows of its record's atoms.  No atomics, no read-modify-write, no batching constraint on
 //     the record list.
 //   * the records a lane group owns keep their geometry (gradient vectors of the feature) in registers from phase A to C.
+#include "cvf_features.hpp"
 #include "cvf_metric.hpp"
 
 namespace {
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       const AngleG e = angle_eval(x0, x1, x2);
       ge.v0 = e.ga; ge.v1 = e.gc;
       ge.cs = e.cs;
-      ge.sn = -1.0f / sqrtf(fmaxf(1.0f - e.cs * e.cs, 1e-30f));
+      ge.sn = -1.0f / acos_den(e.cs);
     } else if (ty == CVF_FEAT_DIHEDRAL) {
       const DihedralG e = dihedral_eval(x0, x1, x2, x3);
       ge.v0 = e.g1; ge.v1 = e.g4;
@@ -208,10 +209,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       const V3 pv = mat_times(R, g);
       put_row(r0, pv);
       sa[0] += pv.x; sa[1] += pv.y; sa[2] += pv.z;
-      const V3 xc = ge.v0;
-      sa[3] += xc.x * g.x; sa[4] += xc.x * g.y; sa[5] += xc.x * g.z;
-      sa[6] += xc.y * g.x; sa[7] += xc.y * g.y; sa[8] += xc.y * g.z;
-      sa[9] += xc.z * g.x; sa[10] += xc.z * g.y; sa[11] += xc.z * g.z;
+      outer_add(sa + 3, ge.v0, g);
     } else if (ty == CVF_FEAT_BOND) {
       const V3 ga = rx.g[0] * ge.v0;
       put_row(r0, ga);
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       put_row(r1, v3(-ga.x - gc.x, -ga.y - gc.y, -ga.z - gc.z));
       put_row(r2, gc);
     } else {
-      const float gs = pp.use_angle_value ? rx.g[0] : (rx.g[1] * ge.cs - rx.g[0] * ge.sn);
+      const float gs = dihedral_adjoint(pp.use_angle_value, ge.cs, ge.sn, [&](int j) { return rx.g[j]; });
       const V3 g1 = gs * ge.v0, g4 = gs * ge.v1;
       put_row(r0, g1);
       put_row(r1, (-1.0f - ge.p) * g1 + ge.q * g4);
@@ -279,18 +277,8 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
   CVF_STAMP(23);
   const V3 sump = v3(sa[0], sa[1], sa[2]);
   const float* M = sa + 3;
-  float T[9], Z[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * M[j] + R[3 + i] * M[3 + j] + R[6 + i] * M[6 + j];
-  const V3 s = sym_times(Kinv, v3(T[7] - T[5], T[2] - T[6], T[3] - T[1]));
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Z[3 * i + 0] = R[3 * i + 1] * s.z - R[3 * i + 2] * s.y;
-    Z[3 * i + 1] = -R[3 * i + 0] * s.z + R[3 * i + 2] * s.x;
-    Z[3 * i + 2] = R[3 * i + 0] * s.y - R[3 * i + 1] * s.x;
-  }
+  float Z[9];
+  rotation_term(R, Kinv, M, Z);
   const float sh[3] = {inv_nal * sump.x, inv_nal * sump.y, inv_nal * sump.z};
   // ---- dense part from the moments
   float E = 0.0f, usd[3], dH[9];
@@ -413,18 +401,8 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
   for (int cc = 0; cc < 3; ++cc)
 #pragma unroll
     for (int j = 0; j < 3; ++j) dH[3 * cc + j] -= ub[cc] * R1[j];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) T[3 * i + j] = R[i] * dH[j] + R[3 + i] * dH[3 + j] + R[6 + i] * dH[6 + j];
-  const V3 w = sym_times(Kinv, v3(T[7] - T[5], T[2] - T[6], T[3] - T[1]));
   float dR[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    dR[3 * i + 0] = R[3 * i + 1] * w.z - R[3 * i + 2] * w.y;
-    dR[3 * i + 1] = -R[3 * i + 0] * w.z + R[3 * i + 2] * w.x;
-    dR[3 * i + 2] = R[3 * i + 0] * w.y - R[3 * i + 1] * w.x;
-  }
+  rotation_term(R, Kinv, dH, dR);
   // ---- phase C: q = J u, by the records' owners
   auto jvp = [&](const Geo& ge) {
     const int ty = geo_type(ge);
@@ -433,7 +411,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
     const int u0 = ge.u01 & 0xffff, u1 = (unsigned)ge.u01 >> 16, u2 = ge.u23 & 0xffff, u3 = (unsigned)ge.u23 >> 16;
     if (ty == CVF_FEAT_POSITION) {
       const V3 u = rowat(u0);
-      const V3 qa = row_times(v3(u.x - ub[0], u.y - ub[1], u.z - ub[2]), R) + row_times(ge.v0, dR);
+      const V3 qa = position_jvp(R, dR, v3(u.x - ub[0], u.y - ub[1], u.z - ub[2]), ge.v0);
       qp[0] = qa.x;
       qp[CVF_TILE] = qa.y;
       qp[2 * CVF_TILE] = qa.z;
@@ -450,12 +428,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       const V3 w1 = x1 + (-1.0f - ge.p) * x2 + ge.p * x3;
       const V3 w4 = x4 + ge.q * x2 + (-1.0f - ge.q) * x3;
       const float dphi = dot(ge.v0, w1) + dot(ge.v1, w4);
-      if (pp.use_angle_value) {
-        qp[0] = dphi;
-      } else {
-        qp[0] = -ge.sn * dphi;
-        qp[CVF_TILE] = ge.cs * dphi;
-      }
+      dihedral_tangent(pp.use_angle_value, ge.cs, ge.sn, dphi, [&](int j, float v) { qp[j * CVF_TILE] = v; });
     }
   };
 #pragma unroll
