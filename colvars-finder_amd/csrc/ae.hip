@@ -1113,38 +1113,57 @@ extern "C" int64_t cvf_ae_scratch_floats(const cvf_mlp_desc* mlp, int64_t B) {
   return G * mlp->n_params + 4 * G + 4;
 }
 
+// The kernel and layout cvf_ae_step launches for this chain, parameter buffer and pass: 0 = ae16_kernel, 1 = ae_mfma_kernel on
+// the roomy layout, 2 = on the tight one (ae_mlayout), negative = refused (cvf_last_error() has the text); *lds_bytes (may be
+// NULL) receives the launch's dynamic LDS.  cvf_ae_step decides by calling this function: there is no second copy of the rules.
+extern "C" int cvf_ae_step_route(const cvf_mlp_desc* mlp, const void* theta, int with_grad, int64_t* lds_bytes) {
+  CVF_REQUIRE(mlp && theta, "cvf_ae_step: bad argument");
+  CVF_REQUIRE(mlp->n_nets == 1 && mlp->n_layers >= 1 && mlp->n_layers <= CVF_MAX_LAYERS, "cvf_ae_step: one chain expected");
+  CVF_REQUIRE(mlp->dims[0] == mlp->dims[mlp->n_layers], "cvf_ae_step: output width %d != input width %d",
+              mlp->dims[mlp->n_layers], mlp->dims[0]);
+  int hmax = 1;
+  for (int l = 1; l < mlp->n_layers; ++l) hmax = mlp->dims[l] > hmax ? mlp->dims[l] : hmax;
+  // the chain in registers (ae16_kernel): its shapes, a 16-byte aligned theta (128-bit weight loads) and a compiled instance
+  if (getenv("CVF_NO_AE16") == nullptr && ae16_shape(mlp) && (reinterpret_cast<uintptr_t>(theta) & 15) == 0 &&
+      ae16_dispatch(mlp->dims[0], hmax, [](auto, auto) {})) {
+    if (lds_bytes) *lds_bytes = (int64_t)ae16_layout(*mlp).total * (int64_t)sizeof(float);
+    return 0;
+  }
+  const AeMLayout lay = ae_mlayout(*mlp, with_grad != 0);
+  const size_t lds = (size_t)lay.total * sizeof(float);
+  if (lds_bytes) *lds_bytes = (int64_t)lds;
+  CVF_REQUIRE(lds <= 160 * 1024, "cvf_ae_step: the chain needs %zu B of LDS per workgroup (> 160 KiB)", lds);
+  // (ae_mlayout returns the tight layout only where it is smaller than the roomy one)
+  return lay.total != ae_mlayout_of(*mlp, with_grad != 0, false).total ? 2 : 1;
+}
+
 extern "C" int cvf_ae_step(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx,
                            int64_t B, const float* w, double inv_wsum, float* scratch, double* out2, float* grad,
                            int32_t* step_count, const cvf_adam_args* adam, void* stream) {
   CVF_REQUIRE(mlp && theta && feat_rows && w && scratch && out2 && B > 0, "cvf_ae_step: bad argument");
-  CVF_REQUIRE(mlp->n_nets == 1 && mlp->n_layers >= 1 && mlp->n_layers <= CVF_MAX_LAYERS, "cvf_ae_step: one chain expected");
-  CVF_REQUIRE(mlp->dims[0] == mlp->dims[mlp->n_layers], "cvf_ae_step: output width %d != input width %d",
-              mlp->dims[mlp->n_layers], mlp->dims[0]);
   CVF_REQUIRE(adam == nullptr || (grad && adam->theta && adam->m && adam->v && adam->step_count),
               "cvf_ae_step: incomplete adam arguments");
+  int64_t lds_bytes = 0;
+  const int route = cvf_ae_step_route(mlp, theta, grad != nullptr, &lds_bytes);
+  if (route < 0) return route;
+  const bool fast = route == 0;
+  const size_t lds = (size_t)lds_bytes;
   const int G = ae_grid(B);
   const int Pn = mlp->n_params;
   // scratch: [slab floats][partials as doubles, 8-byte aligned]
   float* slab = scratch;
   double* partial = reinterpret_cast<double*>(scratch + (((int64_t)G * Pn + 1) & ~(int64_t)1));
   hipStream_t s = (hipStream_t)stream;
-  static const bool no_fast = getenv("CVF_NO_AE16") != nullptr;
-  int hmax = 1;
-  for (int l = 1; l < mlp->n_layers; ++l) hmax = mlp->dims[l] > hmax ? mlp->dims[l] : hmax;
-  bool fast = !no_fast && ae16_shape(mlp) && (reinterpret_cast<uintptr_t>(theta) & 15) == 0;
   if (fast) {   // the chain in registers (ae16_kernel)
-    const size_t lds16 = (size_t)ae16_layout(*mlp).total * sizeof(float);
-    fast = ae16_dispatch(mlp->dims[0], hmax, [&](auto d_, auto h_) {
+    int hmax = 1;
+    for (int l = 1; l < mlp->n_layers; ++l) hmax = mlp->dims[l] > hmax ? mlp->dims[l] : hmax;
+    ae16_dispatch(mlp->dims[0], hmax, [&](auto d_, auto h_) {
       auto kernel = ae16_kernel<decltype(d_)::value, decltype(h_)::value>;
-      if (lds16 > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-      hipLaunchKernelGGL(kernel, dim3(G), dim3(256), lds16, s, *mlp, theta, feat_rows, idx, B, w, inv_wsum, grad ? 1 : 0, slab, partial,
+      if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kernel, dim3(G), dim3(256), lds, s, *mlp, theta, feat_rows, idx, B, w, inv_wsum, grad ? 1 : 0, slab, partial,
                          grad ? step_count : nullptr, ae16_layout(*mlp));
     });
-  }
-  if (!fast) {
-    const AeMLayout lay = ae_mlayout(*mlp, grad != nullptr);
-    const size_t lds = (size_t)lay.total * sizeof(float);
-    CVF_REQUIRE(lds <= 160 * 1024, "cvf_ae_step: the chain needs %zu B of LDS per workgroup (> 160 KiB)", lds);
+  } else {
     auto kernel = chain_is_tanh(mlp) ? ae_mfma_kernel<true> : ae_mfma_kernel<false>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     AeReg none = {};

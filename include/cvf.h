@@ -372,6 +372,13 @@ int cvf_ae_step(const cvf_mlp_desc* mlp, const float* theta, const float* feat_r
                 const float* w, double inv_wsum, float* scratch, double* out2, float* grad, int32_t* step_count,
                 const cvf_adam_args* adam, void* stream);
                 /* step_count (may be NULL) is advanced by one when grad != NULL; adam (may be NULL): update in the same call */
+/* The kernel cvf_ae_step launches for (mlp, theta, grad != NULL) - host arithmetic only, no launch: 0 = the register-resident
+ * chain (ae16_kernel: tanh chains of d0 <= 80, hidden widths <= 32, at most 80 KiB of LDS, a 16-byte aligned theta, CVF_NO_AE16
+ * unset in the environment), 1 / 2 = the general kernel (ae_mfma_kernel) on its roomy / tight LDS layout, negative = refused
+ * (more than 160 KiB of LDS; cvf_last_error()).  lds_bytes (may be NULL): the launch's dynamic LDS.  cvf_ae_step itself decides
+ * by this function.  CVF_NO_AE16 is consulted with getenv() on EVERY call of either function, so it can be set and cleared
+ * while the process runs - by the thread that makes the calls: getenv is not safe against a concurrent setenv. */
+int cvf_ae_step_route(const cvf_mlp_desc* mlp, const void* theta, int with_grad, int64_t* lds_bytes);
 
 /* --- RegAutoEncoderTask (core.py:746-1217): time-lagged reconstruction loss
  * (weighted_MSE_loss, core.py:883-885) + transfer-operator eigenfunction regulariser (reg_eigen_loss with

@@ -28,14 +28,13 @@ whose exact gradient is 0 (the loss does not change when a constant is added to 
 of a cancelling sum over the batch, which differs with the summation order (2.9e-6 of the largest entry at k = 1 in transfer
 mode); the comparison of both batches with the oracle bounds them.
 """
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from tests import ef_cases as E
+from tests import sweep_errors
 from tests.synth import Traj, diag_coeff_for, make_molecule_traj
 
 pytestmark = pytest.mark.gpu
@@ -59,10 +58,7 @@ def dev():
 @pytest.fixture(scope="module", autouse=True)
 def _error_table():
     yield
-    path = os.environ.get("CVF_SWEEP_ERRORS")
-    if path:
-        with open(path, "w") as f:
-            json.dump(ERRORS, f, indent=1)
+    sweep_errors.write(ERRORS)
 
 
 @pytest.fixture(autouse=True)
