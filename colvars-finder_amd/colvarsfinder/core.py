@@ -27,6 +27,7 @@ for it) and the HIP extension must be built, otherwise construction raises.
 """
 
 import copy
+import gc
 import math
 import os
 import types
@@ -691,6 +692,9 @@ class _EFWorkspace:
         self.saved = torch.empty(n_saved, **f32) if n_saved > 0 else None
         self.slab_rows = lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt)
         self.slab = torch.empty(self.slab_rows * n_params, **f32)
+        # alignment rows of the resident batches of this size (EigenFunctionTask._alignment_rows):
+        # (X.data_ptr(), B) -> (X, X._version when the rows were filled, rows)
+        self.align_rows = {}
 
     feat = property(lambda self: self._feat[self.slot])
     aux = property(lambda self: self._aux[self.slot])
@@ -840,6 +844,9 @@ class EigenFunctionTask(TrainingTask):
         self._fused_fm = self._fused_k1 = self._fused_tr = None   # decided on first use: cvf_ef_[align_]fwd_metric_supported(nets, layer)
         self._side = torch.cuda.Stream(device=self.device)
         self._pipeline = os.environ.get("CVF_PIPELINE", "0") == "1"
+        # CVF_ALIGN_CACHE=0: every train step solves its frames' alignment again (see _alignment_rows); read once, here
+        self._align_cache = os.environ.get("CVF_ALIGN_CACHE", "1") != "0"
+        self.alignment_fills = 0   # launches of cvf_ef16_align_rows so far (one per resident batch and per re-fill)
 
     # ---------------------------------------------------------------- model views
     def get_reordered_eigenfunctions(self, model, cvec):
@@ -895,6 +902,54 @@ class EigenFunctionTask(TrainingTask):
                           and bool(_hip.lib().cvf_ef16_supported(self._flat.desc, self._pp)))
         return self._ef16
 
+    def _alignment_rows(self, ws, X):
+        """The alignment rows (csrc/ef16_front_rows.hip: rotation, centroid and K^-1 of every frame, 84 bytes per frame) of the
+        resident batch ``X``, filled on its first visit, or None: this launch solves for them itself.
+
+        The rows depend on the frames and the layer only, and the training loops replay the same static batches every epoch
+        (shuffle=False, core.py:472-481), so every visit after the first starts from them.  An entry is keyed by the batch's
+        address and size and HOLDS ``X``: its memory cannot be handed to another tensor while the entry lives, and an in-place
+        torch write to ``X`` or its base changes ``X._version`` and re-fills.  A write torch cannot see (a raw kernel, another
+        library) is the caller's to announce with :meth:`drop_alignment_cache`.  Entries are never evicted (a captured graph may
+        hold the pointer) and are created only while all of them together stay within the share of the free device memory that
+        RECORD_MEMORY_FRACTION leaves over; nothing is allocated while the stream is capturing."""
+        if not self._align_cache:
+            return None
+        key = (X.data_ptr(), ws.B)
+        ent = ws.align_rows.get(key)
+        if ent is not None and ent[1] == X._version:
+            return ent[2]
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        lib = _hip.lib()
+        if ent is None:
+            nbytes = 4 * int(lib.cvf_ef16_align_rows_floats(ws.B))
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if self.alignment_rows_bytes + nbytes > (1.0 - self.RECORD_MEMORY_FRACTION) * free:
+                return None
+            rows = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
+        else:
+            rows = ent[2]   # (the same buffer: a captured graph may hold its address)
+        # (not through _call: its event log holds the launches of a STEP - bench.py's launches_per_step, the launch checks of the
+        #  tests; this one happens once per resident batch and is counted in `alignment_fills`)
+        _hip.check(lib.cvf_ef16_align_rows(self._pp, _hip.ptr(X), ws.B, _hip.ptr(rows), _hip.stream()), "cvf_ef16_align_rows")
+        self.alignment_fills += 1
+        ws.align_rows[key] = (X, X._version, rows)
+        return rows
+
+    @property
+    def alignment_rows_bytes(self):
+        """Device memory the alignment rows of the resident batches take now (84 bytes per frame; beside ``resident_bytes``, which
+        counts the frames themselves)."""
+        return sum(e[2].numel() * 4 for ws in self._ws.values() for e in ws.align_rows.values())
+
+    def drop_alignment_cache(self):
+        """Forget the alignment rows of every resident batch, and the captured graphs that read them.  Call it after writing
+        to a batch's frames by means torch does not see; ``task._ws.clear()`` releases the rows too (with the workspaces)."""
+        self._graphs.clear()
+        for ws in self._ws.values():
+            ws.align_rows.clear()
+
     def _sum_stats_and_tail(self, ws):
         """Data-parallel step, collective #1 + the loss tail on this rank's batch sums in ``ws.stats``:
         one launch over the peer-to-peer windows (cvf_ef_loss_dp), else an all-reduce followed by cvf_ef_loss."""
@@ -917,9 +972,11 @@ class EigenFunctionTask(TrainingTask):
             self._call("cvf_align_feature_fwd", lib.cvf_align_feature_fwd, self._pp, P(X_lag), B, P(feat_lag), None, None,
                        P(ws._k1_scratch[slot]), _hip.stream())
 
-    def _forward(self, X, w, X_lag=None, w_lag=None, slot=0, aligned=False, out=None):
+    def _forward(self, X, w, X_lag=None, w_lag=None, slot=0, aligned=False, out=None, cache=False):
         """Everything up to the loss for one (local) batch; leaves loss_vec / coef on the device.
         ``aligned``: buffer ``slot`` already holds this batch's features (a previous step prefetched them).
+        ``cache``: ``X`` is a resident batch that will be visited again (the training loops): generator mode on the 16-frame
+        route keeps its alignment rows (:meth:`_alignment_rows`) - same results bit for bit.
         ``out``: fp64 device row of length 3 + 2k that receives the loss vector instead of ``ws.loss_vec`` (the training
         loops pass the step's slot of the epoch log: no copy kernel per step)."""
         lib, s, P = _hip.lib(), _hip.stream(), _hip.ptr
@@ -965,9 +1022,15 @@ class EigenFunctionTask(TrainingTask):
             # coordinates -> features, y, hidden activations, q = J A J^T g, E and the batch sums in one launch, 16 frames per
             # wave (+ the short launch that adds the units' rows and evaluates the loss tail)
             rows = lib.cvf_ef16_rows(B) > 0   # the units' rows of batch sums are added by a second, short launch
-            self._call("cvf_ef16_front", lib.cvf_ef16_front, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), B,
-                       P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch),
-                       None if rows else P(ws.stats), lv, cf, s)
+            al = self._alignment_rows(ws, X) if cache else None
+            if al is not None:   # (the same name for either form: one call of the step, the same outputs)
+                self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), B,
+                           P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch),
+                           None if rows else P(ws.stats), lv, cf, P(al), s)
+            else:
+                self._call("cvf_ef16_front", lib.cvf_ef16_front, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), B,
+                           P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch),
+                           None if rows else P(ws.stats), lv, cf, s)
             comm = None if single else _dist.fused_comm()
             if rows and comm is not None:   # the units' rows -> sums -> collective #1 -> loss tail: one launch
                 self._call("cvf_ef16_finish_dp", lib.cvf_ef16_finish_dp, self._cfg, B, P(ws.scratch), P(ws.stats), P(ws.loss_out),
@@ -1064,7 +1127,7 @@ class EigenFunctionTask(TrainingTask):
         ``[loss, npl, pen, eig_1..k, cvec_1..k]`` (fp64) without synchronising the host.
         ``prefetch = (X_next, X_lag_next)``: align that batch into the other feature buffer on a side stream while this
         step's backward kernel runs; the next call then passes ``slot ^ 1, aligned=True``."""
-        ws = self._forward(X, w, X_lag, w_lag, slot, aligned, out=out)
+        ws = self._forward(X, w, X_lag, w_lag, slot, aligned, out=out, cache=True)
         if prefetch is not None:   # beside the backward kernel, which leaves SIMD slots and LDS free at these sizes
             self._side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._side):
@@ -1080,7 +1143,12 @@ class EigenFunctionTask(TrainingTask):
     #    (batch, kind) pair is captured once and replayed in all later epochs: one host call per step
     def _graph_step(self, key, fn, out_slot, takes_out=False):
         """Run ``fn()`` (a step that returns the device loss vector) and copy its result into ``out_slot``;
-        captured into a hipGraph on first use when graphs are enabled."""
+        captured into a hipGraph on first use when graphs are enabled.
+
+        A replay does not pass through Python: a captured train step assumes static batch POINTERS and, since it starts from
+        the batch's alignment rows (:meth:`_alignment_rows`; the ``_version`` check cannot run in a replay), static batch
+        CONTENTS.  train() owns its gathered copies; a caller that rewrites a batch in place calls :meth:`drop_alignment_cache`,
+        which drops the captured graphs with the rows."""
         def run():
             # (steps that take the slot write their loss vector there themselves; others return a tensor to copy)
             got = fn(out_slot) if takes_out else fn()
@@ -1094,6 +1162,7 @@ class EigenFunctionTask(TrainingTask):
         if g is None:
             run()                                     # eager warm-up: allocates the workspace of this batch size
             torch.cuda.current_stream().synchronize()
+            gc.collect()                              # (see _graph_call)
             g = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(g):
@@ -1116,7 +1185,10 @@ class EigenFunctionTask(TrainingTask):
         """Run ``body()`` - any sequence of steps on static batches that writes its results into fixed device buffers, e.g.
         a whole epoch - through ONE hipGraph: captured on first use (after an eager run that allocates the workspaces),
         replayed afterwards.  One replay per epoch instead of one per step: the ~9 us the GPU idles between two graph
-        launches (rocprofv3 kernel trace of bench.py) is paid once per epoch."""
+        launches (rocprofv3 kernel trace of bench.py) is paid once per epoch.
+
+        As in :meth:`_graph_step`, the captured steps assume that the batches' CONTENTS are static, not only their addresses
+        (they read the alignment rows of the eager run); :meth:`drop_alignment_cache` drops the graphs with the rows."""
         if not self._use_graphs:
             body()
             return
@@ -1125,6 +1197,9 @@ class EigenFunctionTask(TrainingTask):
             body()
             torch.cuda.current_stream().synchronize()
             self.optimizer.sync_lr()
+            # unreachable tasks of the same process may still hold captured graphs; the cycle collector would destroy them whenever
+            # it next runs - inside the capture below that aborts the process (a graph may not be destroyed while a stream captures)
+            gc.collect()
             g = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(g):
@@ -1176,7 +1251,7 @@ class EigenFunctionTask(TrainingTask):
         """core.py:459-566 with the trajectory resident in HBM and one host copy of the losses per epoch."""
         k, lag = self.k, self.lag_idx
         self._flat.repack()
-        self._graphs = {}   # captured steps hold pointers into the previous call's batches
+        self.drop_alignment_cache()   # captured steps hold pointers into the previous call's batches, the rows belong to them
         ll = self._n_frames - lag
         _split(ll, self.test_ratio)                                  # core.py:465 (drawn, discarded)
         idx_train, idx_test = _split(ll, self.test_ratio)            # core.py:468
@@ -1256,7 +1331,7 @@ class EigenFunctionTask(TrainingTask):
 
         def test_one(it):                                          # core.py:535-551 (same loss, no update)
             X, w, Xl, wl = sl(Xte, *te_batches[it])
-            self._forward(X, w, Xl, wl, out=log_te[it])
+            self._forward(X, w, Xl, wl, out=log_te[it], cache=True)
 
         # every step of the epoch (static batches) replays from hipGraphs: ONE graph per epoch, or - small batches on a long
         # trajectory - one per kEpochChunk steps (a graph of many thousands of kernel nodes takes seconds to instantiate)

@@ -1,5 +1,5 @@
-// Shared by ef16_front.hip and ef16_back.hip (the 16-frames-per-wave step, split in two translation units so that they compile
-// side by side): constants of the unit decomposition, the front kernel's LDS layout, the net shapes covered and their dispatch.
+// Shared by ef16_front.hip, ef16_front_rows.hip and ef16_back.hip (the 16-frames-per-wave step, split in translation units so that
+// they compile side by side): constants of the unit decomposition, the front kernel's LDS layout, the net shapes covered and their dispatch.
 #pragma once
 #include "cvf_metric.hpp"
 #include "ef_frag.hpp"

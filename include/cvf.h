@@ -290,6 +290,19 @@ int cvf_ef16_front(const cvf_mlp_desc* mlp, const float* theta, const float* pac
 int cvf_ef16_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float* theta, const float* packed, int64_t B,
                       const float* w, const float* feat_tiled, const float* y_tiled, const float* q_tiled, const double* coef,
                       float* slab, int32_t* step_count, const float* saved, void* stream);
+/* A RESIDENT batch (csrc/ef16_front_rows.hip): the per-frame alignment records cvf_ef16_front solves for (rotation, centroid,
+ * K^-1) depend on the coordinates and the layer only, not on the parameters, so a loop that visits the same frames again - the
+ * static batches of core.py:472-481 - computes them once:
+ *  cvf_ef16_align_rows : x [B][n_coord] -> rows (cvf_ef16_align_rows_floats(B) floats, 16-byte aligned; opaque: per unit of 16
+ *                        frames the 16 x 21 floats the front kernel keeps on the chip, then the sum of the centred reference).
+ *  cvf_ef16_front_rows : cvf_ef16_front (same arguments, same outputs BIT FOR BIT) starting from `rows` instead of solving.
+ *                        The caller answers for `rows` being those of exactly these B frames of `x` under this `pp`. */
+int64_t cvf_ef16_align_rows_floats(int64_t B);
+int cvf_ef16_align_rows(const cvf_pp_desc* pp, const float* x, int64_t B, float* rows, void* stream);
+int cvf_ef16_front_rows(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled, const cvf_pp_desc* pp,
+                        const float* x, int64_t B, const float* a, float* y_tiled, float* saved, float* q_tiled, float* e_tiled,
+                        const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats, double* loss_vec, double* coef,
+                        const float* rows, void* stream);
 /* Transfer-operator mode (lag_tau > 0; core.py:403,414: y = model(pp_layer(X)) on the frames and on their lagged partners, then
  * core.py:420-431,440 and loss.backward()) on the same kernels:
  *  cvf_ef16_front_transfer   : x, x_lag [B][n_coord] -> feat_tiled [2T][d_r][64], y_tiled [2T][k][64] (the partners' tiles follow
