@@ -32,6 +32,7 @@ import math
 import os
 import types
 from abc import ABC, abstractmethod
+from typing import NamedTuple
 
 import numpy as np
 import pandas as pd
@@ -656,11 +657,31 @@ class TrainingTask(ABC):
         pass
 
 
-class _EFWorkspace:
-    """Device buffers of one batch size (all sizes follow include/cvf.h)."""
+class _EFRoute(NamedTuple):
+    """Which launches an EigenFunctionTask step runs: decided once per task, on first use (EigenFunctionTask._route), from the
+    nets, the layer and the developer switches below - every place that picks a launch reads this record.
 
-    def __init__(self, B, k, d_r, n_params, lag, mlp_desc, device, ef16=False, general=False):
+    Switches (environment; read once, when the route is decided, except as noted):
+      CVF_PIPELINE=1           align the next batch beside the backward launch (read at construction); turns the ef16 route off
+      CVF_NO_EF16              generator mode: no 16-frame route (the C library reads it too, in cvf_ef16_supported)
+      CVF_NO_EF16_TRANSFER     transfer mode: no 16-frame route
+      CVF_NO_TRANSFER_ROWS     ef16 transfer mode: the front launch without unit rows + cvf_ef_stats
+      CVF_NO_ALIGN_FWD         transfer mode: no fused alignment + forward launch (plain route instead)
+      CVF_NO_FWD_METRIC        read by the C library in cvf_ef_fwd_metric_supported: no fused generator launch
+      CVF_NO_ALIGN_FUSED       read by the C library in cvf_ef_align_fwd_metric_supported: alignment outside the fused launch
+    """
+    kind: str            # "ef16" (16 frames per wave), "fused" / "plain" (64-frame kernels) or "general" (per-layer launches)
+    align_inside: bool   # the forward launch can solve the alignment itself (used when the batch is not already aligned)
+    unit_rows: bool      # ef16 transfer mode: the paired front launch that leaves the units' rows of the time-lagged sums
+    backward: tuple      # (call name = C function, takes packed, takes w_lag, takes q) of the backward launch
+
+
+class _EFWorkspace:
+    """Device buffers of one batch size (all sizes follow include/cvf.h) and what the route needs to know about that size."""
+
+    def __init__(self, B, k, d_r, n_params, lag, mlp_desc, device, route):
         lib = _hip.lib()
+        ef16, general = route.kind == "ef16", route.kind == "general"
         T = _hip.ntiles(B)
         Tt = 2 * T if lag > 0 else T
         f32 = dict(device=device, dtype=torch.float32)
@@ -683,6 +704,7 @@ class _EFWorkspace:
                                    lib.cvf_ef_stats_scratch_doubles(k, lag), **f64)
         self.stats = torch.empty(lib.cvf_ef_nstats(k, lag), **f64)
         self.loss_vec = torch.empty(3 + 2 * k, **f64)
+        self.loss_out = self.loss_vec   # where this step's loss vector goes (_forward: the caller's row, else loss_vec)
         self.coef = torch.empty(4 * k + k * k, **f64)
         self._k1_scratch, self.k1_scratch_checked = [None, None], False   # large-molecule alignment scratch, sized on first use
         # hidden activations handed from the forward kernel to the backward kernel (0 floats: shape without hand-off)
@@ -692,6 +714,10 @@ class _EFWorkspace:
         self.saved = torch.empty(n_saved, **f32) if n_saved > 0 else None
         self.slab_rows = lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt)
         self.slab = torch.empty(self.slab_rows * n_params, **f32)
+        # the 16-frame step at this batch size: > 0 - the front launch leaves the units' rows of the batch sums in `scratch` and
+        # cvf_ef16_finish[_dp] adds them; 0 - it sums them itself (generator mode) / cvf_ef_stats does (transfer mode)
+        self.unit_rows = (0 if not ef16 else lib.cvf_ef16_rows(B) if lag == 0 else
+                          lib.cvf_ef16_transfer_rows(B, k) if route.unit_rows else 0)
         # alignment rows of the resident batches of this size (EigenFunctionTask._alignment_rows):
         # (X.data_ptr(), B) -> (X, X._version when the rows were filled, rows)
         self.align_rows = {}
@@ -834,15 +860,14 @@ class EigenFunctionTask(TrainingTask):
         # captured inside the graph (backend nccl only; a failed capture falls back to eager launches for good)
         self._use_graphs = os.environ.get("CVF_GRAPH", "1") != "0" and (not _dist.collectives() or _dist.backend() == "nccl" or
                                                                         _dist.fused_comm() is not None)   # (the peer-to-peer kernels capture on any backend)
-        # CVF_PIPELINE=1: the next batch's alignment (independent of the parameters) runs on this stream beside the
-        # current step's backward kernel.  Off by default: at 20 000 frames per step it measured 133 us/step against
-        # 126 serial - the two-branch graph costs more at the fork/join than the 14 us kernel it hides.
-        self._ef16 = None
+        self._route_record = None   # which launches a step runs (`_route`): decided on first use
         # (RegAutoEncoderTask drives an inner task of this class: `_local_only` - evaluate the batch handed in on this rank alone, no
         #  cross-rank sums; `_grad_local` - leave the parameter gradient un-reduced, the caller sums its own flat gradient later)
         self._local_only = self._grad_local = False
-        self._fused_fm = self._fused_k1 = self._fused_tr = None   # decided on first use: cvf_ef_[align_]fwd_metric_supported(nets, layer)
         self._side = torch.cuda.Stream(device=self.device)
+        # CVF_PIPELINE=1: the next batch's alignment (independent of the parameters) runs on this stream beside the
+        # current step's backward kernel.  Off by default: at 20 000 frames per step it measured 133 us/step against
+        # 126 serial - the two-branch graph costs more at the fork/join than the 14 us kernel it hides.
         self._pipeline = os.environ.get("CVF_PIPELINE", "0") == "1"
         # CVF_ALIGN_CACHE=0: every train step solves its frames' alignment again (see _alignment_rows); read once, here
         self._align_cache = os.environ.get("CVF_ALIGN_CACHE", "1") != "0"
@@ -892,15 +917,33 @@ class EigenFunctionTask(TrainingTask):
         ws = self._ws.get(B)
         if ws is None:
             ws = self._ws[B] = _EFWorkspace(B, self.k, self._pp.d_r, self._flat.n, self.lag_idx, self._flat.desc, self.device,
-                                            ef16=self._use_ef16(), general=self._general)
+                                            self._route)
         return ws
 
+    @property
+    def _route(self):
+        """The step's launches (:class:`_EFRoute`), decided on first use: the ONE place that reads the route's switches."""
+        if self._route_record is None:
+            lib, fl, pp, env, gen = _hip.lib(), self._flat, self._pp, os.environ, self.lag_idx == 0
+            if self._general:      # (no kernel instance: none of the queries below would say yes)
+                r = _EFRoute("general", False, False, ("cvf_ef_general_backward", False, True, True))
+            elif (not self._pipeline and env.get("CVF_NO_EF16" if gen else "CVF_NO_EF16_TRANSFER") is None
+                    and bool(lib.cvf_ef16_supported(fl.desc, pp))):
+                r = _EFRoute("ef16", True, not gen and env.get("CVF_NO_TRANSFER_ROWS") is None,
+                             ("cvf_ef16_backward", True, False, True) if gen else ("cvf_ef16_backward_transfer", True, True, False))
+            else:
+                if gen:   # [alignment,] nets forward, q = J A J^T g, E and the batch sums in one launch: g never leaves the chip
+                    fused = bool(lib.cvf_ef_fwd_metric_supported(fl.desc, pp))
+                    inside = fused and bool(lib.cvf_ef_align_fwd_metric_supported(fl.desc, pp))
+                else:     # alignment + forward of both frame sets in one launch
+                    fused = inside = env.get("CVF_NO_ALIGN_FWD") is None and bool(lib.cvf_ef_align_fwd_metric_supported(fl.desc, pp))
+                r = _EFRoute("fused" if fused else "plain", inside, False, ("cvf_ef_backward", True, True, True))
+            self._route_record = r
+        return self._route_record
+
     def _use_ef16(self):
-        """The fast layout: the 16-frames-per-wave step (csrc/ef16_front.hip, ef16_back.hip; generator and transfer-operator mode), decided once."""
-        if self._ef16 is None:
-            self._ef16 = (not self._pipeline and os.environ.get("CVF_NO_EF16_TRANSFER" if self.lag_idx > 0 else "CVF_NO_EF16") is None
-                          and bool(_hip.lib().cvf_ef16_supported(self._flat.desc, self._pp)))
-        return self._ef16
+        """The fast layout: the 16-frames-per-wave step (csrc/ef16_front.hip, ef16_back.hip; generator and transfer-operator mode)."""
+        return self._route.kind == "ef16"
 
     def _alignment_rows(self, ws, X):
         """The alignment rows (csrc/ef16_front_rows.hip: rotation, centroid and K^-1 of every frame, 84 bytes per frame) of the
@@ -979,139 +1022,118 @@ class EigenFunctionTask(TrainingTask):
         route keeps its alignment rows (:meth:`_alignment_rows`) - same results bit for bit.
         ``out``: fp64 device row of length 3 + 2k that receives the loss vector instead of ``ws.loss_vec`` (the training
         loops pass the step's slot of the epoch log: no copy kernel per step)."""
-        lib, s, P = _hip.lib(), _hip.stream(), _hip.ptr
-        B = X.shape[0]
-        ws = self._workspace(B)
+        route, s, P = self._route, _hip.stream(), _hip.ptr
+        assert not (aligned and route.kind == "ef16"), \
+            "the 16-frame step aligns inside its front launch: there is no prefetched feature buffer to start from (CVF_PIPELINE=1 turns it off)"
+        ws = self._workspace(X.shape[0])
         ws.slot = slot
-        fl, k, d_r = self._flat, self.k, self._pp.d_r
-        lag = self.lag_idx
         single = not _dist.collectives() or self._local_only   # no cross-rank reduction: the loss tail runs inside the stats launch
         ws.loss_out = ws.loss_vec if out is None else out
-        assert ws.loss_out.is_contiguous() and ws.loss_out.dtype == torch.float64 and ws.loss_out.numel() == 3 + 2 * k
+        assert ws.loss_out.is_contiguous() and ws.loss_out.dtype == torch.float64 and ws.loss_out.numel() == 3 + 2 * self.k
         lv, cf = (P(ws.loss_out), P(ws.coef)) if single else (None, None)
-        if self._use_ef16() and not aligned and lag > 0:
-            # transfer-operator mode: coordinates of the frames and of their lagged partners -> features, y, hidden activations
-            # in one launch (16 frames per wave), then the time-lagged batch sums and the loss tail
-            comm = None if single else _dist.fused_comm()
-            if lib.cvf_ef16_transfer_rows(B, k) > 0 and os.environ.get("CVF_NO_TRANSFER_ROWS") is None:
-                # a unit and its lagged partner in one block: the units' rows of the time-lagged sums leave the front launch,
-                # the finishing launch adds them (+ collective #1 in a data-parallel job) and evaluates the loss tail
-                self._call("cvf_ef16_front_transfer", lib.cvf_ef16_front_transfer_rows, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat),
-                           self._pp, P(X), P(X_lag), B, P(ws.y), P(ws.saved), P(w), P(w_lag), P(ws.scratch), s)
-                if comm is not None:
-                    self._call("cvf_ef16_finish_dp", lib.cvf_ef16_finish_dp, self._cfg, B, P(ws.scratch), P(ws.stats), P(ws.loss_out),
-                               P(ws.coef), comm, s)
-                    return ws
-                self._call("cvf_ef16_finish", lib.cvf_ef16_finish, self._cfg, B, P(ws.scratch), P(ws.stats), lv, cf, s)
-                if not single:
-                    self._sum_stats_and_tail(ws)                                                            # collective #1
-                return ws
-            self._call("cvf_ef16_front_transfer", lib.cvf_ef16_front_transfer, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat),
-                       self._pp, P(X), P(X_lag), B, P(ws.y), P(ws.saved), s)
-            y_lag = ws.y[ws.T * k * _hip.TILE:]
-            if comm is not None:   # collective #1 and the loss tail inside the finishing launch of the sums
-                self._call("cvf_ef_stats_dp", lib.cvf_ef_stats_dp, self._cfg, B, P(w), P(ws.y), None, P(w_lag), P(y_lag),
-                           P(ws.scratch), P(ws.stats), P(ws.loss_out), P(ws.coef), comm, s)
-                return ws
-            self._call("cvf_ef_stats", lib.cvf_ef_stats, self._cfg, B, P(w), P(ws.y), None, P(w_lag), P(y_lag),
-                       P(ws.scratch), P(ws.stats), lv, cf, s)
-            if not single:
-                self._sum_stats_and_tail(ws)                                                                # collective #1
-            return ws
-        if self._use_ef16() and not aligned:
-            # coordinates -> features, y, hidden activations, q = J A J^T g, E and the batch sums in one launch, 16 frames per
-            # wave (+ the short launch that adds the units' rows and evaluates the loss tail)
-            rows = lib.cvf_ef16_rows(B) > 0   # the units' rows of batch sums are added by a second, short launch
-            al = self._alignment_rows(ws, X) if cache else None
-            if al is not None:   # (the same name for either form: one call of the step, the same outputs)
-                self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), B,
-                           P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch),
-                           None if rows else P(ws.stats), lv, cf, P(al), s)
-            else:
-                self._call("cvf_ef16_front", lib.cvf_ef16_front, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), B,
-                           P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch),
-                           None if rows else P(ws.stats), lv, cf, s)
-            comm = None if single else _dist.fused_comm()
-            if rows and comm is not None:   # the units' rows -> sums -> collective #1 -> loss tail: one launch
-                self._call("cvf_ef16_finish_dp", lib.cvf_ef16_finish_dp, self._cfg, B, P(ws.scratch), P(ws.stats), P(ws.loss_out),
-                           P(ws.coef), comm, s)
-                return ws
-            if rows:
-                self._call("cvf_ef16_finish", lib.cvf_ef16_finish, self._cfg, B, P(ws.scratch), P(ws.stats), lv, cf, s)
-            if not single:
-                self._sum_stats_and_tail(ws)                                                                # collective #1
-            return ws
-        if not ws.k1_scratch_checked:
-            ws._k1_scratch = [_hip.align_scratch(self._pp, B, self.device) for _ in range(2)]
+        if route.kind != "ef16" and not ws.k1_scratch_checked:
+            ws._k1_scratch = [_hip.align_scratch(self._pp, ws.B, self.device) for _ in range(2)]
             ws.k1_scratch_checked = True
-        if self._fused_fm is None:
-            self._fused_fm = lag == 0 and bool(lib.cvf_ef_fwd_metric_supported(fl.desc, self._pp))
-            self._fused_k1 = self._fused_fm and bool(lib.cvf_ef_align_fwd_metric_supported(fl.desc, self._pp))
-        with_k1 = self._fused_k1 and not aligned   # the alignment runs inside the fused launch
-        if self._fused_tr is None:                 # transfer mode: alignment + forward of both frame sets in one launch
-            self._fused_tr = (lag > 0 and os.environ.get("CVF_NO_ALIGN_FWD") is None and
-                              bool(lib.cvf_ef_align_fwd_metric_supported(fl.desc, self._pp)))
-        with_tr = self._fused_tr and not aligned
-        if not aligned and not with_k1 and not with_tr:
-            self._align(ws, slot, X, X_lag)
-        if self._fused_fm:   # [alignment,] nets forward, q = J A J^T g, E and the batch sums in one launch: g never leaves the chip
-            name, fn = (("cvf_ef_align_fwd_metric_stats", lib.cvf_ef_align_fwd_metric_stats) if with_k1 else
-                        ("cvf_ef_fwd_metric_stats", lib.cvf_ef_fwd_metric_stats))
-            rows = lib.cvf_ef_fused_stats_rows(fl.desc, self._pp, B, int(with_k1))   # > 0: per-tile sums left for a short second launch
-            self._call(name, fn, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat),
-                       self._pp, P(X), B, P(ws.aux), P(self._diag_coeff), P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg,
-                       P(w), P(ws.scratch), None if rows > 0 else P(ws.stats), lv, cf, s)
-            if rows > 0:
-                self._call("cvf_ef_stats_finish_rows", lib.cvf_ef_stats_finish_rows, self._cfg, rows, P(ws.scratch), P(ws.stats),
-                           lv, cf, s)
-            if not single:
-                self._sum_stats_and_tail(ws)                                                                # collective #1
-            return ws
-        if with_tr:
-            self._call("cvf_ef_align_fwd", lib.cvf_ef_align_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X),
-                       P(X_lag), B, P(ws.y), P(ws.saved), s)
-        elif self._general:
-            self._call("cvf_ef_general_fwd", lib.cvf_ef_general_fwd, fl.desc, P(fl.theta), P(ws.feat), ws.Tt, P(ws.y),
-                       P(ws.g) if lag == 0 else None, P(ws.saved), s)
-        else:
-            self._call("cvf_ef_mlp_fwd", lib.cvf_ef_mlp_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), ws.Tt, P(ws.y),
-                       P(ws.g) if lag == 0 else None, P(ws.saved), s)
-        if lag == 0:   # q = J A J^T g, E, and the batch sums (K2/K3 + K5) in one launch
-            self._call("cvf_metric_apply", lib.cvf_metric_apply_stats, self._pp, P(X), B, P(ws.aux), P(self._diag_coeff), k,
-                       P(ws.g), P(ws.q), P(ws.e), P(ws.k1_scratch), P(self._dense), self._cfg, P(w), P(ws.y),
-                       P(ws.scratch), P(ws.stats), lv, cf, s)
-        else:
-            y_lag = ws.y[ws.T * k * _hip.TILE:]
-            self._call("cvf_ef_stats", lib.cvf_ef_stats, self._cfg, B, P(w), P(ws.y), None, P(w_lag), P(y_lag),
-                       P(ws.scratch), P(ws.stats), lv, cf, s)
-        if not single:
-            self._sum_stats_and_tail(ws)                                                                    # collective #1
+        fwd = ((self._fwd_ef16_gen if self.lag_idx == 0 else self._fwd_ef16_tr) if route.kind == "ef16" else
+               self._fwd_fused_gen if route.kind == "fused" and self.lag_idx == 0 else self._fwd_separate)
+        # The route's launches.  `fin`: the launch that finishes the batch sums, left to the rule below - (call name, C function,
+        # its `_dp` twin or None, arguments up to `stats`) - or None: the forward launch took `stats` (and `lv`, `cf`) itself.
+        fin = fwd(ws, X, w, X_lag, w_lag, aligned, cache, lv, cf)
+        # Who adds the rows, who sums over the ranks, who runs the loss tail:
+        if fin is not None:
+            name, fn, fn_dp, head = fin
+            comm = None if single or fn_dp is None else _dist.fused_comm()
+            if comm is not None:   # 2. rows -> sums -> collective #1 -> loss tail in ONE launch over the peer-to-peer windows
+                self._call(fn_dp.__name__, fn_dp, *head, P(ws.stats), P(ws.loss_out), P(ws.coef), comm, s)
+                return ws
+            self._call(name, fn, *head, P(ws.stats), lv, cf, s)   # 1. (single: `lv`, `cf` set) it runs the loss tail itself
+        if not single:                                            # 3. else collective #1 and the tail follow the sums
+            self._sum_stats_and_tail(ws)
         return ws
+
+    def _fwd_ef16_gen(self, ws, X, w, X_lag, w_lag, aligned, cache, lv, cf):
+        """coordinates -> features, y, hidden activations, q = J A J^T g, E and the batch sums in one launch, 16 frames per wave;
+        the units' rows of the sums are left to cvf_ef16_finish[_dp] (batches past cvf_ef16_rows: summed in the front launch)."""
+        lib, fl, s, P = _hip.lib(), self._flat, _hip.stream(), _hip.ptr
+        args = (fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), ws.B, P(self._diag_coeff), P(ws.y), P(ws.saved),
+                P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch), None if ws.unit_rows else P(ws.stats), lv, cf)
+        al = self._alignment_rows(ws, X) if cache else None
+        if al is not None:   # (the same name for either form: one call of the step, the same outputs)
+            self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, *args, P(al), s)
+        else:
+            self._call("cvf_ef16_front", lib.cvf_ef16_front, *args, s)
+        if ws.unit_rows:
+            return "cvf_ef16_finish", lib.cvf_ef16_finish, lib.cvf_ef16_finish_dp, (self._cfg, ws.B, P(ws.scratch))
+        return None
+
+    def _fwd_ef16_tr(self, ws, X, w, X_lag, w_lag, aligned, cache, lv, cf):
+        """Transfer-operator mode: coordinates of the frames and of their lagged partners -> features, y, hidden activations in one
+        launch (16 frames per wave), then the time-lagged batch sums."""
+        lib, fl, s, P = _hip.lib(), self._flat, _hip.stream(), _hip.ptr
+        args = (fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), P(X_lag), ws.B, P(ws.y), P(ws.saved))
+        if ws.unit_rows:   # a unit and its lagged partner in one block: the units' rows of the sums leave the front launch
+            self._call("cvf_ef16_front_transfer", lib.cvf_ef16_front_transfer_rows, *args, P(w), P(w_lag), P(ws.scratch), s)
+            return "cvf_ef16_finish", lib.cvf_ef16_finish, lib.cvf_ef16_finish_dp, (self._cfg, ws.B, P(ws.scratch))
+        self._call("cvf_ef16_front_transfer", lib.cvf_ef16_front_transfer, *args, s)
+        return self._lagged_stats(ws, w, w_lag, lib.cvf_ef_stats_dp)
+
+    def _lagged_stats(self, ws, w, w_lag, fn_dp):
+        """The finishing launch of transfer mode: the time-lagged batch sums of ``ws.y``."""
+        lib, P = _hip.lib(), _hip.ptr
+        y_lag = ws.y[ws.T * self.k * _hip.TILE:]
+        return "cvf_ef_stats", lib.cvf_ef_stats, fn_dp, (self._cfg, ws.B, P(w), P(ws.y), None, P(w_lag), P(y_lag), P(ws.scratch))
+
+    def _fwd_fused_gen(self, ws, X, w, X_lag, w_lag, aligned, cache, lv, cf):
+        """Generator mode, 64 frames per wave: [alignment,] nets forward, q = J A J^T g, E and the batch sums in one launch (no
+        `_dp` twin of its finishing launch: collective #1 and the loss tail follow in their own)."""
+        lib, fl, s, P = _hip.lib(), self._flat, _hip.stream(), _hip.ptr
+        inside = self._route.align_inside and not aligned
+        if not aligned and not inside:
+            self._align(ws, ws.slot, X, X_lag)
+        name, fn = (("cvf_ef_align_fwd_metric_stats", lib.cvf_ef_align_fwd_metric_stats) if inside else
+                    ("cvf_ef_fwd_metric_stats", lib.cvf_ef_fwd_metric_stats))
+        rows = lib.cvf_ef_fused_stats_rows(fl.desc, self._pp, ws.B, int(inside))   # > 0: per-tile sums left for a short second launch
+        self._call(name, fn, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), ws.B, P(ws.aux), P(self._diag_coeff),
+                   P(ws.y), P(ws.saved), P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch), None if rows > 0 else P(ws.stats), lv, cf, s)
+        if rows > 0:
+            return "cvf_ef_stats_finish_rows", lib.cvf_ef_stats_finish_rows, None, (self._cfg, rows, P(ws.scratch))
+        return None
+
+    def _fwd_separate(self, ws, X, w, X_lag, w_lag, aligned, cache, lv, cf):
+        """The forward launch and the statistics launch apart: the plain and general routes, and transfer mode of the fused route
+        (alignment inside the forward launch).  Neither statistics launch is handed a `_dp` twin here."""
+        lib, fl, s, P = _hip.lib(), self._flat, _hip.stream(), _hip.ptr
+        gen = self.lag_idx == 0
+        inside = self._route.align_inside and not aligned
+        if not aligned and not inside:
+            self._align(ws, ws.slot, X, X_lag)
+        if inside:
+            self._call("cvf_ef_align_fwd", lib.cvf_ef_align_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X),
+                       P(X_lag), ws.B, P(ws.y), P(ws.saved), s)
+        elif self._route.kind == "general":
+            self._call("cvf_ef_general_fwd", lib.cvf_ef_general_fwd, fl.desc, P(fl.theta), P(ws.feat), ws.Tt, P(ws.y), P(ws.g), P(ws.saved), s)
+        else:
+            self._call("cvf_ef_mlp_fwd", lib.cvf_ef_mlp_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), ws.Tt, P(ws.y), P(ws.g),
+                       P(ws.saved), s)
+        if not gen:
+            return self._lagged_stats(ws, w, w_lag, None)
+        # q = J A J^T g, E, and the batch sums (K2/K3 + K5) in one launch
+        return "cvf_metric_apply", lib.cvf_metric_apply_stats, None, (
+            self._pp, P(X), ws.B, P(ws.aux), P(self._diag_coeff), self.k, P(ws.g), P(ws.q), P(ws.e), P(ws.k1_scratch), P(self._dense),
+            self._cfg, P(w), P(ws.y), P(ws.scratch))
 
     def _backward(self, ws, w, w_lag=None, advance=False, fuse_adam=False):
         """Parameter gradient into the flat buffer.  ``advance``: this gradient belongs to an optimiser step
         (the kernel advances the device step counter).  ``fuse_adam``: single-process training - the kernel
         that sums the per-block partial gradients applies the Adam update in the same launch."""
         lib, fl, P = _hip.lib(), self._flat, _hip.ptr
-        if self._use_ef16() and self.lag_idx > 0:
-            self._call("cvf_ef16_backward_transfer", lib.cvf_ef16_backward_transfer, self._cfg, fl.desc, P(fl.theta), P(fl.packed), ws.B,
-                       P(w), P(w_lag), P(ws.feat), P(ws.y), P(ws.coef), P(ws.slab),
-                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
-        elif self._use_ef16():
-            self._call("cvf_ef16_backward", lib.cvf_ef16_backward, self._cfg, fl.desc, P(fl.theta), P(fl.packed), ws.B, P(w),
-                       P(ws.feat), P(ws.y), P(ws.q), P(ws.coef), P(ws.slab),
-                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
-        elif self._general:
-            self._call("cvf_ef_general_backward", lib.cvf_ef_general_backward, self._cfg, fl.desc, P(fl.theta), ws.B, P(w), P(w_lag),
-                       P(ws.feat), P(ws.y), P(ws.q) if self.lag_idx == 0 else None, P(ws.coef), P(ws.slab),
-                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
-        else:
-            self._call("cvf_ef_backward", lib.cvf_ef_backward, self._cfg, fl.desc, P(fl.theta), P(fl.packed), ws.B, P(w), P(w_lag),
-                       P(ws.feat), P(ws.y), P(ws.q) if self.lag_idx == 0 else None, P(ws.coef), P(ws.slab),
-                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
+        name, packed, lagged, q = self._route.backward
+        self._call(name, getattr(lib, name), self._cfg, fl.desc, P(fl.theta), *([P(fl.packed)] if packed else []), ws.B, P(w),
+                   *([P(w_lag)] if lagged else []), P(ws.feat), P(ws.y), *([P(ws.q)] if q else []), P(ws.coef), P(ws.slab),
+                   P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
         local = self._local_only or self._grad_local
         # (the general route's gradient exceeds the peer-to-peer window of cvf_slab_reduce_dp: slab reduction + all-reduce)
-        comm = None if local or self._general else _dist.fused_comm()
+        comm = None if local or self._route.kind == "general" else _dist.fused_comm()
         if comm is not None:   # sum of the slab rows -> collective #2 -> (train_step) the identical Adam update: one launch
             adam = self.optimizer.fused_args() if advance else None
             self._call("cvf_slab_reduce_dp", lib.cvf_slab_reduce_dp, P(ws.slab), ws.slab_rows, fl.n, P(fl.grad), adam, comm, _hip.stream())
@@ -1143,43 +1165,14 @@ class EigenFunctionTask(TrainingTask):
     #    (batch, kind) pair is captured once and replayed in all later epochs: one host call per step
     def _graph_step(self, key, fn, out_slot, takes_out=False):
         """Run ``fn()`` (a step that returns the device loss vector) and copy its result into ``out_slot``;
-        captured into a hipGraph on first use when graphs are enabled.
-
-        A replay does not pass through Python: a captured train step assumes static batch POINTERS and, since it starts from
-        the batch's alignment rows (:meth:`_alignment_rows`; the ``_version`` check cannot run in a replay), static batch
-        CONTENTS.  train() owns its gathered copies; a caller that rewrites a batch in place calls :meth:`drop_alignment_cache`,
-        which drops the captured graphs with the rows."""
+        through :meth:`_graph_call`: captured into a hipGraph on first use when graphs are enabled."""
         def run():
             # (steps that take the slot write their loss vector there themselves; others return a tensor to copy)
             got = fn(out_slot) if takes_out else fn()
             if got is not out_slot and got.data_ptr() != out_slot.data_ptr():
                 out_slot.copy_(got)
 
-        if not self._use_graphs:
-            run()
-            return
-        g = self._graphs.get(key)
-        if g is None:
-            run()                                     # eager warm-up: allocates the workspace of this batch size
-            torch.cuda.current_stream().synchronize()
-            gc.collect()                              # (see _graph_call)
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    run()
-            except Exception as exc:                   # e.g. a collective that cannot be captured on this stack
-                if not _dist.collectives():
-                    raise
-                self._use_graphs = False
-                self._graphs.clear()
-                torch.cuda.synchronize()
-                print(f"[colvarsfinder] hipGraph capture of the data-parallel step failed ({type(exc).__name__}: {exc}); "
-                      "continuing with eager launches", flush=True)
-                return
-            self._graphs[key] = g
-            return                                     # the warm-up call already did this step's work once... see note
-        self.optimizer.sync_lr()                       # the captured kernels read the learning rate from a device scalar
-        g.replay()
+        self._graph_call(key, run)
 
     def _graph_call(self, key, body):
         """Run ``body()`` - any sequence of steps on static batches that writes its results into fixed device buffers, e.g.
@@ -1187,14 +1180,16 @@ class EigenFunctionTask(TrainingTask):
         replayed afterwards.  One replay per epoch instead of one per step: the ~9 us the GPU idles between two graph
         launches (rocprofv3 kernel trace of bench.py) is paid once per epoch.
 
-        As in :meth:`_graph_step`, the captured steps assume that the batches' CONTENTS are static, not only their addresses
-        (they read the alignment rows of the eager run); :meth:`drop_alignment_cache` drops the graphs with the rows."""
+        A replay does not pass through Python: the captured steps assume static batch POINTERS and, since they start from
+        the batches' alignment rows (:meth:`_alignment_rows`; the ``_version`` check cannot run in a replay), static batch
+        CONTENTS.  train() owns its gathered copies; a caller that rewrites a batch in place calls :meth:`drop_alignment_cache`,
+        which drops the captured graphs with the rows."""
         if not self._use_graphs:
             body()
             return
         g = self._graphs.get(key)
         if g is None:
-            body()
+            body()                                     # eager: allocates the workspaces (and does this call's work)
             torch.cuda.current_stream().synchronize()
             self.optimizer.sync_lr()
             # unreachable tasks of the same process may still hold captured graphs; the cycle collector would destroy them whenever
@@ -1210,12 +1205,12 @@ class EigenFunctionTask(TrainingTask):
                 self._use_graphs = False
                 self._graphs.clear()
                 torch.cuda.synchronize()
-                print(f"[colvarsfinder] hipGraph capture of the data-parallel epoch failed ({type(exc).__name__}: {exc}); "
+                print(f"[colvarsfinder] hipGraph capture of the data-parallel steps failed ({type(exc).__name__}: {exc}); "
                       "continuing with eager launches", flush=True)
                 return
             self._graphs[key] = g
-            return                                     # (the eager run above already did this call's work)
-        self.optimizer.sync_lr()
+            return
+        self.optimizer.sync_lr()                       # the captured kernels read the learning rate from a device scalar
         g.replay()
 
     def _dev(self, t, dtype=torch.float32):

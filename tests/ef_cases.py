@@ -4,23 +4,24 @@ Plain Python (no torch, no GPU).  `tests/test_ef_instances.py` (CPU) reads the i
 checks that every one is claimed by a case here or listed in `UNREACHABLE`; `tests/test_ef_sweep_gpu.py` runs every case on
 the GPU against the fp64 oracle and checks that the launches are the ones `route()` predicts.
 
-The rules below mirror the host dispatch; the comments cite the lines they copy.  If the C++ changes, change them too: the
-GPU sweep's launch check (`launches()`) fails when the mirror and the host disagree.
+The rules below mirror the host dispatch; the comments name the functions they copy.  If those change, change them too: the
+GPU sweep's checks (`route()` against the task's own route record, `launches()` against its calls) fail when the mirror and
+the host disagree.
 """
 
 from collections import namedtuple
 
 # ---------------------------------------------------------------------------------------------------- shapes and limits
-# ef16_dispatch, csrc/ef16_common.hpp:68-81 - the 16-frames-per-wave step (ef16_front.hip, ef16_back.hip)
+# ef16_dispatch (csrc/ef16_common.hpp) - the 16-frames-per-wave step (ef16_front.hip, ef16_back.hip)
 EF16_SHAPES = ((8, 1), (8, 2), (8, 3), (12, 1), (12, 2), (12, 3), (16, 1), (16, 2), (16, 3), (20, 1), (20, 2), (20, 3),
                (24, 2), (24, 3), (32, 2), (32, 3))
-# ef_dispatch, csrc/ef_mfma.hip:1602-1626 - the 64-frame kernels
+# ef_dispatch (csrc/ef_mfma.hip) - the 64-frame kernels
 EF_SHAPES = EF16_SHAPES + ((48, 2), (48, 3), (64, 2), (64, 3), (20, 4), (20, 5), (32, 4), (32, 5))
-FUSED_MAX_H = 32     # kFusedMaxH, ef_mfma.hip:1601: the fused launches are instantiated up to 32 units
+FUSED_MAX_H = 32     # kFusedMaxH (ef_mfma.hip): the fused launches are instantiated up to 32 units
 MAX_NETS = 8         # CVF_MAX_NETS
-TILE, UNIT = 64, 16  # CVF_TILE (include/cvf.h), kU (ef16_common.hpp:13)
-IMG_PITCH, AUX_PITCH = 76, 21   # kImgP, kAuxP (ef16_common.hpp:14-16)
-SLAB_ROWS = 1024     # cvf_ef16_backward_slab_rows, ef16_back.hip:356
+TILE, UNIT = 64, 16  # CVF_TILE (include/cvf.h), kU (ef16_common.hpp)
+IMG_PITCH, AUX_PITCH = 76, 21   # kImgP, kAuxP (ef16_common.hpp)
+SLAB_ROWS = 1024     # cvf_ef16_backward_slab_rows (ef16_back.hip)
 
 # MIXED features of tests/test_gpu_parity.py: positions, bonds, angles and dihedrals of a 10-atom molecule (d_r = 22)
 MIXED = [("position", (0, 2, 3, 5)), ("bond", (0, 1)), ("bond", (2, 7)), ("angle", (1, 2, 3)),
@@ -46,7 +47,7 @@ def _nrec_options(nit):
 
 
 def front16_lds_bytes(n_coord, n_align, k):
-    """front16_lds(nc, nal, k).total * 4, ef16_common.hpp:33-48 (x_tile_stride: cvf_common.hpp:151)."""
+    """front16_lds(nc, nal, k).total * 4 (ef16_common.hpp; the stride: x_tile_stride, cvf_common.hpp)."""
     stride = n_coord if n_coord & 3 == 2 else n_coord | 1
     ref = UNIT * stride
     a = ref + 3 * n_align
@@ -140,19 +141,19 @@ def d_r(case):
 
 
 def shape(case):
-    """(H, NH) of the nets; the cases use kernel widths only (no zero padding, core.py:370-420)."""
+    """(H, NH) of the nets; the cases use kernel widths only (no zero padding: _FlatParams._init_padded)."""
     H = case.hidden[0]
     assert all(h == H for h in case.hidden), case
     return H, len(case.hidden)
 
 
 def _pos_fast(case):
-    # CVF_PP_ALIGN_CONTIG | CVF_PP_PURE_POSITION (pp.py:104-109): aligned on atoms 0..n_align-1, positions of atoms 0..n_rec-1
+    # CVF_PP_ALIGN_CONTIG | CVF_PP_PURE_POSITION (AlignFeatureLayer.pp_desc): aligned on atoms 0..n_align-1, positions of atoms 0..n_rec-1
     return case.layout == "pos"
 
 
 def ef16_supported(case):
-    """cvf_ef16_supported, ef16_front.hip:649-658, and EigenFunctionTask._use_ef16, core.py:879-884."""
+    """cvf_ef16_supported (ef16_front.hip) and the ef16 row of EigenFunctionTask._route."""
     H, NH = shape(case)
     nc = 3 * case.n_atoms
     return (not case.no_ef16 and NH <= 3 and (H, NH) in EF16_SHAPES and _pos_fast(case)
@@ -161,15 +162,15 @@ def ef16_supported(case):
 
 
 def fwd_metric_lds_bytes(n_coord, n_align, k):
-    """fwd_metric_lds, ef_mfma.hip:1722-1725."""
+    """fwd_metric_lds (ef_mfma.hip)."""
     stride = n_coord if n_coord & 3 == 2 else n_coord | 1
     head = (TILE * stride + 3 * n_align + n_coord + 3) & ~3
     return 4 * (head + k * n_coord * TILE + k * TILE)
 
 
 def _saved_floats_ok(case):
-    """cvf_ef_saved_floats(mlp, 1) > 0 for H <= 32 (ef_mfma.hip:1659-1668): fwd_wg_ok (ef_mfma.hip:1653-1657, pack_layout:
-    cvf_pack.hpp:20-29) or a first layer wider than kWideD = 128."""
+    """cvf_ef_saved_floats(mlp, 1) > 0 for H <= 32 (ef_mfma.hip): fwd_wg_ok (ef_mfma.hip; pack_layout: cvf_pack.hpp) or a first
+    layer wider than kWideD = 128."""
     H, NH = shape(case)
     D = d_r(case)
     ng, s1, ct = (H + 3) // 4, (D + 3) // 4, (D + 15) // 16
@@ -178,7 +179,7 @@ def _saved_floats_ok(case):
 
 
 def fwd_metric_supported(case):
-    """cvf_ef_fwd_metric_supported, ef_mfma.hip:1729-1737."""
+    """cvf_ef_fwd_metric_supported (ef_mfma.hip)."""
     H, NH = shape(case)
     nc = 3 * case.n_atoms
     return (H <= FUSED_MAX_H and _pos_fast(case) and case.n_align <= case.n_rec and d_r(case) <= 72 and nc <= 192
@@ -186,22 +187,24 @@ def fwd_metric_supported(case):
 
 
 def route(case):
-    """'ef16', 'fused' (gen: cvf_ef_[align_]fwd_metric_stats; tr: cvf_ef_align_fwd) or 'plain' - core.py:923-1008."""
+    """'ef16', 'fused' (gen: cvf_ef_[align_]fwd_metric_stats; tr: cvf_ef_align_fwd) or 'plain': `kind` of the task's route record
+    (EigenFunctionTask._route), which the GPU sweep compares with this."""
     if ef16_supported(case):
         return "ef16"
-    if fwd_metric_supported(case) and (case.mode == "gen" or 3 * case.n_atoms >= 30):   # tr: ef_mfma.hip:1836-1839, core.py:976
+    if fwd_metric_supported(case) and (case.mode == "gen" or 3 * case.n_atoms >= 30):   # tr: cvf_ef_align_fwd_metric_supported
         return "fused"
     return "plain"
 
 
 def launches(case):
-    """The C-ABI calls (EigenFunctionTask._call names) of one loss_func + backward, core.py:923-1037."""
+    """The C-ABI calls (EigenFunctionTask._call names) of one loss_func + backward: the _fwd_* method of the route, the rule at the
+    end of EigenFunctionTask._forward, and _backward (tests/test_ef_routes_gpu.py pins their order and counts)."""
     r, gen = route(case), case.mode == "gen"
     if r == "ef16":
         return {"cvf_ef16_front", "cvf_ef16_finish", "cvf_ef16_backward", "cvf_slab_reduce"} if gen else \
                {"cvf_ef16_front_transfer", "cvf_ef16_finish", "cvf_ef16_backward_transfer", "cvf_slab_reduce"}
     if r == "fused" and gen:
-        k1 = 3 * case.n_atoms >= 30   # cvf_ef_align_fwd_metric_supported, ef_mfma.hip:1836-1839
+        k1 = 3 * case.n_atoms >= 30   # cvf_ef_align_fwd_metric_supported
         return {"cvf_ef_align_fwd_metric_stats" if k1 else "cvf_ef_fwd_metric_stats", "cvf_ef_stats_finish_rows", "cvf_ef_backward",
                 "cvf_slab_reduce"} | (set() if k1 else {"cvf_align_feature_fwd"})
     if r == "fused":
@@ -222,15 +225,15 @@ def instances(case, B=None):
     H, NH = shape(case)
     gen, r = case.mode == "gen", route(case)
     if r == "ef16":
-        # front: NIT = ceil(n_rec / 4), ALLAL = (n_align == n_rec) (ef16_front.hip:724-742); transfer: <H, NH, 0, true> (:775)
+        # front: NIT = ceil(n_rec / 4), ALLAL = (n_align == n_rec) (cvf_ef16_front); transfer: <H, NH, 0, true> (ef16_front_transfer_impl)
         front = ("ef16_front_kernel", H, NH, (case.n_rec + 3) // 4, int(case.n_align == case.n_rec)) if gen else \
                 ("ef16_front_kernel", H, NH, 0, 1)
-        # back: MULTI when the backward tiles (T, or 2 T with the lagged partners) outnumber the 1024 slab rows (ef16_back.hip:383-402)
+        # back: MULTI when the backward tiles (T, or 2 T with the lagged partners) outnumber the 1024 slab rows (cvf_ef16_backward[_transfer])
         tiles = n_tiles(B) if gen else 2 * n_tiles(B)
         return {front, ("ef16_back_kernel", H, NH, int(tiles > SLAB_ROWS), int(gen))}
-    out = {("ef_bwd_mfma_kernel", H, NH)}                       # ef_mfma.hip:1915-1920
+    out = {("ef_bwd_mfma_kernel", H, NH)}                       # cvf_ef_backward
     if r == "fused":
-        out.add(("ef_fwd_metric_kernel", H, NH) if gen else ("ef_align_fwd_kernel", H, NH))   # ef_mfma.hip:1775-1777, 1812
+        out.add(("ef_fwd_metric_kernel", H, NH) if gen else ("ef_align_fwd_kernel", H, NH))   # fwd_metric_launch, cvf_ef_align_fwd
     return out
 
 

@@ -164,7 +164,7 @@ def _run_case(dev, hidden, k, act, B, mode, seed):
     layer = pp.AlignFeatureLayer(N_ATOMS, spec["align_idx"], spec["ref_pos"], spec["features"], False).to(dev)
     dims = [layer.d_r] + list(hidden) + [1]
     task, model, sd0, a, eig_w = _task(dev, traj, w, layer, dims, k, act, gen)
-    assert task._general and task._flat.packed is None
+    assert task._general and task._route.kind == "general" and task._flat.packed is None
     X, wt = torch.tensor(traj[:B]), torch.tensor(w[:B])
     Xl, wl = (None, None) if gen else (torch.tensor(traj[lag:lag + B]), torch.tensor(w[lag:lag + B]))
     v, got, cvec, launched = _step(task, model, X, wt, Xl, wl)

@@ -1,9 +1,9 @@
 """GPU (-m gpu): one EigenFunctionTask step (loss_func + backward) per case of tests/ef_cases.py against the fp64 oracle - every
 compiled instance of the step's kernels (tests/test_ef_instances.py checks that the cases claim them all).
 
-Each case asserts the route the host took (the task's C-ABI launches, and cvf_ef16_supported for the fast layout), so a
-shape that silently fell back to another kernel cannot pass as coverage.  The MULTI backward instances (more than 1024
-backward tiles) are checked by duplication: two copies of a case's batch give its loss, eigenvalues and gradient, with the
+Each case asserts the route the host took (the task's route record and C-ABI launches, and cvf_ef16_supported for the fast
+layout), so a shape that silently fell back to another kernel cannot pass as coverage.  The MULTI backward instances (more than
+1024 backward tiles) are checked by duplication: two copies of a case's batch give its loss, eigenvalues and gradient, with the
 bars of test_gpu_parity.py::test_large_batch_paths_by_duplication; the case itself is checked against the oracle first.
 
 Bars.  The sweep started from KAT_TOL["f64"] of test_gpu_parity.py (1e-6 / 1e-6 / 1e-5), which the golden fixtures meet on
@@ -118,6 +118,7 @@ def test_step_vs_fp64_oracle(dev, case, monkeypatch):
         return np.asarray([float(loss), float(npl), float(pen)] + [float(e) for e in eig]), g, list(cvec), launched
 
     v, got, cvec, launched = step(1)
+    assert task._route.kind == E.route(case), (task._route, E.route(case))   # the host's own record of the route it took
     assert launched == E.launches(case), (launched, E.launches(case))
 
     torch.set_default_dtype(torch.float64)
