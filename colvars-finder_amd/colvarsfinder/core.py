@@ -718,11 +718,13 @@ class _EFWorkspace:
         # cvf_ef16_finish[_dp] adds them; 0 - it sums them itself (generator mode) / cvf_ef_stats does (transfer mode)
         self.unit_rows = (0 if not ef16 else lib.cvf_ef16_rows(B) if lag == 0 else
                           lib.cvf_ef16_transfer_rows(B, k) if route.unit_rows else 0)
-        # alignment rows of the resident batches of this size (EigenFunctionTask._alignment_rows):
-        # (X.data_ptr(), B) -> (X, X._version when the rows were filled, rows)
+        # alignment rows and feature tile of the resident batches of this size (EigenFunctionTask._alignment_rows):
+        # (X.data_ptr(), B) -> (X, X._version when they were filled, rows, tile)
         self.align_rows = {}
+        self.tile = None   # the resident batch's feature tile this step's front launch read (None: it wrote `feat`)
 
     feat = property(lambda self: self._feat[self.slot])
+    feat_in = property(lambda self: self._feat[self.slot] if self.tile is None else self.tile)   # what the backward launch reads
     aux = property(lambda self: self._aux[self.slot])
     k1_scratch = property(lambda self: self._k1_scratch[self.slot])
 
@@ -871,7 +873,7 @@ class EigenFunctionTask(TrainingTask):
         self._pipeline = os.environ.get("CVF_PIPELINE", "0") == "1"
         # CVF_ALIGN_CACHE=0: every train step solves its frames' alignment again (see _alignment_rows); read once, here
         self._align_cache = os.environ.get("CVF_ALIGN_CACHE", "1") != "0"
-        self.alignment_fills = 0   # launches of cvf_ef16_align_rows so far (one per resident batch and per re-fill)
+        self.alignment_fills = 0   # launches of cvf_ef16_align_rows_tile so far (one per resident batch and per re-fill)
 
     # ---------------------------------------------------------------- model views
     def get_reordered_eigenfunctions(self, model, cvec):
@@ -946,39 +948,44 @@ class EigenFunctionTask(TrainingTask):
         return self._route.kind == "ef16"
 
     def _alignment_rows(self, ws, X):
-        """The alignment rows (csrc/ef16_front_rows.hip: rotation, centroid and K^-1 of every frame, 84 bytes per frame) of the
-        resident batch ``X``, filled on its first visit, or None: this launch solves for them itself.
+        """``(rows, tile)`` of the resident batch ``X`` - its alignment rows (csrc/ef16_front_rows.hip: rotation, centroid and
+        K^-1 of every frame, 84 bytes per frame) and its feature tile (the aligned positions as the backward launch reads them,
+        ``Tt * d_r * 64`` floats: 264 bytes per frame at d_r = 66) - filled by one launch on its first visit, or None: this step's
+        front launch derives both itself.
 
-        The rows depend on the frames and the layer only, and the training loops replay the same static batches every epoch
+        Both depend on the frames and the layer only, and the training loops replay the same static batches every epoch
         (shuffle=False, core.py:472-481), so every visit after the first starts from them.  An entry is keyed by the batch's
         address and size and HOLDS ``X``: its memory cannot be handed to another tensor while the entry lives, and an in-place
         torch write to ``X`` or its base changes ``X._version`` and re-fills.  A write torch cannot see (a raw kernel, another
         library) is the caller's to announce with :meth:`drop_alignment_cache`.  Entries are never evicted (a captured graph may
-        hold the pointer) and are created only while all of them together stay within the share of the free device memory that
-        RECORD_MEMORY_FRACTION leaves over; nothing is allocated while the stream is capturing."""
+        hold the pointers) and are created - rows and tile together or not at all - only while all of them together stay within
+        the share of the free device memory that RECORD_MEMORY_FRACTION leaves over; nothing is allocated while the stream is
+        capturing."""
         if not self._align_cache:
             return None
         key = (X.data_ptr(), ws.B)
         ent = ws.align_rows.get(key)
         if ent is not None and ent[1] == X._version:
-            return ent[2]
+            return ent[2], ent[3]
         if torch.cuda.is_current_stream_capturing():
             return None
         lib = _hip.lib()
         if ent is None:
-            nbytes = 4 * int(lib.cvf_ef16_align_rows_floats(ws.B))
+            n_rows, n_tile = int(lib.cvf_ef16_align_rows_floats(ws.B)), ws.Tt * self._pp.d_r * _hip.TILE
             free, _ = torch.cuda.mem_get_info(self.device)
-            if self.alignment_rows_bytes + nbytes > (1.0 - self.RECORD_MEMORY_FRACTION) * free:
+            if self.alignment_rows_bytes + self.feature_tile_bytes + 4 * (n_rows + n_tile) > (1.0 - self.RECORD_MEMORY_FRACTION) * free:
                 return None
-            rows = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
+            rows = torch.empty(n_rows, device=self.device, dtype=torch.float32)
+            tile = torch.empty(n_tile, device=self.device, dtype=torch.float32)
         else:
-            rows = ent[2]   # (the same buffer: a captured graph may hold its address)
+            rows, tile = ent[2], ent[3]   # (the same buffers: a captured graph may hold their addresses)
         # (not through _call: its event log holds the launches of a STEP - bench.py's launches_per_step, the launch checks of the
         #  tests; this one happens once per resident batch and is counted in `alignment_fills`)
-        _hip.check(lib.cvf_ef16_align_rows(self._pp, _hip.ptr(X), ws.B, _hip.ptr(rows), _hip.stream()), "cvf_ef16_align_rows")
+        _hip.check(lib.cvf_ef16_align_rows_tile(self._pp, _hip.ptr(X), ws.B, _hip.ptr(rows), _hip.ptr(tile), _hip.stream()),
+                   "cvf_ef16_align_rows_tile")
         self.alignment_fills += 1
-        ws.align_rows[key] = (X, X._version, rows)
-        return rows
+        ws.align_rows[key] = (X, X._version, rows, tile)
+        return rows, tile
 
     @property
     def alignment_rows_bytes(self):
@@ -986,9 +993,16 @@ class EigenFunctionTask(TrainingTask):
         counts the frames themselves)."""
         return sum(e[2].numel() * 4 for ws in self._ws.values() for e in ws.align_rows.values())
 
+    @property
+    def feature_tile_bytes(self):
+        """Device memory the feature tiles of the resident batches take now (``4 * Tt * d_r * 64`` bytes each: 264 bytes per
+        frame at d_r = 66), beside ``alignment_rows_bytes``."""
+        return sum(e[3].numel() * 4 for ws in self._ws.values() for e in ws.align_rows.values())
+
     def drop_alignment_cache(self):
-        """Forget the alignment rows of every resident batch, and the captured graphs that read them.  Call it after writing
-        to a batch's frames by means torch does not see; ``task._ws.clear()`` releases the rows too (with the workspaces)."""
+        """Forget the alignment rows and the feature tile of every resident batch, and the captured graphs that read them.  Call
+        it after writing to a batch's frames by means torch does not see; ``task._ws.clear()`` releases them too (with the
+        workspaces)."""
         self._graphs.clear()
         for ws in self._ws.values():
             ws.align_rows.clear()
@@ -1026,7 +1040,7 @@ class EigenFunctionTask(TrainingTask):
         assert not (aligned and route.kind == "ef16"), \
             "the 16-frame step aligns inside its front launch: there is no prefetched feature buffer to start from (CVF_PIPELINE=1 turns it off)"
         ws = self._workspace(X.shape[0])
-        ws.slot = slot
+        ws.slot, ws.tile = slot, None
         single = not _dist.collectives() or self._local_only   # no cross-rank reduction: the loss tail runs inside the stats launch
         ws.loss_out = ws.loss_vec if out is None else out
         assert ws.loss_out.is_contiguous() and ws.loss_out.dtype == torch.float64 and ws.loss_out.numel() == 3 + 2 * self.k
@@ -1055,11 +1069,13 @@ class EigenFunctionTask(TrainingTask):
         """coordinates -> features, y, hidden activations, q = J A J^T g, E and the batch sums in one launch, 16 frames per wave;
         the units' rows of the sums are left to cvf_ef16_finish[_dp] (batches past cvf_ef16_rows: summed in the front launch)."""
         lib, fl, s, P = _hip.lib(), self._flat, _hip.stream(), _hip.ptr
-        args = (fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X), ws.B, P(self._diag_coeff), P(ws.y), P(ws.saved),
-                P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch), None if ws.unit_rows else P(ws.stats), lv, cf)
         al = self._alignment_rows(ws, X) if cache else None
+        if al is not None:
+            ws.tile = al[1]   # the front launch reads the batch's tile, and so does the backward launch (`ws.feat_in`)
+        args = (fl.desc, P(fl.theta), P(fl.packed), P(ws.feat_in), self._pp, P(X), ws.B, P(self._diag_coeff), P(ws.y), P(ws.saved),
+                P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch), None if ws.unit_rows else P(ws.stats), lv, cf)
         if al is not None:   # (the same name for either form: one call of the step, the same outputs)
-            self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, *args, P(al), s)
+            self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, *args, P(al[0]), s)
         else:
             self._call("cvf_ef16_front", lib.cvf_ef16_front, *args, s)
         if ws.unit_rows:
@@ -1129,7 +1145,7 @@ class EigenFunctionTask(TrainingTask):
         lib, fl, P = _hip.lib(), self._flat, _hip.ptr
         name, packed, lagged, q = self._route.backward
         self._call(name, getattr(lib, name), self._cfg, fl.desc, P(fl.theta), *([P(fl.packed)] if packed else []), ws.B, P(w),
-                   *([P(w_lag)] if lagged else []), P(ws.feat), P(ws.y), *([P(ws.q)] if q else []), P(ws.coef), P(ws.slab),
+                   *([P(w_lag)] if lagged else []), P(ws.feat_in), P(ws.y), *([P(ws.q)] if q else []), P(ws.coef), P(ws.slab),
                    P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
         local = self._local_only or self._grad_local
         # (the general route's gradient exceeds the peer-to-peer window of cvf_slab_reduce_dp: slab reduction + all-reduce)

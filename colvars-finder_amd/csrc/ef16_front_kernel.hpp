@@ -58,9 +58,23 @@ __device__ __forceinline__ void ef16_align_unit(const float* my, const float* re
   if (lane < 3) rsL[lane] = (float)(lane == 0 ? acc[12] : lane == 1 ? acc[13] : acc[14]);
 }
 
-// ROWS: the instance starts from the alignment rows of its batch (`rows`, see kRowsUnit) instead of solving for them - the
-// records are staged beside the coordinates, wave 0's covariance + solve and the barrier behind it are compiled out, and
-// everything from CVF_STAMP(22) on is the code of the solving instance on the same records.  Generator instances only.
+// The position features of atom `at` of a frame staged at `my`: its aligned position, from the rotation and the centroid
+// (hi AND lo part) of the frame's record.  The solving front kernel (into its LDS image and from there into the feature tile) and
+// the kernel that fills a resident batch's tile once (ef16_front_rows.hip) evaluate THIS expression: the same bits.
+__device__ __forceinline__ V3 ef16_feature(const float* my, const int at, const Centre& c, const float* R) {
+  return row_times(centred(my, at, c), R);
+}
+
+// ROWS: the instance starts from what a previous visit of its resident batch left in global memory (cvf_ef16_align_rows_tile)
+// instead of deriving it again - the alignment rows (`rows`, see kRowsUnit) and the feature tile (`feat_tiled`, here an INPUT):
+//   * wave 0's covariance + solve and the barrier behind it, the feature phase and its barrier, and the tile's store at the
+//     end are compiled out;
+//   * layer 0's B operand comes from the tile, so nothing in front of the d chain reads LDS: the head of the pass requests
+//     the staged pieces (records, coordinates, tables, weight) FIRST and the operand and the first layer's fragments behind
+//     them, all before anything is waited for - vector memory returns in issue order, so the LDS stores of the staged
+//     pieces wait for those loads alone - and the block's one barrier for the staged data stands where it is first read
+//     by another wave, in front of CVF_STAMP(26).
+// Everything else is the code of the solving instance on the same records and features.  Generator instances only.
 template <int H, int NH, int NIT, bool ALLAL, bool ROWS = false>
 __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, const float* __restrict__ theta,
                                                              const float* __restrict__ packed, cvf_pp_desc pp,
@@ -124,14 +138,18 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   float a0[SMAX][RT];
   float bias[NH][RT][4];
   const int q_ = lane >> 4;
-  auto request_layer0 = [&]() {
+  auto request_a0 = [&]() {
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
       const int se = s < S ? s : S - 1;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) a0[s][rt] = pk.ld(L.f0() + (se * RT + rt) * 64);   // (k-steps past S are skipped below)
     }
-    load_hid_const_u<H>(urows(theta + mlp.b_off[net][0], H, q_), bias[0]);
+  };
+  auto request_bias0 = [&]() { load_hid_const_u<H>(urows(theta + mlp.b_off[net][0], H, q_), bias[0]); };
+  auto request_layer0 = [&]() {
+    request_a0();
+    request_bias0();
   };
   const bool lagged = x_lag != nullptr && (paired ? pass == 1 : ub >= units_x);   // (wave-uniform)
   const int64_t unit = (lagged && !paired) ? ub - units_x : ub;   // unit within its frame set
@@ -153,17 +171,63 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   const int col = lane & 15, q = lane >> 4;    // matrix-core phases: frame col of the unit, k-slot / row group q
 
   CVF_STAMP(20);
-  // ---- ROWS: the unit's 16 alignment records as a previous visit of this batch left them (84 16-byte pieces) and the sum of the
-  //      reference, requested ahead of everything else of the pass (clamped indices: no branch around a load)
-  float4 row_a, row_b;
-  float rs_in = 0.0f;
+  float bf0[SMAX];   // ROWS: layer 0's B operand
   if constexpr (ROWS) {
-    constexpr int n4 = kRowsUnit / 4;
-    const float4* src = reinterpret_cast<const float4*>(rows + unit * (int64_t)kRowsUnit);
-    row_a = src[tid < n4 ? tid : n4 - 1];
-    row_b = src[tid + nthreads < n4 ? tid + nthreads : n4 - 1];
-    rs_in = rows[units_x * (int64_t)kRowsUnit + (tid < 3 ? tid : 2)];
-  }
+    // ---- ROWS: EVERYTHING the pass reads from global memory in front of its first matrix instruction is requested here, before
+    //      anything is waited for - ONE round trip at the head of the block (the staging loops below, kept for the solving twins,
+    //      wait per iteration: coordinates, second piece, tables, weights = four in a row).  Clamped indices and selected
+    //      addresses, no branch around a load; at this launch's sizes a thread holds at most two 16-byte pieces of the records,
+    //      two of the coordinates and one table entry, larger layers finish in the counted loops behind the stores.
+    //      The staged data first, then layer 0's operand (feature 4 s + q of frame col, from the batch's tile) and the first
+    //      layer's fragments: vector memory returns in issue order, so the LDS stores do not wait for the fragments.
+    constexpr int n4r = kRowsUnit / 4;
+    const float4* rsrc = reinterpret_cast<const float4*>(rows + unit * (int64_t)kRowsUnit);
+    const float4 row_a = rsrc[tid < n4r ? tid : n4r - 1];
+    const float4 row_b = rsrc[tid + nthreads < n4r ? tid + nthreads : n4r - 1];
+    const float rs_in = rows[units_x * (int64_t)kRowsUnit + (tid < 3 ? tid : 2)];
+    // the unit as it lies in memory (see the solving twins' stager below); otherwise the general stager, behind the stores
+    const bool plain = stride == nc && (unit + 1) * kU <= B && (reinterpret_cast<uintptr_t>(x) & 15) == 0;   // (uniform)
+    const int n4 = (kU * nc) >> 2;
+    const float4* xsrc = reinterpret_cast<const float4*>(x + unit * (int64_t)(kU * nc));
+    const float4* xs = plain ? xsrc : rsrc;   // (not plain: any readable piece, dropped)
+    const int nx = plain ? n4 : 1;
+    const float4 cx0 = xs[tid < nx ? tid : nx - 1];
+    const float4 cx1 = xs[tid + nthreads < nx ? tid + nthreads : nx - 1];
+    const int nt = 3 * nal + nc, jt = tid < nt ? tid : nt - 1;   // refL | aL
+    const bool in_a = jt >= 3 * nal && a != nullptr;
+    const float tv_ld = *(in_a ? a + (jt - 3 * nal) : pp.ref_c + (jt < 3 * nal ? jt : 0));
+    const float tv = (jt < 3 * nal || in_a) ? tv_ld : 0.0f;
+    const int64_t frame = unit * kU + (tid < kU ? tid : kU - 1);
+    const float wv_ld = *(w != nullptr ? w + (frame < B ? frame : B - 1) : rows);
+    const float wv = (w != nullptr && frame < B) ? wv_ld : 0.0f;   // frames past the batch replicate the last one with weight 0
+    {
+      const float* ft = feat_tiled + tile * (int64_t)D * CVF_TILE + kU * sub + col;
+#pragma unroll
+      for (int s = 0; s < SMAX; ++s) {
+        const int kf = 4 * (s < S ? s : S - 1) + q;
+        bf0[s] = ft[(kf < D ? kf : D - 1) * CVF_TILE];   // rows past D meet zero weights
+      }
+    }
+    request_a0();
+    // ---- the stores of what was staged (no barrier behind them: this wave's forward and d chains read no LDS but its own
+    //      image - the block's barrier stands in front of CVF_STAMP(26))
+    float4* adst = reinterpret_cast<float4*>(auxL);
+    if (tid < n4r) adst[tid] = row_a;
+    if (tid + nthreads < n4r) adst[tid + nthreads] = row_b;
+    if (tid < 3) rsL[tid] = rs_in;
+    if (plain) {
+      float4* dst = reinterpret_cast<float4*>(xt);
+      if (tid < n4) dst[tid] = cx0;
+      if (tid + nthreads < n4) dst[tid + nthreads] = cx1;
+      for (int v = tid + 2 * nthreads; v < n4; v += nthreads) dst[v] = xsrc[v];
+    } else {
+      load_x_tile<6>(x, B, nc, unit, xt, tid, nthreads, kU);
+    }
+    if (tid < nt) refL[tid] = tv;
+    for (int j = tid + nthreads; j < nt; j += nthreads) refL[j] = j < 3 * nal ? pp.ref_c[j] : (a != nullptr ? a[j - 3 * nal] : 0.0f);
+    if (tid < kU) wL[tid] = wv;
+    request_bias0();   // (behind the stores: its registers and the staged pieces' are not live together)
+  } else {
   // ---- stage the unit's coordinates (16 x nc floats, one contiguous run), the tables and the weights
   if (stride == nc && (unit + 1) * kU <= B && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     // the unit as it lies in memory (3N = 2 mod 4: plain copy, 16 x 3N floats = a whole number of 16-byte pieces; at most two
@@ -186,17 +250,9 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   //      alignment (requested after the alignment, layer 0 began with a wait of ~2 k cycles per wave)
   // (wave 0 asks after its alignment: the solve's fp64 state and these 36 + 8 registers do not fit 128 together, and
   //  a spilled fragment is stored behind a wait for ALL outstanding loads)
-  if constexpr (ROWS) {
-    // (stores of the records requested at the top of the pass: at most two 16-byte pieces per thread, 64 threads or more)
-    float4* dst = reinterpret_cast<float4*>(auxL);
-    if (tid < kRowsUnit / 4) dst[tid] = row_a;
-    if (tid + nthreads < kRowsUnit / 4) dst[tid + nthreads] = row_b;
-    if (tid < 3) rsL[tid] = rs_in;
-    request_layer0();   // (no solve: every wave asks here, and the one barrier below covers coordinates, tables and records)
-  } else {
-    if (wave != 0) request_layer0();   // (every pass: kept across wave 0's solve of the second pass they would spill)
-  }
+  if (wave != 0) request_layer0();   // (every pass: kept across wave 0's solve of the second pass they would spill)
   __syncthreads();
+  }
   const float* my = xt + f * stride;
   CVF_STAMP(21);
 
@@ -211,7 +267,8 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   CVF_STAMP(22);
 
   // ---- aligned positions = features: the block's waves split the atoms (lane p of wave v: atoms p + 4 v + 4 nw i)
-  {
+  //      (ROWS: they are in the batch's tile)
+  if constexpr (!ROWS) {
     float R[9];
     const float* ar = auxL + f * kAuxP;
 #pragma unroll
@@ -225,14 +282,14 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     // (LDS only here: the tiled copy for the backward kernel leaves at the end of the kernel - vector-memory operations
     //  return in issue order, so global stores at this point would sit in front of every weight fragment requested above)
     for (int at = p + 4 * wave; at < N; at += 4 * nw) {
-      const V3 al = row_times(centred(my, at, c), R);
+      const V3 al = ef16_feature(my, at, c, R);
       float* fi = featI + f * kImgP + 3 * at;
       fi[0] = al.x;
       fi[1] = al.y;
       fi[2] = al.z;
     }
+    lds_barrier();
   }
-  lds_barrier();
   CVF_STAMP(23);
 
   // ---- forward chain of this wave's net on the matrix cores: h_l = tanh(W_l h_{l-1} + b_l), 16 frames = the MFMA's N
@@ -250,7 +307,8 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
       const int kf = 4 * (s < S ? s : S - 1) + q;
-      bf[s] = fr[kf < D ? kf : D - 1];   // rows past D meet zero weights
+      if constexpr (ROWS) bf[s] = bf0[s];
+      else bf[s] = fr[kf < D ? kf : D - 1];   // rows past D meet zero weights
     }
     HFrag<H> hf[NH > 1 ? NH - 1 : 1];
 #pragma unroll
@@ -356,6 +414,9 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
 #pragma unroll
       for (int g = 0; g < NG; ++g) sv.st(((NH + l - 1) * NG + g) * 256, ev[l - 1].v[g >> 2][0][g & 3]);
   }
+  // ROWS: the block's barrier for the staged coordinates, records and tables - from here on a wave reads what others staged
+  // (LDS alone: every wave stored what it staged behind its own wait for the loads; the hand-off stores above stay in flight)
+  if constexpr (ROWS) lds_barrier();
   CVF_STAMP(26);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the image is this wave's own: LDS keeps a wave's accesses in order
 
@@ -536,7 +597,8 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   }
   CVF_STAMP(34);
   // ---- the feature tile for the backward kernel (the first layer's weight-gradient operand), from the LDS image
-  {
+  //      (ROWS: the batch's tile is already what the backward kernel reads)
+  if constexpr (!ROWS) {
     float* ft = feat_tiled + tile * (int64_t)D * CVF_TILE + kU * sub + f;
     const float* fi = featI + f * kImgP;
     // (a plain counted loop: left to itself the compiler unrolls and vectorises this run-time trip count into ~200 vector

@@ -295,10 +295,17 @@ int cvf_ef16_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const floa
  * static batches of core.py:472-481 - computes them once:
  *  cvf_ef16_align_rows : x [B][n_coord] -> rows (cvf_ef16_align_rows_floats(B) floats, 16-byte aligned; opaque: per unit of 16
  *                        frames the 16 x 21 floats the front kernel keeps on the chip, then the sum of the centred reference).
- *  cvf_ef16_front_rows : cvf_ef16_front (same arguments, same outputs BIT FOR BIT) starting from `rows` instead of solving.
- *                        The caller answers for `rows` being those of exactly these B frames of `x` under this `pp`. */
+ *  cvf_ef16_align_rows_tile : the same launch also leaves the batch's FEATURE TILE - feat_tiled [T][d_r][64], T = cvf_ntiles(B), the
+ *                        aligned positions exactly as cvf_ef16_front writes them (every unit of 4 T, frames past B as replicas of
+ *                        the last one) - which depends on the coordinates and the layer only as well.
+ *  cvf_ef16_front_rows : cvf_ef16_front (same arguments, same outputs BIT FOR BIT) starting from `rows` and the tile instead of
+ *                        solving.  In this form `feat_tiled` is READ, NOT WRITTEN (layer 0's operand comes from it): it must be
+ *                        the tile cvf_ef16_align_rows_tile left for the same `x`, and it is the `feat_tiled` cvf_ef16_backward
+ *                        takes afterwards.  The caller answers for `rows` and the tile being those of exactly these B frames of
+ *                        `x` under this `pp`. */
 int64_t cvf_ef16_align_rows_floats(int64_t B);
 int cvf_ef16_align_rows(const cvf_pp_desc* pp, const float* x, int64_t B, float* rows, void* stream);
+int cvf_ef16_align_rows_tile(const cvf_pp_desc* pp, const float* x, int64_t B, float* rows, float* feat_tiled, void* stream);
 int cvf_ef16_front_rows(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled, const cvf_pp_desc* pp,
                         const float* x, int64_t B, const float* a, float* y_tiled, float* saved, float* q_tiled, float* e_tiled,
                         const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats, double* loss_vec, double* coef,

@@ -1,14 +1,17 @@
 // Developer tool (not part of the library): the 16-frames-per-wave generator step (ef16_front.hip + ef16_back.hip: the front kernel and the four-wave
 // backward kernel of ef_mfma.hip) at the config-3 shape - kernel times with HIP events at several batch sizes and, with
-// -DCVF_STAMPS, s_memtime phase stamps per wave.
+// -DCVF_STAMPS, s_memtime phase stamps per wave.  `ef16_probe rows`: the stamped front launch is the one that starts from the
+// batch's alignment rows and feature tile (cvf_ef16_front_rows; -DCVF_DEV_SHAPES compiles the config-3 instances only).
 // Build + run on the GPU box:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DCVF_STAMPS -DCVF_STAMP_WPB=4 -Iinclude -Icolvars-finder_amd/csrc -Wno-pass-failed \
 //       tools/ef16_probe.hip -Lcolvars-finder_amd/colvarsfinder -lcvf_hip -Wl,-rpath,\$ORIGIN/../../colvars-finder_amd/colvarsfinder -o tools/build/ef16_probe
 #include "../colvars-finder_amd/csrc/ef16_front.hip"
+#include "../colvars-finder_amd/csrc/ef16_front_rows.hip"
 #include "../colvars-finder_amd/csrc/ef16_back.hip"
 // (everything else - cvf_ef_pack, the batch sums - comes from the library the probe is linked against)
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -99,6 +102,9 @@ int main(int argc, char** argv) {
   cfg.k = k; cfg.lag_idx = 0; cfg.sort_eigvals = 1; cfg.alpha = 20.0; cfg.beta = 1.0; cfg.dt = 1.0;
   cfg.eig_w[0] = 1.0; cfg.eig_w[1] = 0.75; cfg.eig_w[2] = 0.5;
   if (!cvf_ef16_supported(&m, &pp)) { printf("shape not supported\n"); return 1; }
+  const bool from_rows = argc > 1 && std::strcmp(argv[1], "rows") == 0;
+  float* drows;
+  CK(hipMalloc(&drows, cvf_ef16_align_rows_floats(Bmax) * 4));
   hipEvent_t e0, e1, e2;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); CK(hipEventCreate(&e2));
   const int batches[] = {2500, 5000, 20000, 40000, 160000};
@@ -106,8 +112,10 @@ int main(int argc, char** argv) {
     const int reps = 30;
     float tf = 0, tb = 0;
     for (int it = 0; it < reps + 5; ++it) {
+      if (from_rows && it == 0 && cvf_ef16_align_rows_tile(&pp, dx, B, drows, dfeat, nullptr)) { printf("fill failed: %s\n", cvf_last_error()); return 1; }
       CK(hipEventRecord(e0));
-      int rc = cvf_ef16_front(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, nullptr);
+      int rc = from_rows ? cvf_ef16_front_rows(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, drows, nullptr)
+                         : cvf_ef16_front(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, nullptr);
       if (rc) { printf("front failed: %s\n", cvf_last_error()); return 1; }
       CK(hipEventRecord(e1));
       rc = cvf_ef16_backward(&cfg, &m, dth, dpk, B, dw, dfeat, dy, dq, dcoef, dslab, nullptr, dsaved, nullptr);
@@ -126,7 +134,14 @@ int main(int argc, char** argv) {
   for (int B : {20000, 2500}) {
     std::vector<unsigned long long> st(64 * 4096, 0);
     CK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st.data(), st.size() * 8));
-    cvf_ef16_front(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, nullptr);
+    if (from_rows) {   // (the fill stamps too - it runs ef16_align_unit: cleared before the launch that is read)
+      if (cvf_ef16_align_rows_tile(&pp, dx, B, drows, dfeat, nullptr)) { printf("fill failed: %s\n", cvf_last_error()); return 1; }
+      CK(hipDeviceSynchronize());
+      CK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st.data(), st.size() * 8));
+      cvf_ef16_front_rows(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, drows, nullptr);
+    } else {
+      cvf_ef16_front(&m, dth, dpk, dfeat, &pp, dx, B, da, dy, dsaved, dq, de, &cfg, dw, dscr, dstats, dlv, dcoef, nullptr);
+    }
     CK(hipDeviceSynchronize());
     CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamps), st.size() * 8));
     {
