@@ -25,7 +25,8 @@ def ef_widths(n_hidden):
 
 
 FEAT_ANGLE, FEAT_BOND, FEAT_DIHEDRAL, FEAT_POSITION = 0, 1, 2, 3
-PP_IDENTITY, PP_ALIGN, PP_FACTORED = 0, 1, 2
+PP_IDENTITY, PP_ALIGN, PP_FACTORED, PP_FEATURES = 0, 1, 2, 3
+FEATURES_MAX_SLOT, FEATURES_MAX_REF = 4096, 6144   # CVF_PP_FEATURES limits (include/cvf.h, csrc/k1_features.hip)
 PP_ALIGN_CONTIG, PP_PURE_POSITION, PP_SLOT_BATCHED = 1, 2, 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -856,6 +856,11 @@ class EigenFunctionTask(TrainingTask):
             self._dense = torch.zeros(_hip.lib().cvf_metric_dense_doubles(self._pp), device=self.device, dtype=torch.float64)
             _hip.check(_hip.lib().cvf_metric_dense_tensors(self._pp, _hip.ptr(self._diag_coeff), _hip.ptr(self._dense),
                                                            _hip.stream()), "cvf_metric_dense_tensors")
+        if self.lag_idx == 0 and self._pp.mode == _hip.PP_FEATURES:   # a layer without alignment: the limits of csrc/k1_features.hip
+            why = self.preprocessing_layer.derivative_table_limits()
+            if why is not None:
+                raise NotImplementedError(f"EigenFunctionTask (generator mode) on MI355X: the feature list has {why} "
+                                          "(csrc/k1_features.hip). Use lag_tau > 0 (no derivative through the features) or fewer features.")
         self._ws = {}
         self._graphs = {}
         # whole-step hipGraph replay (CVF_GRAPH=0 turns it off).  In a data-parallel job the two RCCL all-reduces are
@@ -1953,6 +1958,10 @@ class RegAutoEncoderTask(TrainingTask):
         self._weights = torch.as_tensor(np.asarray(traj_obj.weights)).to(device=self.device, dtype=torch.float32).contiguous()
         # pp_layer may be any torch module (core.py:65,122,635): its feature trajectory is computed once with torch
         self._foreign_pp = not isinstance(self.preprocessing_layer, (torch.nn.Identity, AlignFeatureLayer))
+        if self.eta[0] > self._eps and not getattr(self.preprocessing_layer, "aligned", True):
+            raise NotImplementedError("RegAutoEncoderTask on MI355X: the gradient-norm penalty eta[0] is not built for a feature layer "
+                                      "without alignment (PreprocessingANN(None, feature_layer), CVF_PP_FEATURES): its reshape "
+                                      "(core.py:907) wants the aligned coordinates as features")
         if self._foreign_pp:
             if _dist.world() > 1:
                 raise NotImplementedError("RegAutoEncoderTask with a preprocessing module other than Identity / AlignFeatureLayer "

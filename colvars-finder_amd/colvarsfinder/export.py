@@ -27,6 +27,8 @@ class ScriptableAlignFeature(torch.nn.Module):
         rec = layer.rec.detach().cpu().to(torch.long)
         self.d_r: int = int(layer.d_r)
         self.use_angle_value: bool = bool(layer.use_angle_value)
+        # a layer without alignment (pp.PreprocessingANN(None, ...)): position records are the raw coordinates
+        self.aligned: bool = bool(getattr(layer, "aligned", True))
         self.register_buffer("align_idx", layer.align_idx.detach().cpu().to(torch.long))
         self.register_buffer("ref_c", layer.ref_c.detach().cpu().clone())
         # per-atom alignment weights (mean 1; ref_c is already multiplied by them, pp.AlignFeatureLayer); ones = uniform
@@ -53,7 +55,9 @@ class ScriptableAlignFeature(torch.nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         ref = self.ref_c.to(x.dtype)
         out = torch.zeros(x.shape[0], self.d_r, dtype=x.dtype, device=x.device)
-        if self.pos_atoms.numel() > 0:
+        if self.pos_atoms.numel() > 0 and not self.aligned:
+            out[:, self.pos_out] = x[:, self.pos_atoms, :].reshape(x.shape[0], -1)
+        if self.pos_atoms.numel() > 0 and self.aligned:
             xa = x[:, self.align_idx, :]
             c = (self.align_w.to(x.dtype)[None, :, None] * xa).mean(dim=1, keepdim=True)
             h = torch.matmul((xa - c).transpose(1, 2), ref)

@@ -70,7 +70,9 @@ class AlignFeatureLayer(torch.nn.Module):
 
     Args:
         n_atoms: number of input atoms N; ``forward`` takes ``[B, N, 3]``.
-        align_idx: local indices of the atoms used for the alignment.
+        align_idx: local indices of the atoms used for the alignment, or ``None``: no alignment - the features are those of
+            the raw coordinates (molann's ``PreprocessingANN(None, feature_layer)``; ``CVF_PP_FEATURES``, csrc/k1_features.hip),
+            a ``position`` feature returns ``x[:, atoms]`` unchanged.  ``ref_pos`` and ``align_weights`` must then be ``None``.
         ref_pos: ``[n_align, 3]`` reference positions of those atoms (stored centred).
         features: list of ``(type_name, local_atom_indices)``.
         use_angle_value: emit angles in radians instead of cos / (cos, sin).
@@ -82,11 +84,17 @@ class AlignFeatureLayer(torch.nn.Module):
 
     def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None):
         super().__init__()
+        self.aligned = align_idx is not None
+        if not self.aligned:
+            assert ref_pos is None, "ref_pos without align_idx: a layer without alignment has no reference structure"
+            assert align_weights is None, "align_weights without align_idx: a layer without alignment has no alignment weights"
+            align_idx, ref_pos = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
         align_idx = np.asarray(align_idx, dtype=np.int64)
         ref = np.asarray(ref_pos, dtype=np.float64)
         assert ref.shape == (len(align_idx), 3), f"ref_pos must be [{len(align_idx)},3], got {ref.shape}"
-        assert len(align_idx) >= 3, "at least 3 atoms are needed for the alignment"
-        assert align_idx.min() >= 0 and align_idx.max() < n_atoms, "align index out of range"
+        if self.aligned:
+            assert len(align_idx) >= 3, "at least 3 atoms are needed for the alignment"
+            assert align_idx.min() >= 0 and align_idx.max() < n_atoms, "align index out of range"
         rec, out = [], 0
         for tname, atoms in features:
             atoms = [int(a) for a in atoms]
@@ -103,9 +111,9 @@ class AlignFeatureLayer(torch.nn.Module):
         self.features = [(t, tuple(int(a) for a in atoms)) for t, atoms in features]
         # structure hints for the kernels (include/cvf.h): affine tables allow the fast kernels
         flags = 0
-        if np.array_equal(align_idx, np.arange(len(align_idx))):
+        if self.aligned and np.array_equal(align_idx, np.arange(len(align_idx))):
             flags |= _hip.PP_ALIGN_CONTIG
-        if all(r[0] == _hip.FEAT_POSITION and r[1] == i and r[5] == 3 * i for i, r in enumerate(rec)):
+        if self.aligned and all(r[0] == _hip.FEAT_POSITION and r[1] == i and r[5] == 3 * i for i, r in enumerate(rec)):
             flags |= _hip.PP_PURE_POSITION
         # per-atom weights: the kernels take them with mean 1, and the reference positions centred by their WEIGHTED
         # centroid and pre-multiplied by them (include/cvf.h, cvf_pp_desc.align_w) - the covariance
@@ -137,7 +145,7 @@ class AlignFeatureLayer(torch.nn.Module):
         # free; type -1 entries are padding)
         by_type = sorted(rec_slot, key=lambda r: r[0])
         rec_slot = _batch_records(by_type)
-        if w_hat is None:
+        if w_hat is None and self.aligned:
             self._flags |= _hip.PP_SLOT_BATCHED
         self._n_rec_slot = len(rec_slot)
         self._n_slot = len(used)
@@ -169,7 +177,9 @@ class AlignFeatureLayer(torch.nn.Module):
         self.register_buffer("rec_slot", torch.tensor(rec_slot, dtype=torch.int32).reshape(-1, 6))
         self.register_buffer("slot_atom", torch.tensor(used, dtype=torch.int32))
         self.register_buffer("align_idx", torch.tensor(align_idx, dtype=torch.int32))
-        if w_hat is None:
+        if not self.aligned:
+            ref_c, self.align_w = ref, None
+        elif w_hat is None:
             ref_c = ref - ref.mean(axis=0, keepdims=True)
             self.align_w = None
         else:
@@ -182,6 +192,14 @@ class AlignFeatureLayer(torch.nn.Module):
         """None, or why the large-molecule derivative kernel (csrc/metric_large.hip: metric_rows_kernel) cannot take this feature
         list: its tables pack a record's slots and rows into 16-bit fields, a record's position among its atom's rows into 8 bits
         and a slot's row count into 12 bits.  EigenFunctionTask's generator mode asks at construction."""
+        if not self.aligned:   # features of the raw coordinates (csrc/k1_features.hip): the limits of include/cvf.h
+            for what, have, limit in (("distinct feature atoms (n_slot)", self._n_slot, _hip.FEATURES_MAX_SLOT),
+                                      ("contribution rows (n_ref: atoms summed over the features)", self._n_ref, _hip.FEATURES_MAX_REF)):
+                if have > limit:
+                    return f"{have} {what}; the kernels of a layer without alignment take at most {limit}"
+            if getattr(self, "_row_off_max", 0) >= 256:
+                return f"{self._row_off_max + 1} features that share one atom; the derivative kernel's tables hold fewer than 256"
+            return None
         rows_per_slot = int(np.diff(np.concatenate([[0], self.slot_row.cpu().numpy()])).max()) if self.slot_row.numel() else 0
         for what, have, limit in (("contribution rows (atoms summed over the features)", self._n_ref, 65536),
                                   ("distinct feature atoms", self._n_slot, 65536),
@@ -194,12 +212,13 @@ class AlignFeatureLayer(torch.nn.Module):
     def pp_desc(self):
         assert self.rec.is_cuda, "preprocessing layer is not on the GPU (call .to(device))"
         d = _hip.PPDesc()
-        d.mode, d.n_coord, d.n_align, d.n_rec = _hip.PP_ALIGN, 3 * self.n_atoms, self.align_idx.numel(), self.rec.shape[0]
+        d.mode, d.n_coord, d.n_align, d.n_rec = _hip.PP_ALIGN if self.aligned else _hip.PP_FEATURES, 3 * self.n_atoms, self.align_idx.numel(), self.rec.shape[0]
         d.d_r, d.use_angle_value = self.d_r, int(self.use_angle_value)
         d.has_position = int(bool((self.rec[:, 0] == _hip.FEAT_POSITION).any().item()))
         d.flags = self._flags
-        d.align_idx, d.ref_c, d.rec = self.align_idx.data_ptr(), self.ref_c.data_ptr(), self.rec.data_ptr()
-        d.atom_align, d.atom_slot, d.rec_slot = self.atom_align.data_ptr(), self.atom_slot.data_ptr(), self.rec_slot.data_ptr()
+        d.rec, d.atom_slot, d.rec_slot = self.rec.data_ptr(), self.atom_slot.data_ptr(), self.rec_slot.data_ptr()
+        if self.aligned:
+            d.align_idx, d.ref_c, d.atom_align = self.align_idx.data_ptr(), self.ref_c.data_ptr(), self.atom_align.data_ptr()
         d.slot_atom, d.n_slot, d.n_rec_slot = self.slot_atom.data_ptr(), self._n_slot, self._n_rec_slot
         d.align_w = self.align_w.data_ptr() if self.align_w is not None else None
         if self._n_ref < 65536 and self._n_slot < 65536 and getattr(self, "_row_off_max", 0) < 256:   # (else: cvf_metric_apply names what is missing)
@@ -331,6 +350,9 @@ class PreprocessingANN(AlignFeatureLayer):
     """``PreprocessingANN(align_layer, feature_layer)`` (main.ipynb:348) -> one fused GPU layer."""
 
     def __init__(self, align_layer, feature_layer):
+        if align_layer is None:   # molann: no alignment, the features of the raw coordinates
+            AlignFeatureLayer.__init__(self, len(feature_layer.input_ix), None, None, feature_layer.local, feature_layer.use_angle_value)
+            return
         assert np.array_equal(align_layer.input_ix, feature_layer.input_ix), "align and feature layers use different input atoms"
         super().__init__(len(align_layer.input_ix), align_layer.local_idx, align_layer.ref_c, feature_layer.local,
                          feature_layer.use_angle_value, align_weights=getattr(align_layer, "weights", None))

@@ -1,6 +1,6 @@
 // The feature map of the alignment layer and its chain rule, written once for every kernel that evaluates it:
-// values (k1_align.hip, k1_large.hip), J^T g (k1_align.hip, k1_vjp.hip, metric_large.hip) and J u (k1_align.hip,
-// metric_large.hip).  What differs between the kernels comes in as callables: where atom k of a record is read from (an LDS
+// values (k1_align.hip, k1_large.hip, k1_features.hip), J^T g (k1_align.hip, k1_vjp.hip, metric_large.hip, k1_features.hip) and
+// J u (k1_align.hip, metric_large.hip, k1_features.hip).  What differs between the kernels comes in as callables: where atom k of a record is read from (an LDS
 // tile, HBM, a captured slot), where the upstream value of output out + j is read from, and where a value or an atom's
 // gradient row goes.  Everything is __forceinline__: each kernel keeps its own layout, registers and arithmetic.
 #pragma once
@@ -58,9 +58,44 @@ struct DihedralG {
   V3 g1, g2, g3, g4;  // gradient of phi
   float p, q;         // g2 = (-1 - p) g1 + q g4,  g3 = p g1 + (-1 - q) g4
 };
+// The two normals n1 = b1 x b2, n2 = b2 x b3 are where a dihedral loses digits in fp32: when two bonds are close to parallel
+// (kappa = |b||b'| / |b x b'| large) the rounding of the differences b = x' - x and of the products of the cross product is
+// amplified kappa times, in the values and - divided by |n|^2 - in the gradient.  EXACT evaluates the normals as if the
+// differences and the products were exact: the rounding error of every difference is recovered (two_diff), every component
+// a b - c d is taken with the fma error-free product (Kahan), and the first-order terms e x b' + b x e' are added.  Everything
+// downstream of the normals is as before (no amplification there).  Off by default: the kernels that predate it keep their bits.
+__device__ __forceinline__ float two_diff(float a, float b, float& err) {   // a - b = s + err exactly
+  const float s = a - b;
+  const float bb = s - a;
+  err = (a - (s - bb)) - (b + bb);
+  return s;
+}
+__device__ __forceinline__ V3 two_diff(V3 a, V3 b, V3& err) {
+  return V3{two_diff(a.x, b.x, err.x), two_diff(a.y, b.y, err.y), two_diff(a.z, b.z, err.z)};
+}
+__device__ __forceinline__ float diff_of_products(float a, float b, float c, float d) {   // a b - c d, one rounding of the result
+  const float w = c * d;
+  const float e = fmaf(-c, d, w);
+  const float f = fmaf(a, b, -w);
+  return f + e;
+}
+__device__ __forceinline__ V3 cross_exact(V3 a, V3 b) {
+  return V3{diff_of_products(a.y, b.z, a.z, b.y), diff_of_products(a.z, b.x, a.x, b.z), diff_of_products(a.x, b.y, a.y, b.x)};
+}
+template <bool EXACT = false>
 __device__ __forceinline__ DihedralG dihedral_eval(V3 x1, V3 x2, V3 x3, V3 x4) {
-  V3 b1 = x2 - x1, b2 = x3 - x2, b3 = x4 - x3;
-  V3 n1 = cross(b1, b2), n2 = cross(b2, b3);
+  V3 b1, b2, b3, n1, n2;
+  if constexpr (EXACT) {
+    V3 e1, e2, e3;
+    b1 = two_diff(x2, x1, e1);
+    b2 = two_diff(x3, x2, e2);
+    b3 = two_diff(x4, x3, e3);
+    n1 = cross_exact(b1, b2) + (cross(e1, b2) + cross(b1, e2));
+    n2 = cross_exact(b2, b3) + (cross(e2, b3) + cross(b2, e3));
+  } else {
+    b1 = x2 - x1, b2 = x3 - x2, b3 = x4 - x3;
+    n1 = cross(b1, b2), n2 = cross(b2, b3);
+  }
   float n1sq = dot(n1, n1), n2sq = dot(n2, n2), b2sq = dot(b2, b2);
   float l2 = sqrtf(b2sq);
   float inv = 1.0f / sqrtf(n1sq * n2sq);
@@ -102,7 +137,7 @@ __device__ __forceinline__ void dihedral_tangent(bool angle_value, float cs, flo
 // and at(k) returns its atom k (k < 4).
 
 // Values of a bond, angle or dihedral record: emit(j, v) writes output out + j.
-template <class At, class Emit>
+template <bool EXACT = false, class At, class Emit>
 __device__ __forceinline__ void invariant_values(int type, bool angle_value, At at, Emit emit) {
   if (type == CVF_FEAT_BOND) {
     emit(0, bond_eval(at(0), at(1)).val);
@@ -110,7 +145,7 @@ __device__ __forceinline__ void invariant_values(int type, bool angle_value, At 
     const float cs = angle_eval(at(0), at(1), at(2)).cs;
     emit(0, angle_value ? acosf(cs) : cs);
   } else {
-    const DihedralG dg = dihedral_eval(at(0), at(1), at(2), at(3));
+    const DihedralG dg = dihedral_eval<EXACT>(at(0), at(1), at(2), at(3));
     if (angle_value) {
       emit(0, atan2f(dg.sn, dg.cs));
     } else {
@@ -122,7 +157,7 @@ __device__ __forceinline__ void invariant_values(int type, bool angle_value, At 
 
 // J^T g of a bond, angle or dihedral record for n upstream rows that share the record's geometry: g(i, j) is row i's
 // upstream value of output out + j, add(i, k, v) adds v to the gradient of atom k in row i.
-template <class At, class G, class Add>
+template <bool EXACT = false, class At, class G, class Add>
 __device__ __forceinline__ void invariant_vjp(int type, bool angle_value, int n, At at, G g, Add add) {
   if (type == CVF_FEAT_BOND) {
     const BondG e = bond_eval(at(0), at(1));
@@ -141,7 +176,7 @@ __device__ __forceinline__ void invariant_vjp(int type, bool angle_value, int n,
       add(i, 2, gs * e.gc);
     }
   } else {
-    const DihedralG e = dihedral_eval(at(0), at(1), at(2), at(3));
+    const DihedralG e = dihedral_eval<EXACT>(at(0), at(1), at(2), at(3));
     for (int i = 0; i < n; ++i) {
       const float gs = dihedral_adjoint(angle_value, e.cs, e.sn, [&](int j) { return g(i, j); });
       add(i, 0, gs * e.g1);
@@ -153,7 +188,7 @@ __device__ __forceinline__ void invariant_vjp(int type, bool angle_value, int n,
 }
 
 // J u of a bond, angle or dihedral record: u(k) is the tangent of atom k, put(j, v) writes output out + j.
-template <class At, class U, class Put>
+template <bool EXACT = false, class At, class U, class Put>
 __device__ __forceinline__ void invariant_jvp(int type, bool angle_value, At at, U u, Put put) {
   if (type == CVF_FEAT_BOND) {
     const BondG e = bond_eval(at(0), at(1));
@@ -164,7 +199,7 @@ __device__ __forceinline__ void invariant_jvp(int type, bool angle_value, At at,
     if (angle_value) dv = -dv / acos_den(e.cs);
     put(0, dv);
   } else {
-    const DihedralG e = dihedral_eval(at(0), at(1), at(2), at(3));
+    const DihedralG e = dihedral_eval<EXACT>(at(0), at(1), at(2), at(3));
     const float dphi = dot(e.g1, u(0)) + dot(e.g2, u(1)) + dot(e.g3, u(2)) + dot(e.g4, u(3));
     dihedral_tangent(angle_value, e.cs, e.sn, dphi, put);
   }

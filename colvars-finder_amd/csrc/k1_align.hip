@@ -652,6 +652,9 @@ int cvf_k1_large_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float*
 int cvf_factor_feature_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows, hipStream_t s);
 int cvf_metric_factor_launch(const cvf_pp_desc* pp, const float* x, int64_t B, int k, const float* g_tiled, float* q_tiled,
                              float* e_tiled, hipStream_t s);
+int cvf_features_fwd_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows, hipStream_t s);
+int cvf_features_metric_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, int k, const float* g_tiled,
+                               float* q_tiled, float* e_tiled, hipStream_t s);
 size_t cvf_k1_large_scratch_bytes(const cvf_pp_desc* pp, int64_t B);
 size_t cvf_metric_large_lds(const cvf_pp_desc* pp);
 int cvf_ef_stats_finish(const cvf_ef_cfg* cfg, int n_rows, const double* partial, double* stats, double* loss_vec, double* coef,
@@ -684,6 +687,7 @@ extern "C" int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int6
     return cvf_check_launch("k1_identity_kernel");
   }
   if (pp->mode == CVF_PP_FACTORED) return cvf_factor_feature_launch(pp, x, B, feat_tiled, feat_rows, s);   // (csrc/metric_factor.hip)
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_fwd_launch(pp, x, B, feat_tiled, feat_rows, s);     // (csrc/k1_features.hip)
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
               "cvf_align_feature_fwd: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
@@ -785,6 +789,8 @@ static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, c
   }
   if (pp->mode == CVF_PP_FACTORED)   // t = L^T g, q = L t, E = |t|^2 from the records (csrc/metric_factor.hip); stats: two-stage path
     return cvf_metric_factor_launch(pp, x, B, k, g_tiled, q_tiled, e_tiled, s);
+  if (pp->mode == CVF_PP_FEATURES)   // features of the raw coordinates (csrc/k1_features.hip); stats: two-stage path
+    return cvf_features_metric_launch(pp, x, B, a, k, g_tiled, q_tiled, e_tiled, s);
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(aux_tiled, "cvf_metric_apply: align mode needs aux");
   CVF_REQUIRE(!pp->align_w || (pp->flags == 0 && pp->n_coord <= kLanePerFrameMaxCoord),

@@ -15,6 +15,8 @@
 #include "cvf_features.hpp"
 #include "cvf_metric.hpp"
 
+int cvf_features_vjp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, int k, const float* g_rows, float* gx_rows, hipStream_t s);
+
 namespace {
 
 constexpr int kLanePerFrameMaxCoord = 192;   // as cvf_align_feature_fwd (k1_align.hip): aux rows are the same on both paths
@@ -247,6 +249,7 @@ extern "C" int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int6
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_vjp: identity copy: %s", hipGetErrorString(e));
     return 0;
   }
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_vjp_launch(pp, x, B, 1, g_rows, gx_rows, s);   // (csrc/k1_features.hip)
   CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
               "cvf_align_feature_vjp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
@@ -641,6 +644,7 @@ extern "C" int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x,
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_vjp_rows: identity copy: %s", hipGetErrorString(e));
     return 0;
   }
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_vjp_launch(pp, x, B, k, g_rows, gx_rows, s);   // (csrc/k1_features.hip)
   CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
               "cvf_align_feature_vjp_rows: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own "
               "autograd");

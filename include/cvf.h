@@ -41,7 +41,18 @@ enum { CVF_FEAT_ANGLE = 0, CVF_FEAT_BOND = 1, CVF_FEAT_DIHEDRAL = 2, CVF_FEAT_PO
  * cvf_align_feature_fwd copies r(x) out of the records; cvf_metric_apply[_stats] computes t = L^T g, q = L t, E = |t|^2 from them
  * (csrc/metric_factor.hip; `a` and `aux_tiled` are ignored: diag_coeff is folded into L).  The fused and 16-frame launches
  * (cvf_ef16_*, cvf_ef_[align_]fwd_metric_*, cvf_ef_align_fwd) take coordinates and refuse this mode; their predicates answer 0. */
-enum { CVF_PP_IDENTITY = 0, CVF_PP_ALIGN = 1, CVF_PP_FACTORED = 2 };
+enum { CVF_PP_IDENTITY = 0, CVF_PP_ALIGN = 1, CVF_PP_FACTORED = 2, CVF_PP_FEATURES = 3 };
+/* CVF_PP_FEATURES: the features of the RAW coordinates - molann's PreprocessingANN(None, feature_layer): no centroid, no rotation; a
+ * position record copies x[atom] bit for bit (csrc/k1_features.hip).  The descriptor carries n_coord = 3 N, n_rec, rec, d_r,
+ * use_angle_value, has_position, the slot tables (atom_slot, slot_atom, rec_slot, n_slot, n_rec_slot) and, for the derivative entry
+ * points, mrec / slot_row / n_mrec / n_ref; n_align = 0 and align_idx, ref_c, align_w, atom_align, flags are not read.  aux_tiled,
+ * scratch, slot_xyz and dense are ignored wherever they are arguments (NULL is fine) and cvf_align_feature_scratch_bytes answers 0.
+ * Taken by cvf_align_feature_fwd, cvf_align_feature_vjp[_rows] and cvf_metric_apply[_stats] (the batch sums by cvf_ef_stats'
+ * two-stage tail); the fused and 16-frame launches refuse the mode and their predicates answer 0.  One design serves every atom
+ * count - only the feature atoms of a frame are read (12 bytes each), never the frame - so what bounds a launch is the feature list:
+ * beyond the two limits below the entry points return a negative code whose message names the limit, before any launch. */
+#define CVF_FEATURES_MAX_SLOT 4096 /* n_slot: distinct atoms the features read */
+#define CVF_FEATURES_MAX_REF 6144  /* n_ref: (record, atom) pairs = contribution rows of the derivative kernels (vjp, metric) */
 /* cvf_mlp_desc.act[l]: what follows Linear layer l (nn.py:29-59 takes any torch activation module).  The chain kernels
  * (cvf_ae_*, cvf_regae_*, cvf_mlp_eval_rows) and the eigenfunction kernels on 64-frame tiles (cvf_ef_*: they use the
  * activation's first TWO derivatives, expressed through its output) take all of these, one code for every hidden layer of a
@@ -176,7 +187,8 @@ int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int64_t B, floa
  * g_rows [B][d_r]; gx_rows [B][n_coord], fully written (0 for atoms no feature reads and the alignment does not use).
  *   CVF_PP_ALIGN: every descriptor cvf_align_feature_fwd takes (any flags, partial alignment sets, all feature types, both
  *     use_angle_value modes, align_w); frames of more than 192 coordinates also need the slot tables and mrec / slot_row, with
- *     n_ref * 12 bytes within the LDS.  CVF_PP_IDENTITY: a copy.  CVF_PP_FACTORED: refused (the records come from a torch
+ *     n_ref * 12 bytes within the LDS.  CVF_PP_FEATURES: aux_tiled is ignored (may be NULL); gx_rows is 0 on every atom no feature
+ *     reads; n_slot <= CVF_FEATURES_MAX_SLOT, n_ref <= CVF_FEATURES_MAX_REF.  CVF_PP_IDENTITY: a copy.  CVF_PP_FACTORED: refused (the records come from a torch
  *     module, which has its own autograd).
  * No atomics: two calls on the same inputs give the same bits. */
 int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
