@@ -164,6 +164,10 @@ _SIGNATURES = {
     "cvf_ae_step": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamArgs), C.c_void_p]),
     "cvf_ae_step_route": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "cvf_ae_general_supported": (C.c_int, [C.POINTER(MLPDesc)]),
+    "cvf_ae_general_scratch_floats": (C.c_int64, [C.POINTER(MLPDesc), C.c_int64]),
+    "cvf_ae_general_step": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamArgs), C.c_void_p]),
     "cvf_regae_scratch_floats": (C.c_int64, [C.POINTER(MLPDesc), C.c_int64]),
     "cvf_regae_forward": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

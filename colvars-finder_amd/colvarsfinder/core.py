@@ -1385,7 +1385,9 @@ class AutoEncoderTask(TrainingTask):
     """Autoencoder trained with the weighted reconstruction loss (arguments as core.py:610-625).
 
     The feature trajectory ``r(x)`` is computed once for all frames (core.py:635) by kernel K1 and
-    stays in HBM; each step is one fused kernel (forward, weighted MSE, parameter gradient) + Adam.
+    stays in HBM; each step is one fused kernel (forward, weighted MSE, parameter gradient) + Adam.  Chains whose parameters
+    and activations do not fit that kernel's 160 KiB of LDS train layer by layer instead (cvf_ae_general_step: any widths up
+    to 4096 units, the same outputs); a chain past both routes is refused with NotImplementedError at construction.
     """
 
     def __init__(self, traj_obj, pp_layer, model, model_path, learning_rate=0.01, load_model_filename=None,
@@ -1421,6 +1423,20 @@ class AutoEncoderTask(TrainingTask):
             print('\nShape of trajectory data array:\n {}'.format((self._n_frames, pp.d_r)), flush=True)
         self._out2 = torch.zeros(3, device=self.device, dtype=torch.float64)
         self._scratch = {}
+        # with_grad -> the step goes per layer (cvf_ae_general_step): decided once, where cvf_ae_step_route refuses the chain
+        self._general = {wg: self._needs_general(wg) for wg in (False, True)}
+
+    def _needs_general(self, with_grad):
+        """False where cvf_ae_step takes the chain (its kernels keep the chain of a 64-frame tile in LDS), True where only the
+        per-layer route of csrc/ae_general.hip does; a chain past both is refused here, at construction."""
+        lib, fl = _hip.lib(), self._flat
+        if lib.cvf_ae_step_route(fl.desc, _hip.ptr(fl.theta), int(with_grad), None) >= 0:
+            return False
+        fused = lib.cvf_last_error().decode()
+        if lib.cvf_ae_general_supported(fl.desc) != 1:
+            raise NotImplementedError("AutoEncoderTask: no HIP route trains this chain (%s; %s)"
+                                      % (fused, lib.cvf_last_error().decode()))
+        return True
 
     def _features(self, rows):
         """K1 over host frames -> row-major feature rows resident in HBM."""
@@ -1452,18 +1468,20 @@ class AutoEncoderTask(TrainingTask):
         computes it once per (static) batch."""
         lib, fl = _hip.lib(), self._flat
         B = w.shape[0]
-        sc = self._scratch.get(B)
+        general = self._general[bool(with_grad)]
+        step, name = (lib.cvf_ae_general_step, "cvf_ae_general_step") if general else (lib.cvf_ae_step, "cvf_ae_step")
+        sc = self._scratch.get((B, general))
         if sc is None:
-            sc = self._scratch[B] = torch.empty(lib.cvf_ae_scratch_floats(fl.desc, B), device=self.device, dtype=torch.float32)
+            size = lib.cvf_ae_general_scratch_floats if general else lib.cvf_ae_scratch_floats
+            sc = self._scratch[(B, general)] = torch.empty(size(fl.desc, B), device=self.device, dtype=torch.float32)
         if inv_wsum is None:
             wsum = w.sum(dtype=torch.float64)
             _dist.allreduce_sum_(wsum)
             inv_wsum = 1.0 / float(wsum)
         adam = self.optimizer.fused_args() if (fuse_adam and with_grad) else None
-        _hip.check(lib.cvf_ae_step(fl.desc, _hip.ptr(fl.theta), _hip.ptr(feat), _hip.ptr(idx), B, _hip.ptr(w),
-                                   inv_wsum, _hip.ptr(sc), _hip.ptr(self._out2),
-                                   _hip.ptr(fl.grad) if with_grad else None,
-                                   _hip.ptr(self.optimizer.step_count) if advance else None, adam, _hip.stream()), "cvf_ae_step")
+        _hip.check(step(fl.desc, _hip.ptr(fl.theta), _hip.ptr(feat), _hip.ptr(idx), B, _hip.ptr(w), inv_wsum, _hip.ptr(sc),
+                        _hip.ptr(self._out2), _hip.ptr(fl.grad) if with_grad else None,
+                        _hip.ptr(self.optimizer.step_count) if advance else None, adam, _hip.stream()), name)
         if _dist.world() == 1:
             # (the kernel left the ratio beside the two sums: no arithmetic launches on the host side of a step; the caller
             #  copies the value out before the next step overwrites it)

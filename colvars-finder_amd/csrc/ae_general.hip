@@ -1,0 +1,475 @@
+// AutoEncoderTask step for chains of ANY width (cvf_ae_general_*): the chains cvf_ae_step refuses because their parameters and
+// a tile's activation images do not fit 160 KiB of LDS (csrc/ae.hip).  One chain (n_nets == 1, dims[0] == dims[L]) of 1 to
+// CVF_MAX_LAYERS layers, widths 1 to 4096, d0 <= 65536, any activation code of include/cvf.h.  Where ae_mfma_kernel keeps a
+// 64-frame tile's whole chain in LDS, here every product of the step is ONE launch over all tiles, and the activations are
+// handed from launch to launch through HBM (the decomposition of csrc/ef_general.hip):
+//
+//   aeg_gather_kernel   feat_rows[idx] (row-major [n][d0]) -> a_0 [tile][d0][64]; padded frames of the last tile are zero
+//   aeg_layer_kernel    [M x K] x [K x 64 frames] per (tile, 64-row block): W_l (forward) or W_l^T (backward) as the A operand,
+//                       an activation image as the B operand; the epilogue adds the bias and applies act, or multiplies by act'
+//   aeg_err_kernel      zbar_L = 2 w (out - f) inv_wsum .* act'_{L-1}(out) in place of out, and the tile's fp64 sums of w err, w
+//   aeg_wgrad_kernel    dW_l | db_l = sum_frames zbar_{l+1} (x) [a_l ; 1] (K = frames), the tiles split over a fixed number of
+//                       slab rows (row rho sums tiles rho, rho + R, ... in that order)
+//   aeg_loss_sum_kernel loss-only calls: the tiles' pairs -> out2 (with a gradient they ride in cvf_slab_reduce_impl's launch)
+//
+// Mathematics (layers l = 0..L-1, a_0 = f):  a_{l+1} = act_l(W_l a_l + b_l), out = a_L, loss = sum w |out - f|^2 / sum w,
+//   zbar_L = 2 w (out - f) / sum w .* act'_{L-1}(a_L),  zbar_l = (W_l^T zbar_{l+1}) .* act'_{l-1}(a_l)   (act' through the output),
+//   dW_l = sum_frames zbar_{l+1} (x) a_l,  db_l = sum_frames zbar_{l+1}.
+//
+// All products run on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation.  No atomics: every slab entry is written by one
+// thread and the sum order of every entry is fixed by the grid, so two calls on the same inputs give the same bits.  Nothing is
+// read from scratch that the same call did not write.
+#include "cvf_common.hpp"
+#include <stdio.h>
+
+// (csrc/ef_mfma.hip) fixed-order sum of slab rows [+ Adam] [+ one extra block adding n_pair [a, b] rows -> [a, b, a / b]]
+int cvf_slab_reduce_impl(const float* slab, int64_t n_rows, int64_t n_params, float* grad, const float* mask,
+                         const cvf_adam_args* adam, void* stream, const double* pair_partial = nullptr, int n_pair = 0,
+                         double* pair_out = nullptr);
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+constexpr int kMaxWidth = 4096;     // widest hidden layer cvf_ae_general_supported() accepts (d0 up to kMaxD0)
+constexpr int kMaxD0 = 65536;
+constexpr int64_t kSlabBytes = 128ll << 20;   // slab budget: rows = 128 MiB / (4 n_params), at least 1, at most kMaxRows
+constexpr int kMaxRows = 256;
+
+// ---- feat_rows[idx] -> [tile][d0][64], 64 features at a time through an LDS transpose (rows are read along the features)
+constexpr int kTP = 65;
+__global__ __launch_bounds__(256) void aeg_gather_kernel(const float* __restrict__ feat_rows, const int64_t* __restrict__ idx,
+                                                         int64_t B, int d0, float* __restrict__ a0) {
+  __shared__ float S[CVF_TILE * kTP];   // [frame][feature]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  float* out = a0 + tile * d0 * CVF_TILE;
+  for (int c0 = 0; c0 < d0; c0 += 64) {
+#pragma unroll 4
+    for (int it = 0; it < 16; ++it) {
+      const int fr = wave + 4 * it;
+      const int64_t frame = tile * CVF_TILE + fr;
+      float v = 0.0f;
+      if (frame < B && c0 + lane < d0) {
+        const int64_t row = idx != nullptr ? idx[frame] : frame;
+        v = feat_rows[row * d0 + c0 + lane];
+      }
+      S[fr * kTP + lane] = v;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int it = 0; it < 16; ++it) {
+      const int c = wave + 4 * it;
+      if (c0 + c < d0) out[(int64_t)(c0 + c) * CVF_TILE + lane] = S[lane * kTP + c];
+    }
+    __syncthreads();
+  }
+}
+
+enum { EPI_ACT = 0, EPI_BWD = 1 };
+
+struct AegLayerArgs {
+  int w_off, b_off;   // offsets of W_layer and b_layer in theta (b_off < 0: no bias)
+  int ldw;            // row length of W_layer (= dims[layer])
+  int trans;          // 0: A = W [M = dims[layer+1]][K = dims[layer]];  1: A = W^T [M = dims[layer]][K = dims[layer+1]]
+  int M, K;
+  int epi, act;       // EPI_ACT: out = act(acc + b);  EPI_BWD: out = acc .* act'(eh)
+  const float* x;     // B operand [tile][K][64]
+  float* out;         // [tile][M][64]
+  const float* eh;    // EPI_BWD: [tile][M][64]
+  int64_t xs, os, es; // tile strides of the three images
+};
+
+// out[m][frame] (64 x 64 block) = A[m][:] . B[:][frame] for one (tile, row block); 4 waves of 32 x 32
+constexpr int kKC = 32;          // K per LDS stage
+constexpr int kPitch = 80;       // LDS pitch of the k-major images (a fragment read spans 4 k-rows of 16 consecutive words)
+__global__ __launch_bounds__(256) void aeg_layer_kernel(const float* __restrict__ theta, AegLayerArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[kKC * kPitch];   // [k][m]
+  __shared__ __attribute__((aligned(16))) float Bs[kKC * kPitch];   // [k][frame]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t tile = blockIdx.x;
+  const int m0 = blockIdx.y * 64;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int col = lane & 15, kq = lane >> 4;
+  const float* W = theta + a.w_off;
+  const float* xp = a.x + tile * a.xs;
+  // W as stored ([m][k], k contiguous): a wave stages 16 rows x 4 k per pass.  Lanes l and l + 1 read two neighbouring k of a
+  // row (8 bytes), lanes l + 32 and l + 33 the next two; the 32 lanes of a half write two k-rows 16 words apart (pitch 80) at
+  // 16 consecutive m: 32 distinct banks
+  const int kl = (lane & 1) + 2 * (lane >> 5), ml = 16 * wave + ((lane >> 1) & 15);
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  for (int k0 = 0; k0 < a.K; k0 += kKC) {
+#pragma unroll
+    for (int it = 0; it < kKC / 4; ++it) {
+      if (a.trans) {   // W^T: m runs along W's rows, over the lanes
+        const int kk = wave + 4 * it, k = k0 + kk, m = m0 + lane;
+        As[kk * kPitch + lane] = m < a.M && k < a.K ? W[(int64_t)k * a.ldw + m] : 0.0f;
+      } else {
+        const int kk = 4 * it + kl, k = k0 + kk, m = m0 + ml;
+        As[kk * kPitch + ml] = m < a.M && k < a.K ? W[(int64_t)m * a.ldw + k] : 0.0f;
+      }
+      const int kk = wave + 4 * it, k = k0 + kk;
+      Bs[kk * kPitch + lane] = k < a.K ? xp[(int64_t)k * CVF_TILE + lane] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < kKC; ks += 4) {
+      const int kr = (ks + kq) * kPitch;
+      const float a0 = As[kr + wm + col], a1 = As[kr + wm + 16 + col];
+      const float b0 = Bs[kr + wn + col], b1 = Bs[kr + wn + 16 + col];
+      acc[0][0] = mfma4(a0, b0, acc[0][0]);
+      acc[0][1] = mfma4(a0, b1, acc[0][1]);
+      acc[1][0] = mfma4(a1, b0, acc[1][0]);
+      acc[1][1] = mfma4(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: C row = 4 * (lane >> 4) + r of each 16 x 16 block, column (frame) = lane & 15
+  const float* bias = a.b_off >= 0 ? theta + a.b_off : nullptr;
+  float* op = a.out + tile * a.os;
+  const float* ep = a.epi == EPI_BWD ? a.eh + tile * a.es : nullptr;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm + 16 * i + 4 * kq + r;
+        const int f = wn + 16 * j + col;
+        if (m >= a.M) continue;
+        float v = acc[i][j][r];
+        const int64_t o = (int64_t)m * CVF_TILE + f;
+        if (a.epi == EPI_ACT) {
+          if (bias != nullptr) v += bias[m];
+          op[o] = cvf_act(a.act, v);
+        } else {
+          op[o] = cvf_act_d1(a.act, ep[o]) * v;
+        }
+      }
+}
+
+// the output error of one tile: err = sum_i (out_i - f_i)^2 per frame, partial[tile] = {sum w err, sum w} in fp64, and (with a
+// gradient) zbar_L = 2 w (out - f) inv_wsum .* act'(out) in place of out.  Wave j takes rows j, j + 4, ...; the four waves' sums
+// of a frame are added in the order 0, 1, 2, 3.
+__global__ __launch_bounds__(256) void aeg_err_kernel(float* __restrict__ out, const float* __restrict__ a0, const float* __restrict__ w,
+                                                      int64_t B, int d0, int act, double inv_wsum, int with_grad,
+                                                      double* __restrict__ partial, int32_t* __restrict__ step) {
+  __shared__ double part[4][CVF_TILE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  const int64_t frame = tile * CVF_TILE + lane;
+  const float wb = frame < B ? w[frame] : 0.0f;
+  const float s = (float)(2.0 * (double)wb * inv_wsum);
+  float* op = out + tile * d0 * CVF_TILE;
+  const float* fp = a0 + tile * d0 * CVF_TILE;
+  double e = 0.0;
+  for (int i = wave; i < d0; i += 4) {
+    const float o = op[(int64_t)i * CVF_TILE + lane];
+    const float d = o - fp[(int64_t)i * CVF_TILE + lane];
+    e += (double)d * (double)d;
+    if (with_grad) op[(int64_t)i * CVF_TILE + lane] = s * d * cvf_act_d1(act, o);
+  }
+  part[wave][lane] = e;
+  __syncthreads();
+  if (wave == 0) {
+    const double err = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    const double a = wave_sum((double)wb * err), b = wave_sum((double)wb);
+    if (lane == 0) {
+      partial[2 * tile] = a;
+      partial[2 * tile + 1] = b;
+      if (step != nullptr && tile == 0) *step += 1;
+    }
+  }
+}
+
+struct AegGradArgs {
+  int w_off, b_off;   // where layer's W [Mo][Ki] and b [Mo] sit in a slab row
+  int Mo, Ki;
+  int64_t n_tiles, B;
+  int rows;           // slab rows R: row rho sums tiles rho, rho + R, ... in that order
+  int64_t n_params;
+  const float* z;     // zbar_{layer+1} [tile][Mo][64]
+  const float* h;     // a_layer [tile][Ki][64]
+  int64_t zs, hs;
+};
+
+constexpr int kGP = 68;   // LDS pitch of the [row][frame] images (a fragment read spans 16 rows x 4 consecutive frames)
+__global__ __launch_bounds__(256) void aeg_wgrad_kernel(AegGradArgs a, float* __restrict__ slab) {
+  __shared__ __attribute__((aligned(16))) float As[64 * kGP];   // [out row][frame]
+  __shared__ __attribute__((aligned(16))) float Bs[64 * kGP];   // [in column][frame]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int rho = blockIdx.x;
+  const int nbn = (a.Ki + 1 + 63) / 64;
+  const int o0 = (blockIdx.y / nbn) * 64, i0 = (blockIdx.y % nbn) * 64;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int col = lane & 15, kq = lane >> 4;
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  for (int64_t tile = rho; tile < a.n_tiles; tile += a.rows) {
+    const bool valid = tile * CVF_TILE + lane < a.B;   // padded frames contribute nothing: zero on both operands
+    const float* zp = a.z + tile * a.zs;
+    const float* hp = a.h + tile * a.hs;
+#pragma unroll 4
+    for (int it = 0; it < 16; ++it) {
+      const int rr = wave + 4 * it;
+      const int o = o0 + rr, i = i0 + rr;
+      As[rr * kGP + lane] = valid && o < a.Mo ? zp[(int64_t)o * CVF_TILE + lane] : 0.0f;
+      float x = 0.0f;
+      if (valid) {
+        if (i < a.Ki) x = hp[(int64_t)i * CVF_TILE + lane];
+        else if (i == a.Ki) x = 1.0f;   // the bias column: [a ; 1]
+      }
+      Bs[rr * kGP + lane] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < 64; ks += 4) {
+      const int kf = ks + kq;
+      const float a0 = As[(wm + col) * kGP + kf], a1 = As[(wm + 16 + col) * kGP + kf];
+      const float b0 = Bs[(wn + col) * kGP + kf], b1 = Bs[(wn + 16 + col) * kGP + kf];
+      acc[0][0] = mfma4(a0, b0, acc[0][0]);
+      acc[0][1] = mfma4(a0, b1, acc[0][1]);
+      acc[1][0] = mfma4(a1, b0, acc[1][0]);
+      acc[1][1] = mfma4(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+
+  float* row = slab + (int64_t)rho * a.n_params;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = o0 + wm + 16 * i + 4 * kq + r;
+        const int c = i0 + wn + 16 * j + col;
+        if (o >= a.Mo || c > a.Ki) continue;
+        if (c < a.Ki) row[a.w_off + (int64_t)o * a.Ki + c] = acc[i][j][r];
+        else row[a.b_off + o] = acc[i][j][r];
+      }
+}
+
+// loss-only calls: the tiles' [sum w err, sum w] pairs, fixed order -> out2 = {a, b, a / b} (cvf_ae_step's ae_loss_sum_kernel)
+__global__ __launch_bounds__(64) void aeg_loss_sum_kernel(const double* __restrict__ partial, int64_t n, double* __restrict__ out2) {
+  const int lane = threadIdx.x;
+  double a0 = 0.0, a1 = 0.0;
+  for (int64_t g = lane; g < n; g += 64) {
+    a0 += partial[2 * g];
+    a1 += partial[2 * g + 1];
+  }
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  if (lane == 0) {
+    out2[0] = a0;
+    out2[1] = a1;
+    out2[2] = a0 / a1;
+  }
+}
+
+// ---- scratch: a_0, a_1..a_{L-1} ([tile][width][64] each), two ping-pong images of zbar (widest of dims[1..L]; zbar_l and the
+// chain's output sit in image l & 1), the slab rows, the tiles' partial pairs (doubles, 8-byte aligned)
+struct AegLayout {
+  int64_t a[CVF_MAX_LAYERS], zb[2], slab, partial, total;
+  int64_t rows;
+  int wmax;
+};
+
+int64_t aeg_rows(const cvf_mlp_desc* mlp, int64_t n_tiles) {
+  int64_t r = kSlabBytes / (4 * (int64_t)(mlp->n_params > 0 ? mlp->n_params : 1));
+  r = r < 1 ? 1 : r > kMaxRows ? kMaxRows : r;
+  return n_tiles < r ? (n_tiles < 1 ? 1 : n_tiles) : r;
+}
+
+AegLayout aeg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles) {
+  AegLayout L = {};
+  const int64_t per = n_tiles * CVF_TILE;   // floats of one row of every tile
+  int64_t pos = 0;
+  L.wmax = 1;
+  for (int l = 0; l < mlp->n_layers; ++l) {
+    L.a[l] = pos;
+    pos += per * mlp->dims[l];
+    L.wmax = mlp->dims[l + 1] > L.wmax ? mlp->dims[l + 1] : L.wmax;
+  }
+  for (int i = 0; i < 2; ++i) {
+    L.zb[i] = pos;
+    pos += per * L.wmax;
+  }
+  L.rows = aeg_rows(mlp, n_tiles);
+  L.slab = pos;
+  pos += L.rows * mlp->n_params;
+  L.partial = (pos + 1) & ~(int64_t)1;
+  L.total = L.partial + 4 * n_tiles;
+  return L;
+}
+
+const char* aeg_why(const cvf_mlp_desc* mlp) {
+  static thread_local char buf[160];
+  if (mlp == nullptr) return "no chain description";
+  if (mlp->n_nets != 1) {
+    snprintf(buf, sizeof buf, "%d nets: one chain is expected", mlp->n_nets);
+    return buf;
+  }
+  if (mlp->n_layers < 1 || mlp->n_layers > CVF_MAX_LAYERS) {
+    snprintf(buf, sizeof buf, "%d layers: 1 to %d are supported", mlp->n_layers, CVF_MAX_LAYERS);
+    return buf;
+  }
+  const int L = mlp->n_layers;
+  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
+    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
+    return buf;
+  }
+  if (mlp->dims[L] != mlp->dims[0]) {
+    snprintf(buf, sizeof buf, "output width %d != input width %d", mlp->dims[L], mlp->dims[0]);
+    return buf;
+  }
+  for (int l = 1; l < L; ++l)
+    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
+      snprintf(buf, sizeof buf, "hidden layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
+      return buf;
+    }
+  for (int l = 0; l < L; ++l)   // aeg_wgrad_kernel's 64 x 64 blocks of [W_l | b_l] are its grid.y
+    if ((int64_t)((mlp->dims[l + 1] + 63) / 64) * ((mlp->dims[l] + 1 + 63) / 64) > 65535) {
+      snprintf(buf, sizeof buf, "layer %d (%d x %d) has more than 65535 blocks of 64 x 64 weights", l, mlp->dims[l + 1], mlp->dims[l]);
+      return buf;
+    }
+  for (int l = 0; l < L; ++l)
+    if (mlp->act[l] < CVF_ACT_NONE || mlp->act[l] > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
+  int64_t n = 0;
+  for (int l = 0; l < L; ++l) n += (int64_t)mlp->dims[l + 1] * (mlp->dims[l] + 1);
+  if (n != mlp->n_params) return "the flat buffer holds parameters outside the chain";
+  for (int l = 0; l < L; ++l)
+    if (mlp->w_off[0][l] < 0 || mlp->w_off[0][l] + (int64_t)mlp->dims[l + 1] * mlp->dims[l] > n || mlp->b_off[0][l] < 0 ||
+        mlp->b_off[0][l] + (int64_t)mlp->dims[l + 1] > n)
+      return "a layer's parameters lie outside the flat buffer";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int cvf_ae_general_supported(const cvf_mlp_desc* mlp) {
+  const char* why = aeg_why(mlp);
+  if (why != nullptr) {
+    cvf_set_error("cvf_ae_general: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_ae_general_scratch_floats(const cvf_mlp_desc* mlp, int64_t B) {
+  if (aeg_why(mlp) != nullptr || B < 1) return 0;
+  return aeg_layout(mlp, cvf_ntiles(B)).total;
+}
+
+extern "C" int cvf_ae_general_step(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx,
+                                   int64_t B, const float* w, double inv_wsum, float* scratch, double* out2, float* grad,
+                                   int32_t* step_count, const cvf_adam_args* adam, void* stream) {
+  const char* why = aeg_why(mlp);
+  CVF_REQUIRE(why == nullptr, "cvf_ae_general_step: %s", why);
+  CVF_REQUIRE(theta && feat_rows && w && scratch && out2 && B > 0, "cvf_ae_general_step: bad argument");
+  CVF_REQUIRE(adam == nullptr || (grad && adam->theta && adam->m && adam->v && adam->step_count),
+              "cvf_ae_general_step: incomplete adam arguments");
+  const int64_t T = cvf_ntiles(B);
+  CVF_REQUIRE(T <= 0x7fffffff, "cvf_ae_general_step: %lld frames are more than one call takes", (long long)B);
+  hipStream_t s = (hipStream_t)stream;
+  const int L = mlp->n_layers, d0 = mlp->dims[0];
+  const AegLayout lay = aeg_layout(mlp, T);
+  auto A = [&](int l) { return scratch + lay.a[l]; };           // a_l, l = 0..L-1
+  auto Z = [&](int l) { return scratch + lay.zb[l & 1]; };      // zbar_l, l = 1..L (a_L = out before aeg_err_kernel)
+  auto ts = [&](int l) { return (int64_t)mlp->dims[l] * CVF_TILE; };
+  float* slab = scratch + lay.slab;
+  double* partial = reinterpret_cast<double*>(scratch + lay.partial);
+
+  hipLaunchKernelGGL(aeg_gather_kernel, dim3((unsigned)T), dim3(256), 0, s, feat_rows, idx, B, d0, A(0));
+  if (cvf_check_launch("aeg_gather_kernel")) return -1;
+
+  auto layer = [&](const AegLayerArgs& a) {
+    hipLaunchKernelGGL(aeg_layer_kernel, dim3((unsigned)T, (unsigned)((a.M + 63) / 64)), dim3(256), 0, s, theta, a);
+    return cvf_check_launch("aeg_layer_kernel");
+  };
+  // forward: a_{l+1} = act_l(W_l a_l + b_l); the chain's output goes to the zbar image of layer L
+  for (int l = 0; l < L; ++l) {
+    AegLayerArgs a = {};
+    a.w_off = mlp->w_off[0][l];
+    a.b_off = mlp->b_off[0][l];
+    a.ldw = mlp->dims[l];
+    a.M = mlp->dims[l + 1];
+    a.K = mlp->dims[l];
+    a.epi = EPI_ACT;
+    a.act = mlp->act[l];
+    a.x = A(l);
+    a.xs = ts(l);
+    a.out = l + 1 < L ? A(l + 1) : Z(L);
+    a.os = ts(l + 1);
+    if (layer(a)) return -1;
+  }
+  hipLaunchKernelGGL(aeg_err_kernel, dim3((unsigned)T), dim3(256), 0, s, Z(L), A(0), w, B, d0, mlp->act[L - 1], inv_wsum,
+                     grad != nullptr ? 1 : 0, partial, grad != nullptr ? step_count : nullptr);
+  if (cvf_check_launch("aeg_err_kernel")) return -1;
+  if (grad == nullptr) {
+    hipLaunchKernelGGL(aeg_loss_sum_kernel, dim3(1), dim3(64), 0, s, partial, T, out2);
+    return cvf_check_launch("aeg_loss_sum_kernel");
+  }
+
+  const int R = (int)lay.rows;
+  for (int l = L - 1; l >= 0; --l) {
+    {  // layer l's gradient from zbar_{l+1} and a_l
+      AegGradArgs g = {};
+      g.w_off = mlp->w_off[0][l];
+      g.b_off = mlp->b_off[0][l];
+      g.Mo = mlp->dims[l + 1];
+      g.Ki = mlp->dims[l];
+      g.n_tiles = T;
+      g.B = B;
+      g.rows = R;
+      g.n_params = mlp->n_params;
+      g.z = Z(l + 1);
+      g.zs = ts(l + 1);
+      g.h = A(l);
+      g.hs = ts(l);
+      const int nb = ((g.Mo + 63) / 64) * ((g.Ki + 1 + 63) / 64);
+      hipLaunchKernelGGL(aeg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb), dim3(256), 0, s, g, slab);
+      if (cvf_check_launch("aeg_wgrad_kernel")) return -1;
+    }
+    if (l == 0) break;
+    // zbar_l = (W_l^T zbar_{l+1}) .* act'_{l-1}(a_l)
+    AegLayerArgs a = {};
+    a.w_off = mlp->w_off[0][l];
+    a.b_off = -1;
+    a.ldw = mlp->dims[l];
+    a.trans = 1;
+    a.M = mlp->dims[l];
+    a.K = mlp->dims[l + 1];
+    a.epi = EPI_BWD;
+    a.act = mlp->act[l - 1];
+    a.x = Z(l + 1);
+    a.xs = ts(l + 1);
+    a.out = Z(l);
+    a.os = ts(l);
+    a.eh = A(l);
+    a.es = ts(l);
+    if (layer(a)) return -1;
+  }
+  // fixed-order sum of the slab rows (+ the Adam update when asked for), the loss pairs in one extra block of the same launch
+  cvf_adam_args ad;
+  if (adam != nullptr) {
+    ad = *adam;
+    ad.mlp = nullptr;      // an AutoEncoder has no MFMA fragment copy to refresh
+    ad.packed = nullptr;
+  }
+  return cvf_slab_reduce_impl(slab, R, mlp->n_params, grad, nullptr, adam != nullptr ? &ad : nullptr, stream, partial, (int)T, out2);
+}

@@ -412,6 +412,24 @@ int cvf_ae_step(const cvf_mlp_desc* mlp, const float* theta, const float* feat_r
  * while the process runs - by the thread that makes the calls: getenv is not safe against a concurrent setenv. */
 int cvf_ae_step_route(const cvf_mlp_desc* mlp, const void* theta, int with_grad, int64_t* lds_bytes);
 
+/* --- AutoEncoder chains of ANY width (csrc/ae_general.hip): the step for the chains cvf_ae_step_route
+ * refuses - one launch per layer and pass over all 64-frame tiles, the activations handed over through `scratch`, instead of a
+ * chain resident in LDS.  One chain (n_nets == 1, dims[0] == dims[n_layers]) of 1 to CVF_MAX_LAYERS layers, hidden widths 1 to
+ * 4096, d0 <= 65536, at most 65535 blocks of 64 x 64 weights in a layer (d0 = 65536 beside a layer wider than 4032 passes it),
+ * any act code of this header, parameters that fill the flat buffer; theta needs no alignment.  No atomics:
+ * the same inputs give the same bits.
+ *  cvf_ae_general_supported     : 1, or 0 with the reason in cvf_last_error().
+ *  cvf_ae_general_scratch_floats: floats of `scratch` (8-byte aligned) for a batch of B frames, T = ceil(B / 64) tiles:
+ *                                 64 T (d0 + sum of the hidden widths + 2 max(dims[1..n_layers])) for the tiled input, the saved
+ *                                 activations and two adjoint images, R n_params slab rows with R = min(T, 256, 128 MiB /
+ *                                 (4 n_params)) >= 1, rounded up to even, + 4 T for the tiles' loss pairs; 0 for a refused chain.
+ *  cvf_ae_general_step          : the arguments, outputs and conventions of cvf_ae_step (out2, grad, step_count, adam). */
+int cvf_ae_general_supported(const cvf_mlp_desc* mlp);
+int64_t cvf_ae_general_scratch_floats(const cvf_mlp_desc* mlp, int64_t B);
+int cvf_ae_general_step(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                        const float* w, double inv_wsum, float* scratch, double* out2, float* grad, int32_t* step_count,
+                        const cvf_adam_args* adam, void* stream);
+
 /* --- RegAutoEncoderTask (core.py:746-1217): time-lagged reconstruction loss
  * (weighted_MSE_loss, core.py:883-885) + transfer-operator eigenfunction regulariser (reg_eigen_loss with
  * lag_tau_reg > 0, core.py:973-1036) + the variance / covariance penalties on the latent vector (reg_enc_norm_loss,
