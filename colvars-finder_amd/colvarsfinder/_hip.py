@@ -49,7 +49,7 @@ class MLPDesc(C.Structure):
 
 
 class EFCfg(C.Structure):
-    _fields_ = [("k", C.c_int32), ("lag_idx", C.c_int32), ("sort_eigvals", C.c_int32), ("pad_", C.c_int32),
+    _fields_ = [("k", C.c_int32), ("lag_idx", C.c_int32), ("sort_eigvals", C.c_int32), ("iso_metric", C.c_int32),
                 ("alpha", C.c_double), ("beta", C.c_double), ("dt", C.c_double), ("eig_w", C.c_double * MAX_NETS)]
 
 
@@ -191,6 +191,9 @@ _SIGNATURES = {
                                C.c_void_p]),
 }
 
+# the isotropic-metric forms of the two front calls take the arguments of their general twins
+_SIGNATURES["cvf_ef16_front_iso"] = _SIGNATURES["cvf_ef16_front"]
+_SIGNATURES["cvf_ef16_front_rows_iso"] = _SIGNATURES["cvf_ef16_front_rows"]
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

@@ -657,6 +657,19 @@ class TrainingTask(ABC):
         pass
 
 
+def metric_is_isotropic(diag_coeff, n_rec):
+    """True when ``diag_coeff`` (None: ones) holds ONE coefficient per record atom: ``a[3b] == a[3b+1] == a[3b+2]``, compared
+    exactly in the fp32 the kernels read, for every ``b < n_rec``.  Entries past ``3 * n_rec`` belong to atoms no feature reads and
+    are not compared; a NaN anywhere, or a vector shorter than ``3 * n_rec``, answers False."""
+    if diag_coeff is None:
+        return True
+    a = torch.as_tensor(diag_coeff).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    if a.numel() < 3 * n_rec or bool(torch.isnan(a).any()):
+        return False
+    a = a[:3 * n_rec].reshape(n_rec, 3)
+    return bool(((a[:, 0] == a[:, 1]) & (a[:, 1] == a[:, 2])).all())
+
+
 class _EFRoute(NamedTuple):
     """Which launches an EigenFunctionTask step runs: decided once per task, on first use (EigenFunctionTask._route), from the
     nets, the layer and the developer switches below - every place that picks a launch reads this record.
@@ -665,6 +678,8 @@ class _EFRoute(NamedTuple):
       CVF_PIPELINE=1           align the next batch beside the backward launch (read at construction); turns the ef16 route off
       CVF_NO_EF16              generator mode: no 16-frame route (the C library reads it too, in cvf_ef16_supported)
       CVF_NO_EF16_TRANSFER     transfer mode: no 16-frame route
+      CVF_EF16_ISO=0           generator mode, 16-frame route: the general (laboratory-frame) passes of q = J A J^T g even where
+                               diag_coeff is isotropic (read at construction: EigenFunctionTask.metric_isotropic)
       CVF_NO_TRANSFER_ROWS     ef16 transfer mode: the front launch without unit rows + cvf_ef_stats
       CVF_NO_ALIGN_FWD         transfer mode: no fused alignment + forward launch (plain route instead)
       CVF_NO_FWD_METRIC        read by the C library in cvf_ef_fwd_metric_supported: no fused generator launch
@@ -835,6 +850,10 @@ class EigenFunctionTask(TrainingTask):
                 self._pp = identity_desc(int(y.reshape(y.shape[0], -1).shape[1]))
         else:
             self._pp = self._pp_desc(self.tot_dim)
+        # One coefficient per record atom (ones, 1 / mass): the 16-frame front launch forms q = J A J^T g in the aligned frame
+        # (`cfg.iso_metric`, include/cvf.h).  Decided once, here; CVF_EF16_ISO=0 keeps the general passes.
+        self.metric_isotropic = (self.lag_idx == 0 and not self._foreign_pp and os.environ.get("CVF_EF16_ISO", "1") != "0"
+                                 and metric_is_isotropic(diag_coeff, int(self._pp.n_rec)))
         self._traj = None if self._sharded else self._frames(self._traj_host.all())
         self._weights = torch.as_tensor(np.asarray(traj_obj.weights)).to(device=self.device, dtype=torch.float32).contiguous()
         self.resident_bytes = 0 if self._sharded else self._traj.numel() * 4    # frames (or records) held in HBM (train() adds its gathers)
@@ -842,6 +861,7 @@ class EigenFunctionTask(TrainingTask):
             f'preprocessing layer emits {self._pp.d_r} features but the networks take {self._flat.desc.dims[0]}'
         cfg = _hip.EFCfg()
         cfg.k, cfg.lag_idx, cfg.sort_eigvals = k, self.lag_idx, int(bool(sort_eigvals_in_training))
+        cfg.iso_metric = int(self.metric_isotropic)
         cfg.alpha, cfg.beta, cfg.dt = float(alpha), float(beta), float(self.traj_dt)
         for i in range(k):
             cfg.eig_w[i] = float(eig_weights[i])
@@ -1079,6 +1099,7 @@ class EigenFunctionTask(TrainingTask):
             ws.tile = al[1]   # the front launch reads the batch's tile, and so does the backward launch (`ws.feat_in`)
         args = (fl.desc, P(fl.theta), P(fl.packed), P(ws.feat_in), self._pp, P(X), ws.B, P(self._diag_coeff), P(ws.y), P(ws.saved),
                 P(ws.q), P(ws.e), self._cfg, P(w), P(ws.scratch), None if ws.unit_rows else P(ws.stats), lv, cf)
+        # (an isotropic metric travels in `self._cfg.iso_metric`: the same two entry points, their aligned-frame passes)
         if al is not None:   # (the same name for either form: one call of the step, the same outputs)
             self._call("cvf_ef16_front", lib.cvf_ef16_front_rows, *args, P(al[0]), s)
         else:

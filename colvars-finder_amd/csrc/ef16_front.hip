@@ -73,6 +73,16 @@ extern "C" int cvf_ef16_front(const cvf_mlp_desc* mlp, const float* theta, const
                               stats, loss_vec, coef, nullptr, stream);
 }
 
+// ... with an ISOTROPIC metric: `a` holds ONE coefficient per record atom, repeated over its x, y and z (the reference's default of
+// ones and its 1 / mass form), and q = J A J^T g is formed in the aligned frame (see the kernel).  The caller answers for that.
+extern "C" int cvf_ef16_front_iso(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
+                                  const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, float* y_tiled, float* saved,
+                                  float* q_tiled, float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats,
+                                  double* loss_vec, double* coef, void* stream) {
+  return ef16_front_go<false>("cvf_ef16_front_iso", mlp, theta, packed, feat_tiled, pp, x, B, a, y_tiled, saved, q_tiled, e_tiled, cfg, w,
+                              scratch, stats, loss_vec, coef, nullptr, stream, true);
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // transfer-operator mode (lag_tau > 0; core.py:403,414,420-431,440): y on the frames and on their lagged partners, then the

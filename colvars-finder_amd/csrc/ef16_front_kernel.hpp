@@ -74,6 +74,8 @@ __device__ __forceinline__ V3 ef16_feature(const float* my, const int at, const 
 //     them, all before anything is waited for - vector memory returns in issue order, so the LDS stores of the staged
 //     pieces wait for those loads alone - and the block's one barrier for the staged data stands where it is first read
 //     by another wave, in front of CVF_STAMP(26).
+//   * with an isotropic metric (launch bit 9) the head requests and stages no coordinates: the passes read the features, which
+//     the waves copy from layer 0's operand into the LDS image beside layer 0.
 // Everything else is the code of the solving instance on the same records and features.  Generator instances only.
 template <int H, int NH, int NIT, bool ALLAL, bool ROWS = false>
 __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, const float* __restrict__ theta,
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   // held them in two: 5 blocks per CU by registers and LDS)
   constexpr bool kTransfer = NIT == 0;
   extern __shared__ __attribute__((aligned(16))) float lds_all[];
-  // `launch` = units per workgroup | paired << 8.  Several units per workgroup (a developer switch, off by default - measured
+  // `launch` = units per workgroup | paired << 8 | isotropic << 9.  Several units per workgroup (a developer switch, off by default - measured
   // slower, see ef16_units_per_wg): a workgroup of upb k waves takes upb consecutive units, each on its own k waves and its own
   // copy of the LDS layout, exactly as upb workgroups of one unit would - the units only share the workgroup's barriers.
   const int upb = launch & 0xff;
@@ -115,7 +117,11 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   //     launch is one round of units_x blocks doing two units each instead of two rounds of 2 units_x blocks.
   //   unpaired: the units of x, then the units of the lagged frames, one per block.
   // In both the lagged frames' tiles follow the tiles of x in every tiled output, and a pass stops after y and the hand-off.
-  const bool paired = kTransfer && x_lag != nullptr && (launch >> 8) != 0;   // (uniform)
+  const bool paired = kTransfer && x_lag != nullptr && ((launch >> 8) & 1) != 0;   // (uniform)
+  // ISOTROPIC metric (launch bit 9, generator instances; wave-uniform, in an SGPR): the caller vouches that the three coefficients
+  // of every record atom are equal, a[3b] == a[3b+1] == a[3b+2].  Then R a_b R^T = a_b I and q = J A J^T g is formed in the ALIGNED
+  // frame, from the features alone (see the passes behind CVF_STAMP(26)): no rotation, no centroid and no coordinates are read.
+  const bool iso = !kTransfer && ((launch >> 9) & 1) != 0;
   const int nc = pp.n_coord, nal = pp.n_align, N = pp.n_rec;
   const int stride = x_tile_stride(nc);
   const Front16Lds Lo = front16_lds(nc, nal, k);   // (the transfer instance is launched with Lo.g + 16 floats per unit: no g images)
@@ -191,8 +197,11 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     const float4* xsrc = reinterpret_cast<const float4*>(x + unit * (int64_t)(kU * nc));
     const float4* xs = plain ? xsrc : rsrc;   // (not plain: any readable piece, dropped)
     const int nx = plain ? n4 : 1;
-    const float4 cx0 = xs[tid < nx ? tid : nx - 1];
-    const float4 cx1 = xs[tid + nthreads < nx ? tid + nthreads : nx - 1];
+    float4 cx0 = {0.0f, 0.0f, 0.0f, 0.0f}, cx1 = cx0;
+    if (!iso) {   // (uniform; isotropic: the passes read the features, and the head requests no coordinates at all)
+      cx0 = xs[tid < nx ? tid : nx - 1];
+      cx1 = xs[tid + nthreads < nx ? tid + nthreads : nx - 1];
+    }
     const int nt = 3 * nal + nc, jt = tid < nt ? tid : nt - 1;   // refL | aL
     const bool in_a = jt >= 3 * nal && a != nullptr;
     const float tv_ld = *(in_a ? a + (jt - 3 * nal) : pp.ref_c + (jt < 3 * nal ? jt : 0));
@@ -215,7 +224,9 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     if (tid < n4r) adst[tid] = row_a;
     if (tid + nthreads < n4r) adst[tid + nthreads] = row_b;
     if (tid < 3) rsL[tid] = rs_in;
-    if (plain) {
+    if (iso) {
+      // (nothing: the unit's features go from bf0 into the LDS image beside layer 0, below)
+    } else if (plain) {
       float4* dst = reinterpret_cast<float4*>(xt);
       if (tid < n4) dst[tid] = cx0;
       if (tid + nthreads < n4) dst[tid + nthreads] = cx1;
@@ -303,7 +314,20 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   set_bias(h[0], bias[0]);
   {
     float bf[SMAX];
-    const float* fr = featI + col * kImgP;
+    float* fr = featI + col * kImgP;
+    static_assert(4 * (SMAX - 1) + 3 < kImgP, "the ROWS twins' feature copy stays inside a frame's row of the image");
+    // ROWS + isotropic: the passes read the unit's features from the LDS image [frame][feature] the solving twins build in their
+    // feature phase.  Every wave of the block holds the unit's features in bf0 (the matrix layout: feature 4 s + q of frame
+    // col), so the waves split the k-steps - wave v takes s = v mod P, P the largest power of two <= the block's waves (a bit
+    // per k-step in an SGPR: no division) - and write them beside layer 0's matrix instructions, in front of the block's barrier
+    // at CVF_STAMP(26).  A row past D (4 s + q <= 71) lands in the padding of the frame's row (kImgP = 76), which nobody reads.
+    unsigned own = 0u;
+    if constexpr (ROWS) {
+      if (iso) {
+        const int P = nw >= 8 ? 8 : nw >= 4 ? 4 : nw >= 2 ? 2 : 1;
+        own = (P == 8 ? 0x10101u : P == 4 ? 0x11111u : P == 2 ? 0x15555u : 0x3ffffu) << (wave & (P - 1));
+      }
+    }
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
       const int kf = 4 * (s < S ? s : S - 1) + q;
@@ -321,6 +345,9 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       if (s < S) {   // wave-uniform
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) h[0].v[rt][0] = mfma4(a0[s][rt], bf[s], h[0].v[rt][0]);
+        if constexpr (ROWS) {
+          if ((own >> s) & 1u) fr[q + 4 * s] = bf[s];   // (wave-uniform; one address register and an immediate offset)
+        }
       }
     }
     CVF_STAMP(24);
@@ -426,13 +453,107 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   // coordinates are read from LDS ONCE into registers (clamped index + mask for the ragged end, no branches), u = a .* G
   // replaces g in those registers and q is formed from them - one LDS round trip for the three passes instead of three.
   {
-    float R[9];
     const float* ar = auxL + f * kAuxP;
+    float* Ul = gI + f * kImgP;
+    V3 gv[NIT];
+    if (iso) {
+    // ---- ISOTROPIC metric (wave-uniform branch): a_b the one coefficient of atom b, f_b its feature = its aligned position (the LDS
+    // image), r_b its reference position (zero off the align atoms).  With u = a .* G = R (a_b G') the lab-frame passes below
+    // become, in the aligned frame,
+    //   pass 1: gbar = sum_b g_b / n_align, tau = sum_b g_b x f_b (the axial vector of R^T M), s = K^-1 tau
+    //   pass 2: G'_b = g_b + m_b (s x r_b - gbar)  (Z ref = R (s x ref)),  u'_b = a_b G'_b,  E = sum_b u'_b . G'_b,
+    //           om = K^-1 (sum_align r_b x u'_b - rsum x ubar')  (the axial vector of R^T dH)
+    //   pass 3: q_b = u'_b - ubar' + f_b x om  ((x - c) dR = f [om]x)
+    // - cross products instead of 3x3 products, 6 quad sums instead of 24, and neither R nor the centroid nor a coordinate.
+    // The lane, duplicate-atom and mask conventions are those of the general passes.
+    const float* Fl = featI + f * kImgP;
+    V3 gsum = v3(0.0f, 0.0f, 0.0f), tau = v3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      int at = p + 4 * it;
+      asm volatile("" : "+v"(at));   // (opaque: the atom's addresses are formed here, not hoisted and kept across the passes)
+      const bool last = it == NIT - 1;
+      const int ac = (last && at >= N) ? N - 1 : at;
+      const float lv = (last && at >= N) ? 0.0f : 1.0f;
+      gv[it] = v3(Ul[3 * ac], Ul[3 * ac + 1], Ul[3 * ac + 2]);
+      const V3 fb = v3(Fl[3 * ac], Fl[3 * ac + 1], Fl[3 * ac + 2]);
+      const V3 gm = last ? lv * gv[it] : gv[it];
+      gsum = gsum + gm;
+      tau.x = fmaf(gm.y, fb.z, fmaf(-gm.z, fb.y, tau.x));
+      tau.y = fmaf(gm.z, fb.x, fmaf(-gm.x, fb.z, tau.y));
+      tau.z = fmaf(gm.x, fb.y, fmaf(-gm.y, fb.x, tau.z));
+    }
+    CVF_STAMP(27);
+    gsum = v3(quad_sumf16(gsum.x), quad_sumf16(gsum.y), quad_sumf16(gsum.z));
+    tau = v3(quad_sumf16(tau.x), quad_sumf16(tau.y), quad_sumf16(tau.z));
+    float Kinv[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Kinv[i] = ar[12 + i];
+    const V3 s = sym_times(Kinv, tau);
+    const float inv_nal = 1.0f / (float)nal;
+    const V3 gbar = inv_nal * gsum;
+    float E = 0.0f;
+    V3 usum = v3(0.0f, 0.0f, 0.0f), tau2 = v3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      int at = p + 4 * it;
+      asm volatile("" : "+v"(at));
+      const bool last = it == NIT - 1;
+      const int ac = (last && at >= N) ? N - 1 : at;
+      const float lv = (last && at >= N) ? 0.0f : 1.0f;             // alive (not a duplicate): counts in the sums
+      const float ma = ALLAL ? 1.0f : (ac < nal ? 1.0f : 0.0f);      // align atom
+      const int ar_ = ALLAL ? ac : (ac < nal ? ac : 0);
+      V3 rf = v3(refL[3 * ar_], refL[3 * ar_ + 1], refL[3 * ar_ + 2]);
+      if (!ALLAL) rf = ma * rf;
+      const V3 sh = ALLAL ? gbar : ma * gbar;
+      V3 G;
+      G.x = fmaf(s.y, rf.z, fmaf(-s.z, rf.y, gv[it].x - sh.x));
+      G.y = fmaf(s.z, rf.x, fmaf(-s.x, rf.z, gv[it].y - sh.y));
+      G.z = fmaf(s.x, rf.y, fmaf(-s.y, rf.x, gv[it].z - sh.z));
+      const V3 u = aL[3 * ac] * G;
+      gv[it] = u;
+      const bool masked = last || !ALLAL;                            // (compile-time)
+      const V3 ue = last ? lv * u : u;
+      E = fmaf(ue.x, G.x, fmaf(ue.y, G.y, fmaf(ue.z, G.z, E)));
+      const V3 um = masked ? (ma * lv) * u : u;
+      usum = usum + um;
+      tau2.x = fmaf(rf.y, um.z, fmaf(-rf.z, um.y, tau2.x));
+      tau2.y = fmaf(rf.z, um.x, fmaf(-rf.x, um.z, tau2.y));
+      tau2.z = fmaf(rf.x, um.y, fmaf(-rf.y, um.x, tau2.z));
+    }
+    CVF_STAMP(28);
+    E = quad_sumf16(E);
+    usum = v3(quad_sumf16(usum.x), quad_sumf16(usum.y), quad_sumf16(usum.z));
+    tau2 = v3(quad_sumf16(tau2.x), quad_sumf16(tau2.y), quad_sumf16(tau2.z));
+    const V3 rsum = v3(rsL[0], rsL[1], rsL[2]);   // sum of the reference over the align atoms (the fp32 residue of its centring)
+    eL[net * kU + f] = E;   // (the four lanes of a frame hold the same sum and store it to the same place)
+    e_tiled[(tile * k + net) * CVF_TILE + kU * sub + f] = E;
+    const V3 ubar = inv_nal * usum;
+    tau2.x = fmaf(-rsum.y, ubar.z, fmaf(rsum.z, ubar.y, tau2.x));
+    tau2.y = fmaf(-rsum.z, ubar.x, fmaf(rsum.x, ubar.z, tau2.y));
+    tau2.z = fmaf(-rsum.x, ubar.y, fmaf(rsum.y, ubar.x, tau2.z));
+    const V3 om = sym_times(Kinv, tau2);
+    CVF_STAMP(31);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      int at = p + 4 * it;
+      asm volatile("" : "+v"(at));
+      const int ac = (it == NIT - 1 && at >= N) ? N - 1 : at;
+      const V3 fb = v3(Fl[3 * ac], Fl[3 * ac + 1], Fl[3 * ac + 2]);
+      V3 qv;
+      qv.x = fmaf(fb.y, om.z, fmaf(-fb.z, om.y, gv[it].x - ubar.x));
+      qv.y = fmaf(fb.z, om.x, fmaf(-fb.x, om.z, gv[it].y - ubar.y));
+      qv.z = fmaf(fb.x, om.y, fmaf(-fb.y, om.x, gv[it].z - ubar.z));
+      gv[it] = qv;   // (kept: q leaves for global memory at the very end, behind every load of this kernel)
+      Ul[3 * ac] = qv.x;
+      Ul[3 * ac + 1] = qv.y;
+      Ul[3 * ac + 2] = qv.z;
+    }
+    } else {
+    float R[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = ar[i];
     const Centre c = centre_of(ar[9], ar[10], ar[11]);
-    float* Ul = gI + f * kImgP;
-    V3 gv[NIT];
     // pass 1: sum_b g_b and M = sum_b (x_b - c) (x) g_b
     V3 gsum = v3(0.0f, 0.0f, 0.0f);
     Outer3 Mo = {{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}}, {0.0f, 0.0f, 0.0f}};
@@ -554,6 +675,7 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       Ul[3 * ac + 1] = qxy.y;
       Ul[3 * ac + 2] = qz;
     }
+    }   // (general metric)
     CVF_STAMP(32);
     asm volatile("" ::: "memory");   // (not earlier: 36 more live registers during the passes spill, and a spill's reload
                                      //  drains every outstanding store)
@@ -739,12 +861,15 @@ static int ef16_units_per_wg(int64_t units, int k, size_t lds_unit_bytes) {
   return upb;
 }
 
-// argument checks, instance dispatch and launch of the generator-mode front kernel (+ the finishing launch when stats != NULL)
+// argument checks, instance dispatch and launch of the generator-mode front kernel (+ the finishing launch when stats != NULL).
+// iso (the _iso entry points) or cfg->iso_metric: the caller vouches for a[3b] == a[3b+1] == a[3b+2] on every record atom (launch bit 9: the aligned-frame passes) - a
+// run-time switch of the same instances, not a template parameter: the branch is wave-uniform and taken once per block, and a
+// second set of instances would double the two longest compilations of the build.
 template <bool ROWS>
 static int ef16_front_go(const char* what, const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
                          const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, float* y_tiled, float* saved, float* q_tiled,
                          float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats, double* loss_vec,
-                         double* coef, const float* align_rows, void* stream) {
+                         double* coef, const float* align_rows, void* stream, bool iso = false) {
   CVF_REQUIRE(pp && pp->mode != CVF_PP_FACTORED, "%s: takes coordinates, not CVF_PP_FACTORED records", what);
   CVF_REQUIRE(cvf_ef16_supported(mlp, pp), "%s: shape not covered (cvf_ef16_supported() == 0)", what);
   CVF_REQUIRE(theta && packed && feat_tiled && x && a && y_tiled && saved && q_tiled && e_tiled && cfg && w && scratch && B > 0,
@@ -767,7 +892,7 @@ static int ef16_front_go(const char* what, const cvf_mlp_desc* mlp, const float*
     auto go = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL(kernel, dim3((unsigned)((units + upb - 1) / upb)), dim3(64 * k * upb), lds, (hipStream_t)stream, *mlp, theta, packed, *pp,
-                         x, B, a, w, feat_tiled, y_tiled, saved, q_tiled, e_tiled, rows ? scratch : nullptr, upb, (const float*)nullptr, units,
+                         x, B, a, w, feat_tiled, y_tiled, saved, q_tiled, e_tiled, rows ? scratch : nullptr, upb | (iso || cfg->iso_metric != 0 ? 512 : 0), (const float*)nullptr, units,
                          (const float*)nullptr, align_rows);
     };
     const int nit = (pp->n_rec + 3) / 4;   // atoms per lane in the four-lanes-per-frame passes (1..6: d_r <= 72)

@@ -107,3 +107,15 @@ extern "C" int cvf_ef16_front_rows(const cvf_mlp_desc* mlp, const float* theta, 
   return ef16_front_go<true>("cvf_ef16_front_rows", mlp, theta, packed, feat_tiled, pp, x, B, a, y_tiled, saved, q_tiled, e_tiled, cfg, w,
                              scratch, stats, loss_vec, coef, rows, stream);
 }
+
+// ... with an isotropic metric (see cvf_ef16_front_iso): bit for bit the outputs of cvf_ef16_front_iso on the same frames.  The
+// head of the block requests no coordinates: the passes read the features, which the waves copy from layer 0's operand into LDS.
+extern "C" int cvf_ef16_front_rows_iso(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
+                                       const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, float* y_tiled, float* saved,
+                                       float* q_tiled, float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch,
+                                       double* stats, double* loss_vec, double* coef, const float* rows, void* stream) {
+  CVF_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+              "cvf_ef16_front_rows_iso: rows (cvf_ef16_align_rows_tile of this batch) missing or not 16-byte aligned");
+  return ef16_front_go<true>("cvf_ef16_front_rows_iso", mlp, theta, packed, feat_tiled, pp, x, B, a, y_tiled, saved, q_tiled, e_tiled, cfg,
+                             w, scratch, stats, loss_vec, coef, rows, stream, true);
+}

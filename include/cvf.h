@@ -133,7 +133,9 @@ typedef struct cvf_ef_cfg {
   int32_t k;
   int32_t lag_idx;       /* 0: generator (core.py:418-426,438); >0: transfer operator (428,440) */
   int32_t sort_eigvals;  /* core.py:430-434 */
-  int32_t pad_;
+  int32_t iso_metric;    /* generator mode, the 16-frame front launches (cvf_ef16_front, cvf_ef16_front_rows): 1 = the caller vouches for an
+                          * ISOTROPIC metric, a[3b] == a[3b+1] == a[3b+2] for every record atom b, and q = J A J^T g is formed in the
+                          * aligned frame; 0 = the general passes.  (Was padding: zero in every earlier caller.)  Not read elsewhere. */
   double alpha;          /* core.py:455 */
   double beta;           /* core.py:426,438 */
   double dt;             /* core.py:428,440 */
@@ -322,6 +324,21 @@ int cvf_ef16_front_rows(const cvf_mlp_desc* mlp, const float* theta, const float
                         const float* x, int64_t B, const float* a, float* y_tiled, float* saved, float* q_tiled, float* e_tiled,
                         const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats, double* loss_vec, double* coef,
                         const float* rows, void* stream);
+/* ISOTROPIC metric: both front calls once more (same arguments, same outputs) for an `a` that holds ONE coefficient per record
+ * atom, a[3b] == a[3b+1] == a[3b+2] for b < n_rec - ones, or 1 / mass.  Then R a_b R^T = a_b I, and q = J A J^T g and E are formed in
+ * the aligned frame from the features alone: cross products instead of 3x3 products, no rotation, centroid or coordinate read
+ * behind the alignment (the _rows_ form reads no coordinates at all).  The result is that of the general call up to fp32
+ * reassociation; cvf_ef16_front_rows_iso and cvf_ef16_front_iso agree bit for bit.  The library cannot look at `a` (device memory):
+ * the caller answers for the premise, and with an anisotropic `a` the result is wrong.  cvf_ef16_front / cvf_ef16_front_rows with
+ * cfg->iso_metric = 1 are the same launches (what EigenFunctionTask sets); with 0, as in every earlier caller, they keep the general passes. */
+int cvf_ef16_front_iso(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled, const cvf_pp_desc* pp,
+                       const float* x, int64_t B, const float* a, float* y_tiled, float* saved, float* q_tiled, float* e_tiled,
+                       const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats, double* loss_vec, double* coef,
+                       void* stream);
+int cvf_ef16_front_rows_iso(const cvf_mlp_desc* mlp, const float* theta, const float* packed, float* feat_tiled,
+                            const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, float* y_tiled, float* saved,
+                            float* q_tiled, float* e_tiled, const cvf_ef_cfg* cfg, const float* w, double* scratch, double* stats,
+                            double* loss_vec, double* coef, const float* rows, void* stream);
 /* Transfer-operator mode (lag_tau > 0; core.py:403,414: y = model(pp_layer(X)) on the frames and on their lagged partners, then
  * core.py:420-431,440 and loss.backward()) on the same kernels:
  *  cvf_ef16_front_transfer   : x, x_lag [B][n_coord] -> feat_tiled [2T][d_r][64], y_tiled [2T][k][64] (the partners' tiles follow
