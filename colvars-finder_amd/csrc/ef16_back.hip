@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   constexpr int NT = 256, WPB = 4;
   constexpr int kRows = 2 * H + 2 * (H + 1) + 16;   // packed images: reads past an image's rows meet finite values whose products are discarded
   __shared__ __attribute__((aligned(16))) float IMG[kRows * kPitch];
+  __shared__ float PART[4 * (H + 1)];   // the last layer's gradient, one partial row per wave (strip_rows, ef16_common.hpp)
   extern __shared__ float GI[];  // MULTI (a block walks several tiles): its partial gradient of `net`, flat parameter order
   float* SA1 = IMG;
   float* SA2 = SA1 + H * kPitch;
@@ -46,8 +47,14 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform values in SGPRs (see the front kernel)
   const int col = lane & 15, q = lane >> 4, row16 = col, r0 = 4 * q;
   const int fo = 16 * wave + col;   // this lane's frame of the tile
+  const int rowf = 4 * col + q;     // the row whose strip sum this lane keeps (strip_rows: hid_feature(col >> 2, col & 3, q))
   const int net = blockIdx.y, k = args.k, D = mlp.dims[0];
   const int CT1 = (D + 1 + 15) / 16;
+  // A last column tile of the first layer [f ; 1] with 1..4 useful columns (D = 66: features 64, 65 and the bias) does not go to
+  // the matrix cores: its columns are `ncol` strips of H sums over the frames (strip_rows).  CTM column tiles stay matrix tiles.
+  const int c0 = 16 * (CT1 - 1), nfeat = D - c0, ncol = nfeat + 1;   // the last tile's first column, its features, its columns
+  const bool strip = ncol <= 4;
+  const int CTM = strip ? CT1 - 1 : CT1;
   const int gbase = mlp.w_off[net][0];
   const int gspan = mlp.b_off[net][NH] + 1 - gbase;
   float* out = slab + (int64_t)blockIdx.x * mlp.n_params + gbase;   // this block's slab row, this net's span
@@ -105,6 +112,36 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
     acc = outer_half(A1, B1, rt, ct, lane, acc);
     if constexpr (GEN) acc = outer_half(A2, B2, rt, ct, lane, acc);
     return acc;
+  };
+
+  // a strip entry: stored like a tile's (no lane-divergent branch around the store, dead lanes get an offset past the span)
+  auto emit_entry = [&](bool live, int idx, float v) {
+    if (MULTI) {
+      if (live) GI[idx] += v;
+    } else {
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), out_rs, live ? idx * 4 : 0x7ffffff0, 0, 0);
+    }
+  };
+  // the last layer's H weights and bias from the four waves' partials in PART (one wave; behind a block barrier)
+  auto emit_last = [&]() {
+    if (wave == WPB - 1) {   // wave-uniform
+      int i = lane;
+      asm volatile("" : "+v"(i));
+      const bool live = i <= H;
+      const float v = strip_total(PART + (live ? i : H), H + 1);
+      emit_entry(live, i < H ? mlp.w_off[net][NH] - gbase + i : mlp.b_off[net][NH] - gbase, v);
+    }
+  };
+  // the first layer's strip columns from the partials in SB1 ([wave][row][4 columns]; behind a block barrier)
+  auto emit_strip = [&]() {
+    if (strip && 64 * wave < 4 * H) {   // wave-uniform
+      int e = tid;
+      asm volatile("" : "+v"(e));
+      const int o = e >> 2, c = e & 3;
+      const bool live = o < H && c < ncol;
+      const float v = strip_total(SB1 + (o < H ? e : 0), 4 * H);
+      emit_entry(live, c < nfeat ? mlp.w_off[net][0] - gbase + o * D + c0 + c : mlp.b_off[net][0] - gbase + o, v);
+    }
   };
 
   for (int64_t tile = blockIdx.x; tile < args.n_tiles; tile += gridDim.x) {
@@ -189,32 +226,18 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
       }
     }
     CVF_STAMP(11);
-    // ---- last layer (1 x H):  W_L += sum alpha h_{NH} + tdot_{NH} ; b_L += sum alpha
+    // ---- last layer (1 x H):  W_L += sum alpha h_{NH} + tdot_{NH} ; b_L += sum alpha.  One useful row: no matrix tile - every wave
+    // sums its 16 frames in registers and leaves H + 1 partials in PART; they are added and stored behind the first barrier of
+    // the reverse sweep (emit_last).
     {
-      if (q == 0) {
-        SA1[fo] = alpha;
-        if constexpr (GEN) SA2[fo] = 1.0f;
-      }
-      store_image<H, 1, false>(SB1, h[NH - 1], one, lane, fo);
-      if constexpr (GEN) {
-        Vec<H, 1> td;
-        tangent_of<H, 1>(td, h[NH - 1], t[NH - 1]);
-        store_image<H, 1, false>(SB2, td, one, lane, fo);
-      }
-      __syncthreads();
-      for (int ct = wave; ct < CTH; ct += WPB) {
-        const f32x4 acc = outer2(SA1, SB1, SA2, SB2, 0, ct);
-        if (q == 0) {  // output row 0 lives in register 0 of lanes 0..15
-          const int wo = mlp.w_off[net][NH] - gbase, bo = mlp.b_off[net][NH] - gbase;
-          const int i = 16 * ct + row16;
-          if (i <= H) {
-            const int idx = i < H ? wo + i : bo;
-            if (MULTI) GI[idx] += acc[0];
-            else out[idx] = acc[0];
-          }
-        }
-      }
-      __syncthreads();
+      const float pick = strip_rows<H>([&](int rt, int r) {
+        const float hv = h[NH - 1].v[rt][0][r];
+        if constexpr (GEN) return fmaf(alpha, hv, (1.0f - hv * hv) * t[NH - 1].v[rt][0][r]);
+        else return alpha * hv;
+      }, col);
+      const float sa = row_sumf16(alpha);
+      if (col < NG && rowf < H) PART[wave * (H + 1) + rowf] = pick;
+      if (lane == 0) PART[wave * (H + 1) + H] = sa;
     }
     CVF_STAMP(12);
     // ---- reverse sweep
@@ -228,6 +251,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
     // behind the stores (at the top of the next step) waited for the stores' acknowledgements first.
     HFrag<H> tfl;
     float4 bA[4], bB[4];
+    float xs[3] = {0.0f, 0.0f, 0.0f}, qs[3] = {0.0f, 0.0f, 0.0f};   // the frame's features of the strip columns, and its q
     auto request = [&](float4 (&dst)[4], const float* src_tile, int ct) {
       const int i = 16 * ct + row16;
       const float4* p = reinterpret_cast<const float4*>(src_tile + (int64_t)(i < D ? i : D - 1) * CVF_TILE + 4 * q);
@@ -238,6 +262,16 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
       if (l > 0) {
         load_hfrag_u<H>(tfl, pk, L.th(l));
       } else {
+        // (the strip's values first: they are used ahead of bA / bB, and with those eight requests behind them the wait for them
+        //  cannot fall on the acknowledgements of the previous step's stores - a wave without a tile there issues none)
+        if (strip) {   // wave-uniform
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            if (c < nfeat) {
+              xs[c] = f_tile[(int64_t)(c0 + c) * CVF_TILE + fo];
+              if constexpr (GEN) qs[c] = q_tile[(int64_t)(c0 + c) * CVF_TILE + fo];
+            }
+        }
         request(bA, f_tile, wave);
         if constexpr (GEN) request(bB, q_tile, wave);
       }
@@ -286,8 +320,27 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
           const int rt = pr / CTH, ct = pr - rt * CTH;
           emit_tile(l, H, H, rt, ct, outer2(SA1, SB1, SA2, SB2, rt, ct));
         }
+        if (l == NH - 1) emit_last();
         __syncthreads();
       } else {
+        // the strip columns (see `strip`): column c of row o is  sum_f zbar[o] x_c (+ gamma dl[o] q_c), the bias column  sum_f zbar[o].
+        // SB1's rows below H are free in this step (the B operands are in registers): the waves' partials go there.
+        // (unrolled, a wave-uniform branch per column: the wait for x_c / q_c counts the previous step's stores issued behind their
+        //  requests instead of waiting for those stores' acknowledgements, which a loop over c made it do)
+        if (strip) {   // wave-uniform
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if (c < ncol) {   // wave-uniform
+              const float xv = c == nfeat ? 1.0f : xs[c < 3 ? c : 2];
+              const float qv = c == nfeat ? 0.0f : gamma * qs[c < 3 ? c : 2];
+              const float pick = strip_rows<H>([&](int rt, int r) {
+                if constexpr (GEN) return fmaf(zbar.v[rt][0][r], xv, dl.v[rt][0][r] * qv);
+                else return zbar.v[rt][0][r] * xv;
+              }, col);
+              if (col < NG && rowf < H) SB1[(wave * H + rowf) * 4 + c] = pick;
+            }
+          }
+        }
         __syncthreads();
         // one half of the contraction of column tile `ct` for the row tiles rt0, rt0 + rstep, ..: A rows from the LDS image
         // `SA`, B rows in registers; columns: features, then the ones (bias) column when `ones`, zeros past it
@@ -312,13 +365,12 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
             }
           }
         };
-        // column tiles beyond the first four (a fifth, ragged one for D = 66: two features and the bias column) are dealt
-        // by (column tile, row tile) pairs: pair p -> wave p % 4
-        const int extra = (CT1 - WPB) * RTO;
+        // matrix column tiles beyond the first four are dealt by (column tile, row tile) pairs: pair p -> wave p % 4
+        const int extra = (CTM - WPB) * RTO;
         f32x4 acc[RTO];
 #pragma unroll
         for (int rt = 0; rt < RTO; ++rt) acc[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (wave < CT1) {   // wave-uniform
+        if (wave < CTM) {   // wave-uniform
           half0(acc, SA1, bA, wave, 0, 1, true);
           if (wave < extra) request(bA, f_tile, WPB + wave / RTO);   // the extra pair's rows, behind the second half
           if constexpr (GEN) half0(acc, SA2, bB, wave, 0, 1, false);
@@ -327,7 +379,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
         }
         for (int pr = wave; pr < extra; pr += WPB) {
           const int ct = WPB + pr / RTO, rt = pr % RTO;
-          if (pr != wave || wave >= CT1) request(bA, f_tile, ct);
+          if (pr != wave || wave >= CTM) request(bA, f_tile, ct);
           if constexpr (GEN) request(bB, q_tile, ct);
 #pragma unroll
           for (int r_ = 0; r_ < RTO; ++r_) acc[r_] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -337,6 +389,8 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
           for (int r_ = 0; r_ < RTO; ++r_)
             if (r_ == rt) emit_tile(0, H, D, r_, ct, acc[r_]);
         }
+        emit_strip();
+        if (NH == 1) emit_last();
         __syncthreads();
       }
     }

@@ -28,6 +28,37 @@ __device__ __forceinline__ double quad_sumd16(double v) {
   return v;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Strips of a weight gradient too thin for a matrix tile (the backward kernel's 1 x (H + 1) last layer; a last column tile
+// of the first layer with <= 4 useful columns).  A wave holds its 16 frames' hidden vectors in the acc layout (lane = (frame
+// `col`, row group q), register j = 4 rt + r = row 4 j + q), so a product summed over the wave's frames is a sum over the 16
+// lanes of a DPP row: a fixed tree, no LDS.  The four waves' partial sums then meet in a small LDS area behind a barrier the
+// kernel has anyway and are added in wave order - the same order on every run.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float row_sumf16(float v) {   // every lane of the row gets the sum
+  v = quad_sumf16(v);
+  v += dpp_movf<0x141, 0xf>(v);   // row_half_mirror: the other quad of the lane's eight
+  v += dpp_movf<0x140, 0xf>(v);   // row_mirror: the other eight
+  return v;
+}
+// val(rt, r): the lane's value of row 4 (4 rt + r) + q for its frame.  Each of the NG rows is summed over the wave's frames, one
+// after the other (one live partial at a time); lane `col == j` keeps the sum of ITS row 4 j + q, so a strip leaves the wave in
+// one LDS write per column
+template <int H, class F>
+__device__ __forceinline__ float strip_rows(F&& val, int col) {
+  float pick = 0.0f;
+#pragma unroll
+  for (int j = 0; j < Hid<H>::NG; ++j) {
+    const float s = row_sumf16(val(j >> 2, j & 3));
+    pick = col == j ? s : pick;
+  }
+  return pick;
+}
+// the four waves' partials of one value (P[wave * stride]), in wave order
+__device__ __forceinline__ float strip_total(const float* P, int stride) {
+  return ((P[0] + P[stride]) + P[2 * stride]) + P[3 * stride];
+}
+
 struct Front16Lds {   // offsets in floats
   int ref, a, aux, w, rs, y, e, feat, g, total;
 };
