@@ -222,6 +222,10 @@ __global__ __launch_bounds__(256, 2) void ae_mfma_kernel(cvf_mlp_desc mlp, const
     for (int i = lay.tail_off / 4 + tid; i < lay.total / 4; i += 256) l4[i] = z4;
 #pragma unroll 4
     for (int i = lay.skip0 + tid; i < mlp.n_params; i += 256) WL[i] = theta[i];
+    // the up to 3 floats between the last parameter and tail_off (theta's length rounded up to 4): the k-steps that read rows
+    // past zbar reach them too (6 -> 16 -> 2 -> 48 -> 8, 682 parameters: rows 58 of the 48-row layer, columns 2 and 3), and
+    // what an earlier kernel left in LDS there - a NaN, an Inf - times the 0 of the A operand is NaN
+    if (tid < 3 && mlp.n_params + tid < lay.skip0 + lay.tail_off - lay.w_off) WL[mlp.n_params + tid] = 0.0f;
   }
   __syncthreads();
   for (int l = 1; l < L; ++l)

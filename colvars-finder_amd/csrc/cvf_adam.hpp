@@ -6,19 +6,26 @@ struct AdamDev {           // device-side view of cvf_adam_args
   float* theta;
   float* m;
   float* v;
-  float lr, b1, b2, eps;
+  float lr, b2, eps;
+  float omb1, omb2;        // 1 - beta1, 1 - beta2: rounded from the host's doubles (1.0f - (float)0.999 is 1.3e-5 off 0.001)
+  double b1d, b2d;         // the betas as the host gave them, for the bias corrections 1 - beta^t
   const int32_t* step;     // number t >= 1 of the current step (advanced by the gradient kernel)
   float* packed;           // MFMA fragment copy to refresh, or nullptr
   const float* lr_dev;     // device scalar overriding `lr` (a captured hipGraph then follows the host's learning rate), or nullptr
 };
+
+inline AdamDev adam_dev(float* theta, float* m, float* v, double lr, double beta1, double beta2, double eps, const int32_t* step,
+                        float* packed, const float* lr_dev) {
+  return AdamDev{theta, m, v, (float)lr, (float)beta2, (float)eps, (float)(1.0 - beta1), (float)(1.0 - beta2), beta1, beta2, step, packed, lr_dev};
+}
 
 struct AdamScalars {
   float step_size, bc2_sqrt;
 };
 __device__ __forceinline__ AdamScalars adam_scalars(const AdamDev& a) {
   const int t = *a.step;
-  const double bc1 = 1.0 - pow((double)a.b1, (double)t);
-  const double bc2 = 1.0 - pow((double)a.b2, (double)t);
+  const double bc1 = 1.0 - pow(a.b1d, (double)t);
+  const double bc2 = 1.0 - pow(a.b2d, (double)t);
   const float lr = a.lr_dev != nullptr ? *a.lr_dev : a.lr;
   return AdamScalars{(float)((double)lr / bc1), (float)sqrt(bc2)};
 }
@@ -29,8 +36,8 @@ __device__ __forceinline__ void adam_apply(const AdamDev& a, const AdamScalars& 
                                            float m0, float v0, float th0) {
   // (explicit fused multiply-adds: left to the compiler, the contraction of these expressions depends on the surrounding
   //  kernel, and the stand-alone and the fused update must agree bit for bit)
-  const float mi = fmaf(g - m0, 1.0f - a.b1, m0);
-  const float g2 = ((1.0f - a.b2) * g) * g;
+  const float mi = fmaf(g - m0, a.omb1, m0);
+  const float g2 = (a.omb2 * g) * g;
   const float vi = fmaf(a.b2, v0, g2);
   a.m[i] = mi;
   a.v[i] = vi;

@@ -41,7 +41,8 @@ struct PackTab {
   int bend[CVF_MAX_NETS];   // last parameter of net n
 };
 // one thread, constant indices only (scalar loads from the kernel arguments); callers follow with a barrier
-__device__ __forceinline__ void pack_tab_fill(PackTab& t, const cvf_mlp_desc& mlp) {
+// (__host__ as well, like pack_scatter: tools/pack_host.hip runs both on the CPU for tests/test_pack_host.py)
+__host__ __device__ __forceinline__ void pack_tab_fill(PackTab& t, const cvf_mlp_desc& mlp) {
   t.n_nets = mlp.n_nets;
   t.NH = mlp.n_layers - 1;
   t.H = mlp.dims[1];
@@ -57,7 +58,7 @@ __device__ __forceinline__ void pack_tab_fill(PackTab& t, const cvf_mlp_desc& ml
   }
 }
 // scatter parameter p (new value v) of the flat buffer into its fragment slots
-__device__ __forceinline__ void pack_scatter(const PackTab& t, int p, float v, float* __restrict__ packed) {
+__host__ __device__ __forceinline__ void pack_scatter(const PackTab& t, int p, float v, float* __restrict__ packed) {
   const int NH = t.NH, H = t.H, D = t.D;
   const PackLayout L = pack_layout(H, NH, D);
   for (int n = 0; n < t.n_nets; ++n) {

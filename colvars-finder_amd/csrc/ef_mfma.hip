@@ -1970,8 +1970,8 @@ static int slab_reduce_ll(const float* slab, int64_t n_rows, int64_t n_params, f
     CVF_REQUIRE(adam->theta && adam->m && adam->v && adam->step_count, "cvf_slab_reduce: incomplete adam arguments");
     CVF_REQUIRE(adam->packed == nullptr || (adam->mlp != nullptr && adam->mlp->n_params == n_params),
                 "cvf_slab_reduce: packed buffer needs its mlp desc");
-    ad = AdamDev{adam->theta, adam->m, adam->v, (float)adam->lr, (float)adam->beta1, (float)adam->beta2, (float)adam->eps,
-                 adam->step_count, adam->packed, adam->lr_dev};
+    ad = adam_dev(adam->theta, adam->m, adam->v, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step_count, adam->packed,
+                  adam->lr_dev);
     if (adam->packed) md = *adam->mlp;
   }
   const unsigned nb = (unsigned)((n_params + kSlabPX - 1) / kSlabPX) + (pair_partial != nullptr ? 1u : 0u);

@@ -300,7 +300,7 @@ extern "C" int cvf_adam_step(float* theta, const float* grad, float* m, float* v
   cvf_mlp_desc none = {};
   const cvf_mlp_desc& md = packed ? *mlp : none;
   const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-  AdamDev ad{theta, m, v, (float)lr, (float)beta1, (float)beta2, (float)eps, step_count, packed, lr_dev};
+  const AdamDev ad = adam_dev(theta, m, v, lr, beta1, beta2, eps, step_count, packed, lr_dev);
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ad, grad, n, md);
   return cvf_check_launch("adam_kernel");
 }
