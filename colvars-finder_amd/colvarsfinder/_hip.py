@@ -191,6 +191,13 @@ _SIGNATURES = {
                                C.c_void_p]),
 }
 
+# the per-layer route of RegAutoEncoderTask takes the argument lists of the fused calls
+_SIGNATURES["cvf_regae_route"] = (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.POINTER(C.c_int64)])
+_SIGNATURES["cvf_regae_general_supported"] = (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.c_int])
+_SIGNATURES["cvf_regae_general_scratch_floats"] = _SIGNATURES["cvf_regae_scratch_floats"]
+_SIGNATURES["cvf_regae_general_forward"] = _SIGNATURES["cvf_regae_forward"]
+_SIGNATURES["cvf_regae_general_backward"] = _SIGNATURES["cvf_regae_backward"]
+_SIGNATURES["cvf_regae_general_backward_reuse"] = _SIGNATURES["cvf_regae_backward"]
 # the isotropic-metric forms of the two front calls take the arguments of their general twins
 _SIGNATURES["cvf_ef16_front_iso"] = _SIGNATURES["cvf_ef16_front"]
 _SIGNATURES["cvf_ef16_front_rows_iso"] = _SIGNATURES["cvf_ef16_front_rows"]

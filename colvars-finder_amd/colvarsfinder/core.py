@@ -1955,7 +1955,10 @@ class RegAutoEncoderTask(TrainingTask):
     A step is three launches + the reduction: ``cvf_regae_forward`` (one chain: encoder, then decoder and regulariser
     nets side by side; y on the batch's frames and on their lagged partners, reconstruction error), ``cvf_ef_stats``
     (batch sums, loss tail, d loss / d sum - the eigenfunction task's own kernel), ``cvf_regae_backward`` (forward
-    again, output gradients, parameter gradient on the matrix cores, fixed-order reduction, Adam).
+    again, output gradients, parameter gradient on the matrix cores, fixed-order reduction, Adam).  A merged chain whose
+    parameters and activations do not fit that kernel's 160 KiB of LDS runs the same three calls layer by layer instead
+    (``cvf_regae_general_*``: widths up to 4096 units, the same outputs); a chain past both routes is refused with
+    NotImplementedError at construction.
     """
 
     def __init__(self, traj_obj, pp_layer, model, model_path, eig_weights=[], learning_rate=0.01, load_model_filename=None,
@@ -1991,6 +1994,9 @@ class RegAutoEncoderTask(TrainingTask):
         # an inner EigenFunctionTask (generator-mode regulariser, gradient-norm penalty eta[0]) add their batch sums across the
         # ranks too and leave their gradient shares in the flat gradient, which is summed once, at the end of the step.
         self.init_model_and_optimizer()
+        self._n_enc_layers = len([m for m in self.model.encoder if isinstance(m, torch.nn.Linear)])
+        # the chain goes per layer (cvf_regae_general_*): decided once, where cvf_regae_route refuses it
+        self._general = self._needs_general()
         # --- data: the feature trajectory r(x) of every frame, once (the layer has no parameters), resident in HBM
         traj = _HostFrames(traj_obj.trajectory).all()
         self.tot_dim = int(np.prod(traj.shape[1:]))
@@ -2030,7 +2036,6 @@ class RegAutoEncoderTask(TrainingTask):
         ecfg = _hip.EFCfg()                      # batch sums of the latent vector (the generator-mode layout, E unused)
         ecfg.k, ecfg.lag_idx, ecfg.sort_eigvals, ecfg.alpha, ecfg.beta, ecfg.dt = self.k, 0, 0, 0.0, 1.0, 1.0
         self._ecfg = ecfg
-        self._n_enc_layers = len([m for m in self.model.encoder if isinstance(m, torch.nn.Linear)])
         self._ws = {}
         self._enc_grad = _EncGradPenalty(self) if self.eta[0] > self._eps else None   # (raises here when the encoder does not fit)
         # generator-mode regulariser (lag_tau_reg = 0): needs the coordinates themselves (its derivative runs through r(x))
@@ -2050,6 +2055,19 @@ class RegAutoEncoderTask(TrainingTask):
                 print(f'model file not found: {self.load_model_filename}')
         self._flat = _RegFlatParams(self.model, self.device, self.freeze_encoder)
         self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
+
+    def _needs_general(self):
+        """False where the fused chain kernel takes the merged chain (cvf_regae_route: a 64-frame tile's chain in LDS), True where
+        only the per-layer route of csrc/regae_general.hip does - then for every pass, loss-only ones included; a chain past both
+        is refused here, at construction.  (The layout with a gradient is the larger one: where it fits, the forward pass does.)"""
+        lib, fl = _hip.lib(), self._flat
+        if lib.cvf_regae_route(fl.desc, 1, None) >= 0:
+            return False
+        fused = lib.cvf_last_error().decode()
+        if lib.cvf_regae_general_supported(fl.desc, self.num_reg, self._n_enc_layers) != 1:
+            raise NotImplementedError("RegAutoEncoderTask: no HIP route trains this chain (%s; %s)"
+                                      % (fused, lib.cvf_last_error().decode()))
+        return True
 
     def _features(self, X):
         if self._foreign_pp:
@@ -2077,8 +2095,9 @@ class RegAutoEncoderTask(TrainingTask):
         if ws is None:
             lib, K, dev = _hip.lib(), max(self.num_reg, 1), self.device
             T = _hip.ntiles(B)
+            size = lib.cvf_regae_general_scratch_floats if self._general else lib.cvf_regae_scratch_floats
             ws = dict(
-                scratch=torch.empty(lib.cvf_regae_scratch_floats(self._flat.desc, B), device=dev, dtype=torch.float32),
+                scratch=torch.empty(size(self._flat.desc, B), device=dev, dtype=torch.float32),
                 y=torch.zeros(2 * T * K * 64, device=dev, dtype=torch.float32),
                 out2=torch.zeros(3, device=dev, dtype=torch.float64),
                 stats=torch.zeros(lib.cvf_ef_nstats(K, 1), device=dev, dtype=torch.float64),
@@ -2116,7 +2135,12 @@ class RegAutoEncoderTask(TrainingTask):
         eta1 = float(self.eta[1]) if self.eta[1] > self._eps else 0.0
         eta2 = float(self.eta[2]) if self.eta[2] > self._eps else 0.0
         # (with a gradient to follow, the statistics pass leaves its activations in the scratch buffer for the gradient pass)
-        self._call("cvf_regae_forward", lib.cvf_regae_forward_keep if with_grad else lib.cvf_regae_forward, fl.desc, P(fl.theta),
+        if self._general:
+            fwd = fwd_keep = lib.cvf_regae_general_forward
+            bwd_reuse = lib.cvf_regae_general_backward_reuse
+        else:
+            fwd, fwd_keep, bwd_reuse = lib.cvf_regae_forward, lib.cvf_regae_forward_keep, lib.cvf_regae_backward_reuse
+        self._call("cvf_regae_forward", fwd_keep if with_grad else fwd, fl.desc, P(fl.theta),
                    P(feat), P(idx), B, lag_ae, lag_reg if use_reg else 0, K, P(w), P(ws["scratch"]), P(ws["y"]), self._n_enc_layers,
                    P(ws["enc"]) if use_enc else None, P(ws["out2"]), _hip.stream())
         if dp:
@@ -2152,7 +2176,7 @@ class RegAutoEncoderTask(TrainingTask):
                     _dist.allreduce_sum_(wsum_t)
                 wsum = float(wsum_t)
             adam = self.optimizer.fused_args() if advance and eg is None and gen is None and not dp else None   # (their gradients are added before the update)
-            self._call("cvf_regae_backward", lib.cvf_regae_backward_reuse, fl.desc, P(fl.theta), P(feat), P(idx), B, lag_ae,
+            self._call("cvf_regae_backward", bwd_reuse, fl.desc, P(fl.theta), P(feat), P(idx), B, lag_ae,
                        lag_reg if use_reg else 0, K, P(w), P(w_lag) if use_reg else None, alpha / wsum,
                        float(self.gamma[0]) if use_reg else 0.0, P(ws["y"]) if use_reg else None,
                        P(ws["coef"]) if use_reg else None, self._n_enc_layers, P(ws["ecoef"]) if use_enc else None,

@@ -1208,6 +1208,19 @@ extern "C" int64_t cvf_regae_scratch_floats(const cvf_mlp_desc* mlp, int64_t B) 
   return regae_hand_offset(mlp, B) + 2 * cvf_ntiles(B) * regae_hand_rows(mlp) * CVF_TILE;
 }
 
+// The LDS layout regae_launch takes for this chain and pass - host arithmetic only, no launch: 1 / 2 = ae_mfma_kernel on its roomy
+// / tight layout (ae_mlayout), negative = refused (cvf_last_error() has the text); *lds_bytes (may be NULL) receives the launch's
+// dynamic LDS.  regae_launch decides by calling this function: there is no second copy of the rule.
+extern "C" int cvf_regae_route(const cvf_mlp_desc* mlp, int with_grad, int64_t* lds_bytes) {
+  CVF_REQUIRE(mlp, "cvf_regae: bad argument");
+  CVF_REQUIRE(mlp->n_nets == 1 && mlp->n_layers >= 2 && mlp->n_layers <= CVF_MAX_LAYERS, "cvf_regae: one chain expected");
+  const AeMLayout lay = ae_mlayout(*mlp, with_grad != 0);
+  const size_t lds = (size_t)lay.total * sizeof(float);
+  if (lds_bytes) *lds_bytes = (int64_t)lds;
+  CVF_REQUIRE(lds <= 160 * 1024, "cvf_regae: the chain needs %zu B of LDS per workgroup (> 160 KiB)", lds);
+  return lay.total != ae_mlayout_of(*mlp, with_grad != 0, false).total ? 2 : 1;
+}
+
 static int regae_launch(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
                         const float* w, double mse_scale, bool with_grad, float* scratch, int32_t* step_count, AeReg reg,
                         int* grid_out, hipStream_t s, bool handoff = false) {
@@ -1223,9 +1236,9 @@ static int regae_launch(const cvf_mlp_desc* mlp, const float* theta, const float
     CVF_REQUIRE(mlp->act[reg.enc_layer - 1] == 0, "cvf_regae: the encoder's last layer must have no activation");
     CVF_REQUIRE(reg.k_enc <= CVF_MAX_NETS, "cvf_regae: latent width %d > %d", reg.k_enc, CVF_MAX_NETS);
   }
-  const AeMLayout lay = ae_mlayout(*mlp, with_grad);
-  const size_t lds = (size_t)lay.total * sizeof(float);
-  CVF_REQUIRE(lds <= 160 * 1024, "cvf_regae: the chain needs %zu B of LDS per workgroup (> 160 KiB)", lds);
+  int64_t lds_bytes = 0;
+  if (cvf_regae_route(mlp, with_grad, &lds_bytes) < 0) return -1;
+  const size_t lds = (size_t)lds_bytes;
   reg.T = cvf_ntiles(B);
   reg.n_tiles = (reg.K > 0 && reg.lag_in > 0) ? 2 * reg.T : reg.T;
   const int G = regae_grid(reg.n_tiles);

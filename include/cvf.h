@@ -485,6 +485,43 @@ int cvf_regae_backward_reuse(const cvf_mlp_desc* mlp, const float* theta, const 
                        double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, const double* enc_coef,
                        float* scratch, float* grad, const float* mask, int32_t* step_count, const cvf_adam_args* adam,
                        void* stream);
+/* The LDS layout cvf_regae_forward / cvf_regae_backward take for (mlp, with_grad) - host arithmetic only, no launch: 1 / 2 = the
+ * chain kernel (ae_mfma_kernel) on its roomy / tight layout, negative = refused (more than 160 KiB of LDS; cvf_last_error()).
+ * lds_bytes (may be NULL): the launch's dynamic LDS.  The four calls above decide by this function. */
+int cvf_regae_route(const cvf_mlp_desc* mlp, int with_grad, int64_t* lds_bytes);
+
+/* --- RegAutoEncoderTask chains of ANY width (csrc/regae_general.hip): the calls for the merged chains
+ * cvf_regae_route refuses - one launch per layer and pass over all 64-frame tiles (the kernels of cvf_ae_general_step), the
+ * activations handed over through `scratch`.  One chain of 2 to CVF_MAX_LAYERS layers with dims[n_layers] == dims[0] + K,
+ * 0 <= K <= CVF_MAX_NETS, inner widths 1 to 4096, d0 <= 65536, at most 65535 blocks of 64 x 64 weights in a layer, any act code
+ * of this header, parameters that fill the flat buffer (the merged layers are dense: theta holds zeros off their blocks, `mask`
+ * keeps them zero), 1 <= n_enc_layers < n_layers, no activation on the encoder's last layer, a latent vector of at most
+ * CVF_MAX_NETS entries.  No atomics: the same inputs give the same bits.
+ *  cvf_regae_general_supported     : 1, or 0 with the reason in cvf_last_error().
+ *  cvf_regae_general_scratch_floats: floats of `scratch` (8-byte aligned) for a batch of B frames, T = ceil(B / 64): always laid
+ *                                    out for 2 T tiles - 128 T (sum of dims[0..n_layers-1] + 2 max(dims[1..n_layers])), R n_params
+ *                                    slab rows with R = min(2 T, 256, 128 MiB / (4 n_params)) >= 1, rounded up to even, + 4 T for
+ *                                    the base tiles' loss pairs; 0 for a chain whose sizes are refused.
+ *  cvf_regae_general_forward       : arguments and outputs of cvf_regae_forward; it always leaves its activation images in
+ *                                    `scratch` (there is no _keep twin).
+ *  cvf_regae_general_backward      : arguments and outputs of cvf_regae_backward; runs the chain forward again.
+ *  cvf_regae_general_backward_reuse: the same from the images cvf_regae_general_forward left in `scratch` on the same (theta,
+ *                                    rows, lags, K) - once: the call consumes them. */
+int cvf_regae_general_supported(const cvf_mlp_desc* mlp, int K, int n_enc_layers);
+int64_t cvf_regae_general_scratch_floats(const cvf_mlp_desc* mlp, int64_t B);
+int cvf_regae_general_forward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                      int64_t lag_target, int64_t lag_input, int K, const float* w, float* scratch, float* y_tiled,
+                      int n_enc_layers, float* enc_tiled, double* out2, void* stream);
+int cvf_regae_general_backward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                       int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag, double mse_scale,
+                       double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, const double* enc_coef,
+                       float* scratch, float* grad, const float* mask, int32_t* step_count, const cvf_adam_args* adam,
+                       void* stream);
+int cvf_regae_general_backward_reuse(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                       int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag, double mse_scale,
+                       double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, const double* enc_coef,
+                       float* scratch, float* grad, const float* mask, int32_t* step_count, const cvf_adam_args* adam,
+                       void* stream);
 /* latent penalties from the latent vector's batch sums (cvf_ef_stats layout [W, S1(k), S2(i<=j), ..]):
  * terms = {sum_j (var_j - 1)^2, sum_{i<j} cov_ij^2} (core.py:934, 966); enc_coef [k + k*k] for cvf_regae_backward */
 int cvf_regae_enc_loss(const double* stats, int k, double eta1, double eta2, double* terms, double* enc_coef, void* stream);
