@@ -35,6 +35,9 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   constexpr int RTO = (H + 15) / 16;      // row tiles of an H-row image (natural order)
   constexpr int CTH = (H + 1 + 15) / 16;  // column tiles of [h ; 1]
   constexpr int NT = 256, WPB = 4;
+  // a second row tile with 1..4 useful rows (H = 20 among the instances) goes to the matrix cores as 4x4x1 blocks, which have no
+  // padding rows and cost a quarter of a 16x16x4 instruction each; every other instance compiles to what it was
+  constexpr bool TAIL4 = RTO == 2 && H % 16 >= 1 && H % 16 <= 4;
   constexpr int kRows = 2 * H + 2 * (H + 1) + 16;   // packed images: reads past an image's rows meet finite values whose products are discarded
   __shared__ __attribute__((aligned(16))) float IMG[kRows * kPitch];
   __shared__ float PART[4 * (H + 1)];   // the last layer's gradient, one partial row per wave (strip_rows, ef16_common.hpp)
@@ -316,9 +319,39 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
         init_bias<H, 1>(hbar, nullptr, q);
         hidden_mul<H, 1>(hbar, tfl, zbar);
         request_step(l - 1);
-        for (int pr = wave; pr < RTO * CTH; pr += WPB) {
-          const int rt = pr / CTH, ct = pr - rt * CTH;
-          emit_tile(l, H, H, rt, ct, outer2(SA1, SB1, SA2, SB2, rt, ct));
+        if constexpr (TAIL4) {
+          // Only tile (0, 0) is full.  The rest of the H x (H + 1) gradient is four jobs of sixteen 4x4x1 blocks each (outer_half44):
+          //   R1  rows 16.. x columns 0..15      R2  rows 16.. x columns 16..23 (column groups 16.., 20..; half the blocks idle)
+          //   R3a rows 0..15 x columns 16..19    R3b rows 0..15 x columns 20..23 (the bias column and three dead ones)
+          // i.e. 32 + 4 x 8 quarter-cost instructions per half instead of 4 x 16.  Role 0 has the full tile, role 1 R1 and R2,
+          // role 2 R3a, role 3 R3b; the roles move by two waves from layer to layer, so that over two layers no wave (and no
+          // SIMD, if wave w of every resident block sits on the same one) has the full tile twice.
+          const int role = (wave + 2 * (l & 1)) & 3;   // wave-uniform
+          if (role == 0) {
+            emit_tile(l, H, H, 0, 0, outer2(SA1, SB1, SA2, SB2, 0, 0));
+          } else {
+            const int g = col >> 2, m = lane & 3;
+            const int wo = mlp.w_off[net][l] - gbase, bo = mlp.b_off[net][l] - gbase;
+            // one job: the lane's rows of the A and B images -> entry (o, i) in the lanes of DPP row q (rows_sum_scatter)
+            auto job = [&](int arow, int brow, int o, int i, bool live) {
+              f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+              acc = outer_half44(SA1, arow, SB1, brow, lane, acc);
+              if constexpr (GEN) acc = outer_half44(SA2, arow, SB2, brow, lane, acc);
+              const float v = rows_sum_scatter(acc);
+              asm volatile("" : "+v"(o));   // (opaque, as emit_tile's row)
+              live = live && o < H && i <= H;
+              emit_entry(live, i < H ? wo + o * H + i : bo + o, v);
+            };
+            const bool low = role == 1;                       // rows 16.. (R1, then R2) or rows 0..15 (R3a / R3b)
+            const int cb = role == 3 ? 20 : 16;               // R3's first column
+            job(low ? 16 + m : 4 * g + m, low ? 4 * g + m : cb + m, low ? 16 + q : 4 * g + q, low ? 4 * g + m : cb + m, true);
+            if (low) job(16 + m, 16 + 4 * (g & 1) + m, 16 + q, 16 + 4 * (g & 1) + m, g < 2);
+          }
+        } else {
+          for (int pr = wave; pr < RTO * CTH; pr += WPB) {
+            const int rt = pr / CTH, ct = pr - rt * CTH;
+            emit_tile(l, H, H, rt, ct, outer2(SA1, SB1, SA2, SB2, rt, ct));
+          }
         }
         if (l == NH - 1) emit_last();
         __syncthreads();
@@ -370,12 +403,43 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
         f32x4 acc[RTO];
 #pragma unroll
         for (int rt = 0; rt < RTO; ++rt) acc[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (wave < CTM) {   // wave-uniform
-          half0(acc, SA1, bA, wave, 0, 1, true);
-          if (wave < extra) request(bA, f_tile, WPB + wave / RTO);   // the extra pair's rows, behind the second half
-          if constexpr (GEN) half0(acc, SA2, bB, wave, 0, 1, false);
+        // TAIL4: the same half for the 1..4 useful rows of row tile 1 as sixteen 4x4x1 blocks (rows_sum_scatter, ef16_common.hpp).
+        // The B registers are read as they are: lane (c, q) holds feature 16 ct + c at frames 16 j + 4 q + e, i.e. column lane & 3
+        // of block (q, c >> 2); the A operand of that block is rows 16 + (lane & 3) at the same frames.
+        auto tail0 = [&](f32x4& tacc, const float* SA, const float4 (&b)[4], int ct, bool ones) {
+          const int i = 16 * ct + row16;
+          const float pad = (ones && i == D) ? 1.0f : 0.0f;
+          const float4* a1 = reinterpret_cast<const float4*>(SA + (16 + (lane & 3)) * kPitch + 4 * q);
+          float4 av[4];
 #pragma unroll
-          for (int rt = 0; rt < RTO; ++rt) emit_tile(0, H, D, rt, wave, acc[rt]);
+          for (int j = 0; j < 4; ++j) av[j] = a1[4 * j];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            tacc = mfma1(av[j].x, i < D ? b[j].x : pad, tacc);
+            tacc = mfma1(av[j].y, i < D ? b[j].y : pad, tacc);
+            tacc = mfma1(av[j].z, i < D ? b[j].z : pad, tacc);
+            tacc = mfma1(av[j].w, i < D ? b[j].w : pad, tacc);
+          }
+        };
+        if (wave < CTM) {   // wave-uniform
+          f32x4 tacc = {0.0f, 0.0f, 0.0f, 0.0f};
+          half0(acc, SA1, bA, wave, 0, TAIL4 ? RTO : 1, true);
+          if constexpr (TAIL4) tail0(tacc, SA1, bA, wave, true);
+          if (wave < extra) request(bA, f_tile, WPB + wave / RTO);   // the extra pair's rows, behind the second half
+          if constexpr (GEN) {
+            half0(acc, SA2, bB, wave, 0, TAIL4 ? RTO : 1, false);
+            if constexpr (TAIL4) tail0(tacc, SA2, bB, wave, false);
+          }
+#pragma unroll
+          for (int rt = 0; rt < (TAIL4 ? 1 : RTO); ++rt) emit_tile(0, H, D, rt, wave, acc[rt]);
+          if constexpr (TAIL4) {   // DPP row q holds row 16 + q of the lane's column
+            const float v = rows_sum_scatter(tacc);
+            int o = 16 + q;
+            asm volatile("" : "+v"(o));
+            const int i = 16 * wave + row16;
+            const bool isw = o < H && i < D, isb = o < H && i == D;
+            emit_entry(isw || isb, isw ? mlp.w_off[net][0] - gbase + o * D + i : mlp.b_off[net][0] - gbase + (o < H ? o : 0), v);
+          }
         }
         for (int pr = wave; pr < extra; pr += WPB) {
           const int ct = WPB + pr / RTO, rt = pr % RTO;

@@ -59,6 +59,26 @@ __device__ __forceinline__ float strip_total(const float* P, int stride) {
   return ((P[0] + P[stride]) + P[2 * stride]) + P[3 * stride];
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Tiles with 1..4 useful rows (rows 16..19 at H = 20) as 4x4x1 blocks (mfma1): the wave's sixteen blocks are (frame set
+// q = lane >> 4) x (column group (lane & 15) >> 2), so register r of lane (c, q) is the partial of entry (row r, column c)
+// over frame set q and the four q (lanes l, l ^ 16, l ^ 32, l ^ 48) remain to be added.  Two half-wave swaps and one row
+// swap do it for the four registers at once, in the fixed order (q0 + q2) + (q1 + q3); the lanes of DPP row q return the
+// total of register q - every lane has one entry to store.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float rows_sum_scatter(const f32x4& x) {
+  auto swap_add = [](auto swapped) {
+    const unsigned a = swapped[0], b = swapped[1];   // (by value, for the same reason)
+    return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+  };
+  const float x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3];   // (by value: see emit_tile on bit casts of vector elements)
+  // lanes 0..31: the first operand's two halves added, lanes 32..63: the second's
+  const float s02 = swap_add(__builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x0), __builtin_bit_cast(unsigned, x2), false, false));
+  const float s13 = swap_add(__builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, x3), false, false));
+  // rows 0, 2: s02's row pair added, rows 1, 3: s13's
+  return swap_add(__builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, s02), __builtin_bit_cast(unsigned, s13), false, false));
+}
+
 struct Front16Lds {   // offsets in floats
   int ref, a, aux, w, rs, y, e, feat, g, total;
 };

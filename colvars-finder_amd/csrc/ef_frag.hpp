@@ -14,6 +14,11 @@ constexpr int kPitch = 68;   // multiple of 4: every image row is 16-byte aligne
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
+// sixteen independent 4x4 outer products, one per group of four lanes (block b = lane >> 2): a = A_b[lane & 3], b = B_b[lane & 3],
+// register r of lane 4 b + j += A_b[r] B_b[j].  8 matrix-pipe cycles against the 32 of mfma4 (tools/mfma4x4_probe.hip).
+__device__ __forceinline__ f32x4 mfma1(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
+}
 
 template <int H>
 struct Hid {
@@ -413,6 +418,30 @@ __device__ __forceinline__ f32x4 outer_half(const float* __restrict__ A, const f
     acc = mfma4(av[j].y, bv[j].y, acc);
     acc = mfma4(av[j].z, bv[j].z, acc);
     acc = mfma4(av[j].w, bv[j].w, acc);
+  }
+  return acc;
+}
+// Sixteen 4x4 blocks of a weight gradient over the block's 64 frames (mfma1): block (frame set kq = lane >> 4, group
+// g = (lane & 15) >> 2) multiplies four rows of A by four rows of B over the 16 frames of outer_half's k-slot kq; the lane
+// brings row `arow` of A and row `brow` of B, which the caller derives from (g, lane & 3).  Register r of the lane is then the
+// partial of (the block's A row r) x (the lane's B row) over frame set kq; the four kq remain to be added.
+__device__ __forceinline__ f32x4 outer_half44(const float* __restrict__ A, int arow, const float* __restrict__ B, int brow,
+                                              int lane, f32x4 acc) {
+  const int kq = lane >> 4;
+  const float4* a = reinterpret_cast<const float4*>(A + arow * kPitch + 4 * kq);
+  const float4* b = reinterpret_cast<const float4*>(B + brow * kPitch + 4 * kq);
+  float4 av[4], bv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    av[j] = a[4 * j];
+    bv[j] = b[4 * j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc = mfma1(av[j].x, bv[j].x, acc);
+    acc = mfma1(av[j].y, bv[j].y, acc);
+    acc = mfma1(av[j].z, bv[j].z, acc);
+    acc = mfma1(av[j].w, bv[j].w, acc);
   }
   return acc;
 }
