@@ -185,6 +185,10 @@ _SIGNATURES = {
     "cvf_regae_loss_row": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double,
                                      C.c_double, C.c_void_p, C.c_void_p]),
     "cvf_mlp_eval_rows": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cvf_cv_nets_supported": (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.c_int]),
+    "cvf_cv_nets_scratch_floats": (C.c_int64, [C.POINTER(MLPDesc), C.c_int, C.c_int64, C.c_int]),
+    "cvf_cv_nets_eval": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvf_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_double,
                                 C.c_double, C.c_double, C.c_void_p, C.POINTER(MLPDesc), C.c_void_p, C.c_void_p]),
     "cvf_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.POINTER(MLPDesc), C.c_void_p,

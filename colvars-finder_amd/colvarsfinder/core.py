@@ -42,6 +42,7 @@ import ctypes
 
 from . import _dist, _hip
 from .nn import AutoEncoder, EigenFunctions, RegAutoEncoder, RegModel, mlp_layout  # noqa: F401
+from .nn import _strict_chain_layers
 from .pp import AlignFeatureLayer, FactoredMetric, identity_desc, module_features
 
 try:  # logging sink of the reference (core.py:50,143); optional here
@@ -166,8 +167,10 @@ class _CVModel(torch.nn.Sequential):
         ``xi [B, k]`` and ``J [B, k, *frame_shape]``, ``J[b, i] = d xi_i / d x`` at frame ``b``, on ``X``'s device and in its
         floating-point type, without an autograd graph.  Columns follow the model's outputs (EigenFunctionTask: ``cvec``).
 
-        ``Identity`` and ``AlignFeatureLayer`` preprocessing: the nets' part ``d xi / d r`` by ``torch.func`` (fp32, on the
-        device), the coordinate part by the HIP kernel ``cvf_align_feature_vjp_rows`` (all k rows of a frame in one pass).
+        ``Identity`` and ``AlignFeatureLayer`` preprocessing: the nets' part ``xi`` and ``d xi / d r`` by the per-layer HIP kernels
+        of ``cvf_cv_nets_eval`` when the nets are an ``EigenFunctions`` or a ``create_sequential_nn`` chain such as an encoder
+        (:meth:`nets_route`), by ``torch.func`` otherwise (fp32, on the device); the coordinate part by the HIP kernel
+        ``cvf_align_feature_vjp_rows`` (all k rows of a frame in one pass).
         Any other preprocessing module, and alignment layers whose tables exceed the derivative kernels' limits
         (``AlignFeatureLayer.derivative_table_limits()``), take the slow route: torch autograd through the whole map, one
         backward per CV.  ``chunk`` bounds the device workspace in frames (default: from the free device memory)."""
@@ -206,6 +209,60 @@ class _CVModel(torch.nn.Sequential):
         mods = list(self.children())
         return mods[0], (mods[1] if len(mods) == 2 else torch.nn.Sequential(*mods[1:]))
 
+    def nets_route(self):
+        """``("hip", None)`` when :meth:`jacobian` / :meth:`metric_tensor` take the nets' part ``xi = nets(r)``, ``d xi / d r`` from
+        ``cvf_cv_nets_eval`` (csrc/cv_nets.hip), ``("torch", reason)`` when they take it from ``torch.func``.  Decided from the
+        model alone (no device is touched): the nets must be an ``EigenFunctions`` or a ``create_sequential_nn`` chain - Linear
+        layers and activations the kernels implement - of a shape ``cvf_cv_nets_supported`` accepts, behind an ``Identity`` or an
+        ``AlignFeatureLayer`` within its derivative tables' limits."""
+        pp, nets = self._pp_and_nets()
+        if not isinstance(pp, (torch.nn.Identity, AlignFeatureLayer)):
+            return "torch", f"the preprocessing layer {type(pp).__name__} takes the slow route (torch autograd through the whole map)"
+        if isinstance(pp, AlignFeatureLayer) and pp.derivative_table_limits() is not None:
+            return "torch", f"the feature list has {pp.derivative_table_limits()}: the slow route"
+        try:
+            self._nets_plan(nets)
+        except TypeError as e:
+            return "torch", str(e)
+        return "hip", None
+
+    @staticmethod
+    def _nets_plan(nets):
+        """``(desc, upto_layer, k, params)`` of nets ``cvf_cv_nets_eval`` takes: the ``cvf_mlp_desc`` over the flat buffer
+        ``cat(params)`` (per chain and layer: weight, bias), form A for an ``EigenFunctions`` (its nets in their own order: the
+        model's outputs), form B for a bare chain.  TypeError with the reason for every other module.  Built from the modules on
+        every call - nothing is kept between calls, so parameters trained or replaced in between are the ones read."""
+        if type(nets) is EigenFunctions:
+            chains = [_strict_chain_layers(net) for net in nets.eigen_funcs]
+        elif type(nets) is torch.nn.Sequential:
+            chains = [_strict_chain_layers(nets)]
+        else:
+            raise TypeError(f"the nets are a {type(nets).__name__}: cvf_cv_nets_eval takes an EigenFunctions or a create_sequential_nn chain")
+        shape = lambda c: [(lin.in_features, lin.out_features, act) for lin, act in c]
+        if any(shape(c) != shape(chains[0]) for c in chains):
+            raise TypeError("the nets differ in architecture")
+        L = len(chains[0])
+        k = len(chains) if len(chains) > 1 else chains[0][-1][0].out_features
+        if not 1 <= len(chains) <= _hip.MAX_NETS:
+            raise TypeError(f"k = {len(chains)} nets: the kernels take 1 to {_hip.MAX_NETS}")
+        if L > _hip.MAX_LAYERS:
+            raise TypeError(f"{L} layers: the kernels take 1 to {_hip.MAX_LAYERS}")
+        d, params, pos = _hip.MLPDesc(), [], 0
+        d.n_nets, d.n_layers = len(chains), L
+        for l, (fin, fout, act) in enumerate(shape(chains[0])):
+            d.dims[l], d.dims[l + 1], d.act[l] = fin, fout, act
+        for i, chain in enumerate(chains):
+            for l, (lin, _) in enumerate(chain):
+                d.w_off[i][l], d.b_off[i][l] = pos, pos + lin.weight.numel()
+                pos += lin.weight.numel() + lin.bias.numel()
+                params += [lin.weight, lin.bias]
+        if pos >= 2 ** 31:
+            raise TypeError(f"{pos} parameters: cvf_mlp_desc holds 32-bit offsets")
+        d.n_params = pos
+        if _hip.lib().cvf_cv_nets_supported(d, L, 1) != 1:
+            raise TypeError(_hip.lib().cvf_last_error().decode())
+        return d, L, k, params
+
     def _derivatives(self, X, chunk, want_m, a=None):
         X = self._frames_in(X)
         dev = _hip.require_gpu(self._compute_device())
@@ -219,8 +276,14 @@ class _CVModel(torch.nn.Sequential):
             raise NotImplementedError(f"metric_tensor on MI355X: the feature list has {why} (csrc/metric_large.hip); "
                                       "jacobian() takes this layer (slow route, torch autograd through the whole map)")
         hip_route = isinstance(pp, torch.nn.Identity) or (isinstance(pp, AlignFeatureLayer) and why is None)
+        plan = None
+        if hip_route:
+            try:
+                plan = self._nets_plan(nets)
+            except TypeError:
+                pass    # (nets_route() names the reason) the nets' part by torch.func
         with torch.cuda.device(dev):
-            k = self._n_cv(X[:1], dev) if B > 0 else 0
+            k = (plan[2] if plan is not None else self._n_cv(X[:1], dev)) if B > 0 else 0
             if hip_route and not 1 <= k <= _hip.MAX_NETS:
                 raise NotImplementedError(f"jacobian / metric_tensor on MI355X: {k} CVs; the kernels take 1 to {_hip.MAX_NETS}")
             xi = torch.empty(B, k, device=dev, dtype=torch.float32)
@@ -236,11 +299,15 @@ class _CVModel(torch.nn.Sequential):
                 dense = torch.zeros(_hip.lib().cvf_metric_dense_doubles(desc), device=dev, dtype=torch.float64)
                 _hip.check(_hip.lib().cvf_metric_dense_tensors(desc, _hip.ptr(a_dev), _hip.ptr(dense), _hip.stream()),
                            "cvf_metric_dense_tensors")
-            c = self._chunk_frames(chunk, B, n, k, pp, dev)
+            c = self._chunk_frames(chunk, B, n, k, pp, dev, plan)
+            theta = None
+            if plan is not None:   # the nets' parameters as they are NOW, in the order of the plan's offsets
+                theta = torch.cat([p_.detach().to(device=dev, dtype=torch.float32).reshape(-1) for p_ in plan[3]])
             for s0 in range(0, B, c):
                 xs = X[s0:s0 + c]
                 if hip_route:
-                    xi[s0:s0 + xs.shape[0]], D[s0:s0 + xs.shape[0]] = self._hip_chunk(xs, pp, nets, k, want_m, a_dev, dense, dev)
+                    xi[s0:s0 + xs.shape[0]], D[s0:s0 + xs.shape[0]] = self._hip_chunk(xs, pp, nets, k, want_m, a_dev, dense, dev,
+                                                                                      plan, theta)
                 else:
                     twin = self._autograd_twin() if isinstance(pp, AlignFeatureLayer) else self
                     xi[s0:s0 + xs.shape[0]], D[s0:s0 + xs.shape[0]] = self._slow_chunk(xs, twin, k, want_m, a, dev)
@@ -258,35 +325,57 @@ class _CVModel(torch.nn.Sequential):
                 return t.dtype
         return torch.float32
 
-    def _chunk_frames(self, chunk, B, n, k, pp, dev):
+    def _chunk_frames(self, chunk, B, n, k, pp, dev, plan=None):
         if chunk is not None:
             if int(chunk) < 1:
                 raise ValueError(f"chunk must be a positive number of frames, got {chunk}")
             return int(chunk)
         d_r = pp.d_r if isinstance(pp, AlignFeatureLayer) else n
-        # fp32 per frame: x, features, aux, d xi / d r (rows, padded tiles, q), J rows or M, and torch.func's temporaries
-        per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 6 * k * d_r + k * n + k * k) + 64 * k * d_r
+        if plan is not None:
+            # fp32 per frame: x, features, aux, d xi / d r and q (one layout each), J rows or M, the nets' launch-to-launch images
+            per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 2 * k * d_r + k * n + k * k) \
+                + 4 * _hip.lib().cvf_cv_nets_scratch_floats(plan[0], plan[1], _hip.TILE, 1) // _hip.TILE
+        else:
+            # fp32 per frame: x, features, aux, d xi / d r (rows, padded tiles, q), J rows or M, and torch.func's temporaries
+            per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 6 * k * d_r + k * n + k * k) + 64 * k * d_r
         free, _ = torch.cuda.mem_get_info(dev)
         c = int(self.JACOBIAN_MEMORY_FRACTION * free) // per // _hip.TILE * _hip.TILE
         return max(_hip.TILE, min(c, B))
 
-    def _hip_chunk(self, xs, pp, nets, k, want_m, a_dev, dense, dev):
-        """One chunk on the HIP route: (xi [c, k], J rows [c, k, n] or M [c, k, k]), fp32 on the device."""
+    def _hip_chunk(self, xs, pp, nets, k, want_m, a_dev, dense, dev, plan=None, theta=None):
+        """One chunk on the HIP route: (xi [c, k], J rows [c, k, n] or M [c, k, k]), fp32 on the device.  With a ``plan``
+        (``_nets_plan``; ``theta``: the flat parameters) the nets' part comes from ``cvf_cv_nets_eval``, else from ``torch.func``."""
         lib, P, s = _hip.lib(), _hip.ptr, _hip.stream()
         c = int(xs.shape[0])
         x = xs.detach().to(device=dev, dtype=torch.float32).reshape(c, -1).contiguous()
         n = x.shape[1]
         T = _hip.ntiles(c)
+        r = r_t = None
         if isinstance(pp, AlignFeatureLayer):
             assert n == 3 * pp.n_atoms, f"frames have {n} coordinates, the layer expects {3 * pp.n_atoms}"
-            desc = pp.pp_desc()
-            r = torch.empty(c, pp.d_r, device=dev, dtype=torch.float32)
+            desc, d_r = pp.pp_desc(), pp.d_r
+            if plan is not None:   # the nets read the tiles the alignment kernel writes
+                r_t = torch.empty(T, d_r, _hip.TILE, device=dev, dtype=torch.float32)
+            else:
+                r = torch.empty(c, d_r, device=dev, dtype=torch.float32)
             aux = torch.empty(T, _hip.AUX_ROWS, _hip.TILE, device=dev, dtype=torch.float32)   # padded frame count
             scratch = _hip.align_scratch(desc, c, dev)
-            _hip.check(lib.cvf_align_feature_fwd(desc, P(x), c, None, P(r), P(aux), P(scratch), s), "cvf_align_feature_fwd")
+            _hip.check(lib.cvf_align_feature_fwd(desc, P(x), c, P(r_t), P(r), P(aux), P(scratch), s), "cvf_align_feature_fwd")
         else:
-            desc, r, aux, scratch = identity_desc(n), x, None, None
-        d_r = r.shape[1]
+            desc, r, aux, scratch, d_r = identity_desc(n), x, None, None, n
+        if plan is not None:
+            mdesc, upto = plan[0], plan[1]
+            assert mdesc.dims[0] == d_r, f"the nets take {mdesc.dims[0]} features, the preprocessing layer gives {d_r}"
+            xi = torch.empty(c, k, device=dev, dtype=torch.float32)
+            G = None if want_m else torch.empty(c, k, d_r, device=dev, dtype=torch.float32)
+            g_t = torch.empty(T, k, d_r, _hip.TILE, device=dev, dtype=torch.float32) if want_m else None
+            ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mdesc, upto, c, 1), device=dev, dtype=torch.float32)
+            _hip.check(lib.cvf_cv_nets_eval(mdesc, P(theta), upto, P(r), P(r_t), c, P(xi), P(G), P(g_t), P(ws), s), "cvf_cv_nets_eval")
+            if not want_m:
+                J = torch.empty(c, k, n, device=dev, dtype=torch.float32)
+                _hip.check(lib.cvf_align_feature_vjp_rows(desc, P(x), c, P(aux), k, P(G), P(J), s), "cvf_align_feature_vjp_rows")
+                return xi, J
+            return xi, self._metric_from_tiles(desc, x, c, aux, a_dev, k, d_r, g_t, scratch, dense, dev)
 
         def f(v):
             y = nets(v.unsqueeze(0)).reshape(-1)
@@ -301,13 +390,19 @@ class _CVModel(torch.nn.Sequential):
         g_t = torch.zeros(T * _hip.TILE, k, d_r, device=dev, dtype=torch.float32)
         g_t[:c] = G
         g_t = g_t.reshape(T, _hip.TILE, k, d_r).permute(0, 2, 3, 1).contiguous()   # [T][k][d_r][64]
+        return xi.detach(), self._metric_from_tiles(desc, x, c, aux, a_dev, k, d_r, g_t, scratch, dense, dev)
+
+    @staticmethod
+    def _metric_from_tiles(desc, x, c, aux, a_dev, k, d_r, g_t, scratch, dense, dev):
+        """M [c, k, k] = g_i . (J A J^T g_j) from g_t [T][k][d_r][64] (padded lanes 0): cvf_metric_apply, cvf_metric_gram."""
+        lib, P, s = _hip.lib(), _hip.ptr, _hip.stream()
         q_t = torch.empty_like(g_t)
-        e_t = torch.empty(T, k, _hip.TILE, device=dev, dtype=torch.float32)
+        e_t = torch.empty(g_t.shape[0], k, _hip.TILE, device=dev, dtype=torch.float32)
         _hip.check(lib.cvf_metric_apply(desc, P(x), c, P(aux), P(a_dev), k, P(g_t), P(q_t), P(e_t), P(scratch), P(dense), s),
                    "cvf_metric_apply")
         M = torch.empty(c, k, k, device=dev, dtype=torch.float32)
         _hip.check(lib.cvf_metric_gram(k, c, d_r, P(g_t), P(q_t), P(M), s), "cvf_metric_gram")
-        return xi.detach(), M
+        return M
 
     @staticmethod
     def _slow_chunk(xs, model, k, want_m, a, dev):

@@ -168,9 +168,37 @@ def _chain_layers(seq):
     return out
 
 
+def _strict_chain_layers(seq):
+    """``_chain_layers`` for a module nobody vouches for: the same list when ``seq`` is a plain ``Sequential`` of ``Linear`` layers
+    (with bias, widths that chain), each followed by at most one activation the kernels implement - what ``create_sequential_nn``
+    builds.  TypeError (with the reason) for anything else."""
+    if type(seq) is not torch.nn.Sequential:
+        raise TypeError(f"{type(seq).__name__} is not a create_sequential_nn chain")
+    children, out, i = list(seq._modules.values()), [], 0
+    while i < len(children):
+        lin, act = children[i], ACT_NONE
+        if type(lin) is not torch.nn.Linear or lin.bias is None:
+            raise TypeError(f"child {i} of the chain ({type(lin).__name__}) is not a Linear layer with a bias")
+        if out and out[-1][0].out_features != lin.in_features:
+            raise TypeError(f"child {i} of the chain takes {lin.in_features} inputs, the layer before it has {out[-1][0].out_features} outputs")
+        if i + 1 < len(children) and not isinstance(children[i + 1], torch.nn.Linear):
+            try:
+                act = _act_code(children[i + 1])
+            except NotImplementedError:
+                raise TypeError(f"no HIP kernel for the activation {children[i + 1]}") from None
+            i += 1
+        out.append((lin, act))
+        i += 1
+    if not out:
+        raise TypeError("the chain has no Linear layer")
+    return out
+
+
 def mlp_layout(model):
     """Describe ``model`` as chains of Linear layers over ONE flat fp32 buffer laid out in
-    ``model.parameters()`` order.  Returns dict(nets=[[(w_off, b_off, in, out, act), ...], ...], n_params)."""
+    ``model.parameters()`` order.  Returns dict(nets=[[(w_off, b_off, in, out, act), ...], ...], n_params).
+    ``EigenFunctions``, ``AutoEncoder``, or a bare ``create_sequential_nn`` chain such as an encoder (checked strictly: TypeError
+    when the module is anything else)."""
     offsets, pos = {}, 0
     for p in model.parameters():
         offsets[id(p)] = pos
@@ -181,6 +209,8 @@ def mlp_layout(model):
         #  64-frame kernels take every code above - csrc/ef_mfma.hip: ef_shape; other shapes are rejected by the task)
     elif isinstance(model, AutoEncoder):
         chains = [_chain_layers(model.encoder) + _chain_layers(model.decoder)]
+    elif type(model) is torch.nn.Sequential:
+        chains = [_strict_chain_layers(model)]
     else:
         raise TypeError(f"no HIP layout for model type {type(model).__name__}")
     nets = [[(offsets[id(lin.weight)], offsets[id(lin.bias)], lin.in_features, lin.out_features, int(act))

@@ -533,9 +533,37 @@ int cvf_regae_loss_row(const double* out2, const double* loss_vec, double alpha,
 
 /* --- nets forward on row-major features (inference: colvar_model(), core.py:372-382,
  * 640-647).  out [B][n_out] where n_out = n_nets * d_L; upto_layer < n_layers stops a
- * single chain early (AutoEncoder encoder). */
+ * single chain early (AutoEncoder encoder).  The chain stays in LDS: chains past 160 KiB are refused - wide chains, and
+ * callers that also want d xi / d r, take cvf_cv_nets_eval below. */
 int cvf_mlp_eval_rows(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, int64_t B, int upto_layer,
                       float* out, void* stream);
+
+/* --- a trained CV and its derivative in the features (csrc/cv_nets.hip): xi = nets(r) and
+ * G = d xi / d r per frame, what self.model(...) and autograd through it give the callers of colvar_model() (core.py:372-382,
+ * 640-647, 855-863).  One launch per layer and pass over all 64-frame tiles, activations handed over through `scratch`.  With
+ * cvf_align_feature_fwd before it and cvf_align_feature_vjp_rows behind it, a C caller gets xi(x) and d xi / d x.
+ * The model, read from cvf_mlp_desc (offsets may point anywhere inside theta; n_params is not read):
+ *   form A  n_nets = k >= 2 scalar chains side by side (EigenFunctions), upto_layer = n_layers; weights per net;
+ *   form B  n_nets = 1: the first upto_layer layers of one chain, k = dims[upto_layer] (the encoder of an AutoEncoder /
+ *           RegAutoEncoder flat layout, or a bare chain; one Linear layer is legal).  The trunk runs once, not k times.
+ * 1 to CVF_MAX_LAYERS layers, dims[0] from 1 to 65536, inner widths 1 to 4096, any act code of this header after any layer;
+ * k <= CVF_MAX_NETS when g_rows or g_tiled is asked for (want_g), k <= 4096 for values alone.
+ *  cvf_cv_nets_supported     : 1, or 0 with the reason in cvf_last_error(); the two calls below refuse the same models, before
+ *                              any launch.
+ *  cvf_cv_nets_scratch_floats: floats of `scratch` for B frames, T = ceil(B / 64): 64 T (dims[0] + c sum of dims[1..upto_layer]),
+ *                              c = n_nets chains, + with want_g 128 T k max(dims[1..upto_layer-2]) (chains of three layers or
+ *                              more); 0 for a refused model.
+ *  cvf_cv_nets_eval          : exactly one of feat_rows [B][d_r] and feat_tiled [T][d_r][64] (as cvf_align_feature_fwd writes
+ *                              it) -> xi_rows [B][k] and, each unless NULL, g_rows [B][k][d_r] (what cvf_align_feature_vjp_rows
+ *                              reads) and g_tiled [T][k][d_r][64] (what cvf_metric_apply / cvf_metric_gram read; lanes of padded
+ *                              frames hold exactly 0).  g_rows and g_tiled hold the same bits.
+ * No atomics.  A frame's xi and g depend on its features and theta only - not on B, nor on the tile or lane the frame sits in.
+ * Nothing is read from scratch or the outputs that the same call did not write. */
+int cvf_cv_nets_supported(const cvf_mlp_desc* mlp, int upto_layer, int want_g);
+int64_t cvf_cv_nets_scratch_floats(const cvf_mlp_desc* mlp, int upto_layer, int64_t B, int want_g);
+int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const float* feat_rows,
+                     const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled, float* scratch,
+                     void* stream);
 
 /* --- K6: Adam (torch.optim.Adam defaults as constructed at core.py:164: betas
  * (0.9,0.999), eps 1e-8, no weight decay, no amsgrad), one launch over the flat buffer.
