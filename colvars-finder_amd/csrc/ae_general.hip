@@ -22,7 +22,6 @@
 // thread and the sum order of every entry is fixed by the grid, so two calls on the same inputs give the same bits.  Nothing is
 // read from scratch that the same call did not write.
 #include "aeg_kernels.hpp"
-#include <stdio.h>
 
 // (csrc/ef_mfma.hip) fixed-order sum of slab rows [+ Adam] [+ one extra block adding n_pair [a, b] rows -> [a, b, a / b]]
 int cvf_slab_reduce_impl(const float* slab, int64_t n_rows, int64_t n_params, float* grad, const float* mask,
@@ -73,7 +72,6 @@ struct AegLayout {
   int wmax;
 };
 
-
 AegLayout aeg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles) {
   AegLayout L = {};
   const int64_t per = n_tiles * CVF_TILE;   // floats of one row of every tile
@@ -88,7 +86,7 @@ AegLayout aeg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles) {
     L.zb[i] = pos;
     pos += per * L.wmax;
   }
-  L.rows = aeg_rows(mlp, n_tiles);
+  L.rows = g64_rows(mlp, n_tiles);
   L.slab = pos;
   pos += L.rows * mlp->n_params;
   L.partial = (pos + 1) & ~(int64_t)1;
@@ -103,38 +101,12 @@ const char* aeg_why(const cvf_mlp_desc* mlp) {
     snprintf(buf, sizeof buf, "%d nets: one chain is expected", mlp->n_nets);
     return buf;
   }
-  if (mlp->n_layers < 1 || mlp->n_layers > CVF_MAX_LAYERS) {
-    snprintf(buf, sizeof buf, "%d layers: 1 to %d are supported", mlp->n_layers, CVF_MAX_LAYERS);
+  const char* why = g64_why(mlp, mlp->n_layers, G64Chain{1, "hidden layer", "chain", true, true}, buf, sizeof buf);
+  if (why != nullptr) return why;
+  if (mlp->dims[mlp->n_layers] != mlp->dims[0]) {
+    snprintf(buf, sizeof buf, "output width %d != input width %d", mlp->dims[mlp->n_layers], mlp->dims[0]);
     return buf;
   }
-  const int L = mlp->n_layers;
-  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
-    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
-    return buf;
-  }
-  if (mlp->dims[L] != mlp->dims[0]) {
-    snprintf(buf, sizeof buf, "output width %d != input width %d", mlp->dims[L], mlp->dims[0]);
-    return buf;
-  }
-  for (int l = 1; l < L; ++l)
-    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
-      snprintf(buf, sizeof buf, "hidden layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
-      return buf;
-    }
-  for (int l = 0; l < L; ++l)   // aeg_wgrad_kernel's 64 x 64 blocks of [W_l | b_l] are its grid.y
-    if ((int64_t)((mlp->dims[l + 1] + 63) / 64) * ((mlp->dims[l] + 1 + 63) / 64) > 65535) {
-      snprintf(buf, sizeof buf, "layer %d (%d x %d) has more than 65535 blocks of 64 x 64 weights", l, mlp->dims[l + 1], mlp->dims[l]);
-      return buf;
-    }
-  for (int l = 0; l < L; ++l)
-    if (mlp->act[l] < CVF_ACT_NONE || mlp->act[l] > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
-  int64_t n = 0;
-  for (int l = 0; l < L; ++l) n += (int64_t)mlp->dims[l + 1] * (mlp->dims[l] + 1);
-  if (n != mlp->n_params) return "the flat buffer holds parameters outside the chain";
-  for (int l = 0; l < L; ++l)
-    if (mlp->w_off[0][l] < 0 || mlp->w_off[0][l] + (int64_t)mlp->dims[l + 1] * mlp->dims[l] > n || mlp->b_off[0][l] < 0 ||
-        mlp->b_off[0][l] + (int64_t)mlp->dims[l + 1] > n)
-      return "a layer's parameters lie outside the flat buffer";
   return nullptr;
 }
 

@@ -2,7 +2,7 @@
 // G = d xi / d r per frame, for the callers of colvar_model().jacobian() / .metric_tensor() and for a C caller that biases an
 // MD engine along a learned CV (cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp_rows).
 // One launch per layer and pass over all 64-frame tiles, the activations handed over through `scratch`, in the decomposition of
-// csrc/ef_general.hip and csrc/ae_general.hip:
+// csrc/ef_general.hip and csrc/ae_general.hip, the products on the 64 x 64 core of csrc/cvf_gemm64.hpp:
 //
 //   aeg_gather_kernel  (csrc/aeg_kernels.hpp) feat_rows [B][d0] -> a_0 [tile][d0][64]; skipped when the caller has tiles
 //   cvn_layer_kernel   [M x K] x [K x 64 frames] per (tile, 64-row block, z): W_l (forward) or W_l^T (sweep) as the A operand;
@@ -22,7 +22,6 @@
 // meets the same instructions in the same order whichever tile and lane it sits in, so a frame's xi and g depend on its
 // features and theta only.  Nothing is read from scratch or the outputs that the same call did not write.
 #include "aeg_kernels.hpp"
-#include <stdio.h>
 
 namespace {
 
@@ -51,90 +50,45 @@ struct CvnArgs {
 constexpr int kXP = 65;   // pitch of the [frame][m] image of the g_rows transpose
 static_assert(CVF_TILE * kXP <= 2 * kKC * kPitch, "the transpose reuses the operand stages");
 
-// out[m][frame] (64 x 64 block) = A[m][:] . B[:][frame] for one (tile, row block, z); 4 waves of 32 x 32
+// out[m][frame] (64 x 64 block) = A[m][:] . B[:][frame] for one (tile, row block, z)
 __global__ __launch_bounds__(256) void cvn_layer_kernel(const float* __restrict__ theta, CvnArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * kKC * kPitch];
-  float* As = smem;                   // [k][m]
-  float* Bs = smem + kKC * kPitch;    // [k][frame]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ __attribute__((aligned(16))) float smem[2 * kKC * kPitch];   // As [k][m], then Bs [k][frame]
+  const G64Thread t = g64_thread();
+  const int lane = t.lane, wave = t.wave;
   const int64_t tile = blockIdx.x;
   const int m0 = blockIdx.y * 64, z = blockIdx.z;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  const int col = lane & 15, kq = lane >> 4;
-  const float* W = theta + a.w_off[z];
   const float* xp = a.seed ? nullptr : a.x + z * a.xz + tile * a.xs;
   const float* hp = a.xh != nullptr ? a.xh + z * a.hz + tile * a.hs : nullptr;
   const float* sp = a.seed ? theta + a.s_off[z] : nullptr;
   const float sfac = a.seed ? cvf_act_d1(a.act_top, a.top[z * a.tpz + tile * a.tps + lane]) : 0.0f;
-  // W as stored ([m][k], k contiguous): the staging of aeg_layer_kernel (two neighbouring k of a row per lane pair)
-  const int kl = (lane & 1) + 2 * (lane >> 5), ml = 16 * wave + ((lane >> 1) & 15);
 
   f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  g64_layer_product(smem, smem + kKC * kPitch, theta + a.w_off[z], a.ldw, a.trans, m0, a.M, a.K, t, acc, [&](int k) {
+    float bv = sp != nullptr ? sfac * sp[k] : xp[(int64_t)k * CVF_TILE + lane];
+    if (hp != nullptr) bv *= cvf_act_d1(a.act, hp[(int64_t)k * CVF_TILE + lane]);
+    return bv;
+  });
 
-  for (int k0 = 0; k0 < a.K; k0 += kKC) {
-#pragma unroll
-    for (int it = 0; it < kKC / 4; ++it) {
-      if (a.trans) {   // W^T: m runs along W's rows, over the lanes
-        const int kk = wave + 4 * it, k = k0 + kk, m = m0 + lane;
-        As[kk * kPitch + lane] = m < a.M && k < a.K ? W[(int64_t)k * a.ldw + m] : 0.0f;
-      } else {
-        const int kk = 4 * it + kl, k = k0 + kk, m = m0 + ml;
-        As[kk * kPitch + ml] = m < a.M && k < a.K ? W[(int64_t)m * a.ldw + k] : 0.0f;
-      }
-      const int kk = wave + 4 * it, k = k0 + kk;
-      float bv = 0.0f;
-      if (k < a.K) {
-        bv = sp != nullptr ? sfac * sp[k] : xp[(int64_t)k * CVF_TILE + lane];
-        if (hp != nullptr) bv *= cvf_act_d1(a.act, hp[(int64_t)k * CVF_TILE + lane]);
-      }
-      Bs[kk * kPitch + lane] = bv;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < kKC; ks += 4) {
-      const int kr = (ks + kq) * kPitch;
-      const float a0 = As[kr + wm + col], a1 = As[kr + wm + 16 + col];
-      const float b0 = Bs[kr + wn + col], b1 = Bs[kr + wn + 16 + col];
-      acc[0][0] = mfma4(a0, b0, acc[0][0]);
-      acc[0][1] = mfma4(a0, b1, acc[0][1]);
-      acc[1][0] = mfma4(a1, b0, acc[1][0]);
-      acc[1][1] = mfma4(a1, b1, acc[1][1]);
-    }
-    __syncthreads();
-  }
-
-  // epilogue: C row = 4 * (lane >> 4) + r of each 16 x 16 block, column (frame) = lane & 15
   const float* bias = a.epi == CVN_ACT ? theta + a.b_off[z] : nullptr;
   float* op = a.epi != CVN_G ? a.out + z * a.oz + tile * a.os : nullptr;
   float* gt = a.epi == CVN_G && a.g_tiled != nullptr ? a.g_tiled + (tile * a.k + z) * (int64_t)a.M * CVF_TILE : nullptr;
   const bool rows = a.epi == CVN_G && a.g_rows != nullptr;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int mloc = wm + 16 * i + 4 * kq + r, m = m0 + mloc;
-        const int f = wn + 16 * j + col;
-        float v = acc[i][j][r];
-        if (rows) smem[f * kXP + mloc] = v;   // (the K loop ended on a barrier: the stages are free)
-        if (m >= a.M) continue;
-        const int64_t o = (int64_t)m * CVF_TILE + f;
-        const bool valid = tile * CVF_TILE + f < a.B;
-        if (a.epi == CVN_ACT) {
-          v = cvf_act(a.act, v + bias[m]);
-          op[o] = v;
-          if (a.xi_rows != nullptr && valid) a.xi_rows[(tile * CVF_TILE + f) * a.k + z * a.M + m] = v;
-        } else if (a.epi == CVN_SWEEP) {
-          op[o] = v;
-        } else if (gt != nullptr) {
-          gt[o] = valid ? v : 0.0f;   // lanes of padded frames hold exactly 0
-        }
-      }
+  g64_walk(acc, t, [&](int mloc, int f, float v) {
+    const int m = m0 + mloc;
+    if (rows) smem[f * kXP + mloc] = v;   // (the product ended on a barrier: the stages are free)
+    if (m >= a.M) return;
+    const int64_t o = (int64_t)m * CVF_TILE + f;
+    const bool valid = tile * CVF_TILE + f < a.B;
+    if (a.epi == CVN_ACT) {
+      v = cvf_act(a.act, v + bias[m]);
+      op[o] = v;
+      if (a.xi_rows != nullptr && valid) a.xi_rows[(tile * CVF_TILE + f) * a.k + z * a.M + m] = v;
+    } else if (a.epi == CVN_SWEEP) {
+      op[o] = v;
+    } else if (gt != nullptr) {
+      gt[o] = valid ? v : 0.0f;   // lanes of padded frames hold exactly 0
+    }
+  });
   if (rows) {   // [frame][m] -> g_rows[frame][z][m0 ..], the stores of a wave along m
     __syncthreads();
 #pragma unroll 4
@@ -211,15 +165,8 @@ const char* cvn_why(const cvf_mlp_desc* mlp, int upto, int want_g, CvnShape* sh)
     snprintf(buf, sizeof buf, "%d nets side by side must be scalar (they have %d outputs each)", mlp->n_nets, mlp->dims[upto]);
     return buf;
   }
-  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
-    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
-    return buf;
-  }
-  for (int l = 1; l < upto; ++l)
-    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
-      snprintf(buf, sizeof buf, "layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
-      return buf;
-    }
+  const char* why = g64_why(mlp, upto, G64Chain{1, "layer", "model", false, false}, buf, sizeof buf);
+  if (why != nullptr) return why;
   const int k = form_a ? mlp->n_nets : mlp->dims[upto];
   if (k < 1 || k > kMaxValuesK) {
     snprintf(buf, sizeof buf, "%d outputs: 1 to %d are supported", k, kMaxValuesK);
@@ -230,8 +177,6 @@ const char* cvn_why(const cvf_mlp_desc* mlp, int upto, int want_g, CvnShape* sh)
              kMaxValuesK);
     return buf;
   }
-  for (int l = 0; l < upto; ++l)
-    if (mlp->act[l] < CVF_ACT_NONE || mlp->act[l] > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
   for (int i = 0; i < (form_a ? mlp->n_nets : 1); ++i)
     for (int l = 0; l < upto; ++l)
       if (mlp->w_off[i][l] < 0 || mlp->b_off[i][l] < 0) return "a negative parameter offset";

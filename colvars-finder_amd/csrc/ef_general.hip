@@ -20,22 +20,12 @@
 //   gradient    dW_l = sum_frames zbar_l (x) h_{l-1} + d_l (x) tdot_{l-1},  db_l = sum_frames zbar_l   (zbar_NH = alpha, d_NH = gamma)
 // (the formula of ef_mfma.hip's header; transfer mode has gamma = 0 and no g / tangent).
 //
-// All products run on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation.  The hand-off between layers goes through
-// the `saved` buffer in HBM (layout: efg_layout).  No atomics: every slab entry is written by one thread, and the sum order
-// of every entry is fixed by the grid, so two runs on the same inputs give the same bits.
-#include "cvf_common.hpp"
-#include <stdio.h>
+// All products run on v_mfma_f32_16x16x4_f32 (the 64 x 64 core of csrc/cvf_gemm64.hpp): fp32 operands, fp32 accumulation.
+// The hand-off between layers goes through the `saved` buffer in HBM (layout: efg_layout).  No atomics: every slab entry is
+// written by one thread, and the sum order of every entry is fixed by the grid, so two runs on the same inputs give the same bits.
+#include "cvf_gemm64.hpp"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-constexpr int kMaxWidth = 4096;     // widest layer cvf_ef_general_supported() accepts (d0 up to kMaxD0)
-constexpr int kMaxD0 = 65536;
-constexpr int64_t kSlabBytes = 128ll << 20;   // slab budget: rows = 128 MiB / (4 n_params), at least 1, at most kMaxRows
-constexpr int kMaxRows = 256;
 
 // a tiled tensor over (net, tile, row, lane): element = p[net * ns + tile * ts + row * 64 + lane]
 struct EfgView {
@@ -61,88 +51,46 @@ struct EfgLayerArgs {
   EfgView x, xh, out, eh, eu, gam;
 };
 
-// out[m][frame] (64 x 64 block) = A[m][:] . op(B)[:][frame] for one (tile, row block, net); 4 waves of 32 x 32
-constexpr int kKC = 32;          // K per LDS stage
-constexpr int kPitch = 80;       // LDS pitch of the k-major images (a fragment read spans 4 k-rows of 16 consecutive words)
+// out[m][frame] (64 x 64 block) = A[m][:] . op(B)[:][frame] for one (tile, row block, net)
 __global__ __launch_bounds__(256) void efg_layer_kernel(cvf_mlp_desc mlp, const float* __restrict__ theta, EfgLayerArgs a) {
   __shared__ __attribute__((aligned(16))) float As[kKC * kPitch];   // [k][m]
   __shared__ __attribute__((aligned(16))) float Bs[kKC * kPitch];   // [k][frame]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const G64Thread t = g64_thread();
   const int64_t tile = blockIdx.x;
   const int m0 = blockIdx.y * 64, net = blockIdx.z;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  const int col = lane & 15, kq = lane >> 4;
-  const float* W = theta + mlp.w_off[net][a.layer];
-  const int ldw = mlp.dims[a.layer];
   const float* xb = a.x_bcast ? theta + mlp.w_off[net][mlp.n_layers - 1] : nullptr;
   const float* xp = a.x_bcast ? nullptr : at(a.x, net, tile, 0);
   const float* hp = a.xh.p != nullptr ? at(a.xh, net, tile, 0) : nullptr;
 
   f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  g64_layer_product(As, Bs, theta + mlp.w_off[net][a.layer], mlp.dims[a.layer], a.trans, m0, a.M, a.K, t, acc, [&](int k) {
+    float bv = xb != nullptr ? xb[k] : xp[(int64_t)k * CVF_TILE + t.lane];
+    if (hp != nullptr) bv *= cvf_act_d1(a.act_x, hp[(int64_t)k * CVF_TILE + t.lane]);
+    return bv;
+  });
 
-  for (int k0 = 0; k0 < a.K; k0 += kKC) {
-    // stage A (weights; m runs over the lanes) and B (activations; frames run over the lanes)
-#pragma unroll
-    for (int it = 0; it < kKC / 4; ++it) {
-      const int kk = wave + 4 * it, k = k0 + kk, m = m0 + lane;
-      float av = 0.0f;
-      if (m < a.M && k < a.K) av = a.trans ? W[(int64_t)k * ldw + m] : W[(int64_t)m * ldw + k];
-      As[kk * kPitch + lane] = av;
-      float bv = 0.0f;
-      if (k < a.K) {
-        bv = xb != nullptr ? xb[k] : xp[(int64_t)k * CVF_TILE + lane];
-        if (hp != nullptr) bv *= cvf_act_d1(a.act_x, hp[(int64_t)k * CVF_TILE + lane]);
-      }
-      Bs[kk * kPitch + lane] = bv;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < kKC; ks += 4) {
-      const int kr = (ks + kq) * kPitch;
-      const float a0 = As[kr + wm + col], a1 = As[kr + wm + 16 + col];
-      const float b0 = Bs[kr + wn + col], b1 = Bs[kr + wn + 16 + col];
-      acc[0][0] = mfma4(a0, b0, acc[0][0]);
-      acc[0][1] = mfma4(a0, b1, acc[0][1]);
-      acc[1][0] = mfma4(a1, b0, acc[1][0]);
-      acc[1][1] = mfma4(a1, b1, acc[1][1]);
-    }
-    __syncthreads();
-  }
-
-  // epilogue: C row = 4 * (lane >> 4) + r of each 16 x 16 block, column (frame) = lane & 15
   const float* bias = a.bias ? theta + mlp.b_off[net][a.layer] : nullptr;
   const float* gp = a.epi == EPI_BWD_GEN ? at(a.gam, net, tile, 0) : nullptr;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + 16 * i + 4 * kq + r;
-        const int f = wn + 16 * j + col;
-        if (m >= a.M) continue;
-        float v = acc[i][j][r];
-        float* o = at(a.out, net, tile, m) + f;
-        if (a.epi == EPI_STORE || a.epi == EPI_ACT) {
-          if (bias != nullptr) v += bias[m];
-          *o = a.epi == EPI_ACT ? cvf_act(a.act_e, v) : v;
-        } else {
-          const float h = at(a.eh, net, tile, m)[f];
-          const float s1 = cvf_act_d1(a.act_e, h);
-          if (a.epi == EPI_BWD_TR) {
-            *o = s1 * v;
-          } else {   // o holds zdot (read, then overwritten by zbar); eu holds u (overwritten by d)
-            float* up = at(a.eu, net, tile, m) + f;
-            const float g = gp[f], u = *up, zd = *o;
-            *o = s1 * v + g * cvf_act_d2(a.act_e, h) * zd * u;
-            *up = g * s1 * u;
-          }
-        }
+  g64_walk(acc, t, [&](int row, int f, float v) {
+    const int m = m0 + row;
+    if (m >= a.M) return;
+    float* o = at(a.out, net, tile, m) + f;
+    if (a.epi == EPI_STORE || a.epi == EPI_ACT) {
+      if (bias != nullptr) v += bias[m];
+      *o = a.epi == EPI_ACT ? cvf_act(a.act_e, v) : v;
+    } else {
+      const float h = at(a.eh, net, tile, m)[f];
+      const float s1 = cvf_act_d1(a.act_e, h);
+      if (a.epi == EPI_BWD_TR) {
+        *o = s1 * v;
+      } else {   // o holds zdot (read, then overwritten by zbar); eu holds u (overwritten by d)
+        float* up = at(a.eu, net, tile, m) + f;
+        const float g = gp[f], u = *up, zd = *o;
+        *o = s1 * v + g * cvf_act_d2(a.act_e, h) * zd * u;
+        *up = g * s1 * u;
       }
+    }
+  });
 }
 
 struct EfgGradArgs {
@@ -155,78 +103,20 @@ struct EfgGradArgs {
   EfgView a1, b1, a2, b2, b2h;   // a2.p == NULL: one part (transfer mode)
 };
 
-constexpr int kGP = 68;   // LDS pitch of the [row][frame] images (a fragment read spans 16 rows x 4 consecutive frames)
 __global__ __launch_bounds__(256) void efg_wgrad_kernel(const cvf_mlp_desc mlp, EfgGradArgs a, float* __restrict__ slab) {
   __shared__ __attribute__((aligned(16))) float As[64 * kGP];   // [out row][frame]
   __shared__ __attribute__((aligned(16))) float Bs[64 * kGP];   // [in column][frame]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rho = blockIdx.x, net = blockIdx.z;
-  const int nbn = (a.Ki + 1 + 63) / 64;
-  const int o0 = (blockIdx.y / nbn) * 64, i0 = (blockIdx.y % nbn) * 64;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  const int col = lane & 15, kq = lane >> 4;
-
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-
-  const int parts = a.a2.p != nullptr ? 2 : 1;
-  for (int64_t tile = rho; tile < a.n_tiles; tile += a.rows) {
-    const int64_t t0 = tile >= a.T ? tile - a.T : tile;
-    const bool valid = t0 * CVF_TILE + lane < a.B;   // padded frames contribute nothing
-    for (int part = 0; part < parts; ++part) {
-      const EfgView& av = part == 0 ? a.a1 : a.a2;
-      const EfgView& bv = part == 0 ? a.b1 : a.b2;
-      const float* ap = at(av, net, tile, 0);
-      const float* bp = at(bv, net, tile, 0);
-      const float* hp = part == 1 && a.b2h.p != nullptr ? at(a.b2h, net, tile, 0) : nullptr;
-#pragma unroll 4
-      for (int it = 0; it < 16; ++it) {
-        const int rr = wave + 4 * it;
-        const int o = o0 + rr, i = i0 + rr;
-        As[rr * kGP + lane] = valid && o < a.Mo ? ap[(int64_t)o * CVF_TILE + lane] : 0.0f;
-        float x = 0.0f;
-        if (valid) {
-          if (i < a.Ki) {
-            x = bp[(int64_t)i * CVF_TILE + lane];
-            if (hp != nullptr) x *= cvf_act_d1(a.act_b2, hp[(int64_t)i * CVF_TILE + lane]);
-          } else if (i == a.Ki && part == 0) {
-            x = 1.0f;   // the bias column: [h ; 1] (the tangent part has [tdot ; 0])
-          }
-        }
-        Bs[rr * kGP + lane] = x;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int ks = 0; ks < 64; ks += 4) {
-        const int kf = ks + kq;
-        const float a0 = As[(wm + col) * kGP + kf], a1 = As[(wm + 16 + col) * kGP + kf];
-        const float b0 = Bs[(wn + col) * kGP + kf], b1 = Bs[(wn + 16 + col) * kGP + kf];
-        acc[0][0] = mfma4(a0, b0, acc[0][0]);
-        acc[0][1] = mfma4(a0, b1, acc[0][1]);
-        acc[1][0] = mfma4(a1, b0, acc[1][0]);
-        acc[1][1] = mfma4(a1, b1, acc[1][1]);
-      }
-      __syncthreads();
-    }
-  }
-
-  float* row = slab + (int64_t)rho * a.n_params;
-  const int wo = mlp.w_off[net][a.layer], bo = mlp.b_off[net][a.layer];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int o = o0 + wm + 16 * i + 4 * kq + r;
-        const int c = i0 + wn + 16 * j + col;
-        if (o >= a.Mo || c > a.Ki) continue;
-        if (c < a.Ki) row[wo + (int64_t)o * a.Ki + c] = acc[i][j][r];
-        else row[bo + o] = acc[i][j][r];
-      }
+  const int lane = threadIdx.x & 63, net = blockIdx.z;
+  float* row = slab + (int64_t)blockIdx.x * a.n_params;
+  g64_wgrad_block(
+      As, Bs, a.Mo, a.Ki, a.n_tiles, a.T, a.B, a.rows, a.a2.p != nullptr ? 2 : 1, row + mlp.w_off[net][a.layer],
+      row + mlp.b_off[net][a.layer],
+      [&](int64_t tile, int part, int o) { return at(part == 0 ? a.a1 : a.a2, net, tile, o)[lane]; },
+      [&](int64_t tile, int part, int i) {   // the tangent part: sigma'(b2h) .* b2
+        float x = at(part == 0 ? a.b1 : a.b2, net, tile, i)[lane];
+        if (part == 1 && a.b2h.p != nullptr) x *= cvf_act_d1(a.act_b2, at(a.b2h, net, tile, i)[lane]);
+        return x;
+      });
 }
 
 // alpha = d loss / d y per frame (and gamma = d loss / d (q . g) in generator mode); the layout of `coef` as cvf_ef_backward
@@ -248,30 +138,19 @@ __global__ __launch_bounds__(64) void efg_coef_kernel(EfgCoefArgs a, const float
   const bool valid = frame < a.B;
   const int64_t fc = valid ? frame : a.B - 1;
   const float wb = valid ? w[fc] : 0.0f;
-  const double* gS1 = coef;
-  const double* gS2 = coef + k;
-  const double* gEt = coef + k + k * k;
-  const double* gS1l = coef + 2 * k + k * k;
-  const double* gS2l = coef + 3 * k + k * k;
   const float* yb = y_tiled + t0 * k * CVF_TILE + lane;
   float alpha, gamma = 0.0f;
   if (a.lag_idx == 0) {
+    const double* gS1 = coef;
+    const double* gS2 = coef + k;
+    const double* gEt = coef + k + k * k;
     double s = gS1[net];
     for (int j = 0; j < k; ++j) s += (j == net ? 2.0 : 1.0) * gS2[net * k + j] * (double)yb[j * CVF_TILE];
     alpha = (float)((double)wb * s);
     gamma = (float)(2.0 * (double)wb * gEt[net]);
   } else {
     const float* yl = y_tiled + (a.T + t0) * k * CVF_TILE + lane;
-    const double diff = (double)yl[net * CVF_TILE] - (double)yb[net * CVF_TILE];
-    const double tterm = 2.0 * (double)wb * gEt[net] * diff;
-    if (pass == 0) {
-      double s = gS1[net];
-      for (int j = 0; j < k; ++j) s += (j == net ? 2.0 : 1.0) * gS2[net * k + j] * (double)yb[j * CVF_TILE];
-      alpha = (float)((double)wb * s - tterm);
-    } else {
-      const float wlg = valid ? w_lag[fc] : 0.0f;
-      alpha = (float)((double)wlg * (gS1l[net] + 2.0 * gS2l[net] * (double)yl[net * CVF_TILE]) + tterm);
-    }
+    alpha = (float)g64_transfer_grad(coef, k, net, yb, yl, pass != 0, wb, pass && valid ? w_lag[fc] : 0.0f);
   }
   at(a.alpha, net, tile, 0)[lane] = alpha;
   if (a.lag_idx == 0) at(a.gamma, net, tile, 0)[lane] = gamma;
@@ -358,30 +237,9 @@ const char* efg_why(const cvf_mlp_desc* mlp) {
     return buf;
   }
   if (mlp->dims[mlp->n_layers] != 1) return "the nets' output must be a scalar";
-  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
-    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
-    return buf;
-  }
-  for (int l = 1; l < mlp->n_layers; ++l)
-    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
-      snprintf(buf, sizeof buf, "hidden layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
-      return buf;
-    }
-  for (int l = 0; l < mlp->n_layers; ++l) {
-    const int act = mlp->act[l];
-    if (act < CVF_ACT_NONE || act > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
-    if (l == mlp->n_layers - 1 && act != CVF_ACT_NONE) return "an activation after the output layer";
-  }
-  int64_t n = 0;
-  for (int l = 0; l < mlp->n_layers; ++l) n += (int64_t)mlp->dims[l + 1] * (mlp->dims[l] + 1);
-  if (n * mlp->n_nets != mlp->n_params) return "the flat buffer holds parameters outside the nets";
-  return nullptr;
-}
-
-int64_t efg_rows(const cvf_mlp_desc* mlp, int64_t n_tiles) {
-  int64_t r = kSlabBytes / (4 * (int64_t)(mlp->n_params > 0 ? mlp->n_params : 1));
-  r = r < 1 ? 1 : r > kMaxRows ? kMaxRows : r;
-  return n_tiles < r ? (n_tiles < 1 ? 1 : n_tiles) : r;
+  const char* why = g64_why(mlp, mlp->n_layers, G64Chain{2, "hidden layer", "nets", true, false}, buf, sizeof buf);
+  if (why != nullptr) return why;
+  return mlp->act[mlp->n_layers - 1] != CVF_ACT_NONE ? "an activation after the output layer" : nullptr;
 }
 
 int launch_layer(const cvf_mlp_desc* mlp, const float* theta, const EfgLayerArgs& a, int64_t n_tiles, hipStream_t s) {
@@ -414,7 +272,7 @@ extern "C" int cvf_ef_general_supported(const cvf_mlp_desc* mlp) {
 
 extern "C" int64_t cvf_ef_general_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles) {
   if (efg_why(mlp) != nullptr) return 0;
-  return efg_rows(mlp, n_tiles);
+  return g64_rows(mlp, n_tiles);
 }
 
 extern "C" int64_t cvf_ef_general_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int lag_idx) {
@@ -475,7 +333,7 @@ extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc
   const int NH = mlp->n_layers - 1, k = mlp->n_nets, D = mlp->dims[0];
   const int64_t T = cvf_ntiles(B), nt = gen ? T : 2 * T;
   const EfgLayout L = efg_layout(mlp, nt, gen);
-  const int R = (int)efg_rows(mlp, nt);
+  const int R = (int)g64_rows(mlp, nt);
   const EfgView feat{(float*)feat_tiled, (int64_t)D * CVF_TILE, 0};
   const EfgView qv{(float*)q_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
   auto H = [&](int l) { return img(saved, L.h[l], nt, mlp->dims[l + 1]); };

@@ -18,7 +18,6 @@
 // No atomics.  Nothing is read from scratch that the same call did not write, apart from the hand-off from
 // cvf_regae_general_forward to cvf_regae_general_backward_reuse (the images a_0..a_{L-1} and the chain's output).
 #include "aeg_kernels.hpp"
-#include <stdio.h>
 
 int cvf_slab_reduce_impl(const float* slab, int64_t n_rows, int64_t n_params, float* grad, const float* mask,
                          const cvf_adam_args* adam, void* stream, const double* pair_partial = nullptr, int n_pair = 0,
@@ -105,24 +104,9 @@ __global__ __launch_bounds__(256) void regaeg_out_kernel(float* __restrict__ out
     if (!a.with_grad) continue;
     float zb = 0.0f;
     if (a.coef != nullptr && valid) {
-      const int K = a.K;
-      const float* yb = a.y_in + t0 * K * CVF_TILE + lane;
-      const float* yl = a.y_in + (a.T + t0) * K * CVF_TILE + lane;
-      const double* gS1 = a.coef;
-      const double* gS2 = a.coef + K;
-      const double* gT = a.coef + K + K * K;
-      const double* gS1l = a.coef + 2 * K + K * K;
-      const double* gS2l = a.coef + 3 * K + K * K;
-      const double diff = (double)yl[i * CVF_TILE] - (double)yb[i * CVF_TILE];
-      const double tterm = 2.0 * (double)wraw * gT[i] * diff;
-      double g;
-      if (!lagged) {
-        double s1 = gS1[i];
-        for (int j = 0; j < K; ++j) s1 += (j == i ? 2.0 : 1.0) * gS2[i * K + j] * (double)yb[j * CVF_TILE];
-        g = (double)wraw * s1 - tterm;
-      } else {
-        g = (double)a.w_lag[frame] * (gS1l[i] + 2.0 * gS2l[i] * (double)yl[i * CVF_TILE]) + tterm;
-      }
+      const float* yb = a.y_in + t0 * a.K * CVF_TILE + lane;
+      const float* yl = a.y_in + (a.T + t0) * a.K * CVF_TILE + lane;
+      const double g = g64_transfer_grad(a.coef, a.K, i, yb, yl, lagged, wraw, lagged ? a.w_lag[frame] : 0.0f);
       zb = (float)(a.head_scale * g) * cvf_act_d1(a.act, y);
     }
     op[o] = zb;
@@ -180,7 +164,7 @@ RegaegLayout regaeg_layout(const cvf_mlp_desc* mlp, int64_t T) {
     pos += per * wmax;
   }
   L.slab = pos;
-  pos += aeg_rows(mlp, 2 * T) * mlp->n_params;
+  pos += g64_rows(mlp, 2 * T) * mlp->n_params;
   L.partial = (pos + 1) & ~(int64_t)1;
   L.total = L.partial + 4 * T;
   return L;
@@ -194,17 +178,11 @@ const char* regaeg_why(const cvf_mlp_desc* mlp, int K, int n_enc_layers, bool wi
     snprintf(buf, sizeof buf, "%d nets: one chain is expected", mlp->n_nets);
     return buf;
   }
-  if (mlp->n_layers < 2 || mlp->n_layers > CVF_MAX_LAYERS) {
-    snprintf(buf, sizeof buf, "%d layers: 2 to %d are supported", mlp->n_layers, CVF_MAX_LAYERS);
-    return buf;
-  }
+  const char* why = g64_why(mlp, mlp->n_layers, G64Chain{2, "layer", "chain", true, true}, buf, sizeof buf);
+  if (why != nullptr) return why;
   const int L = mlp->n_layers;
   if (K < 0 || K > CVF_MAX_NETS) {
     snprintf(buf, sizeof buf, "K = %d regulariser heads: 0 to %d are supported", K, CVF_MAX_NETS);
-    return buf;
-  }
-  if (mlp->dims[0] < 1 || mlp->dims[0] > kMaxD0) {
-    snprintf(buf, sizeof buf, "%d input features: 1 to %d are supported", mlp->dims[0], kMaxD0);
     return buf;
   }
   if (mlp->dims[L] != mlp->dims[0] + K) {
@@ -212,25 +190,6 @@ const char* regaeg_why(const cvf_mlp_desc* mlp, int K, int n_enc_layers, bool wi
              mlp->dims[L]);
     return buf;
   }
-  for (int l = 1; l < L; ++l)
-    if (mlp->dims[l] < 1 || mlp->dims[l] > kMaxWidth) {
-      snprintf(buf, sizeof buf, "layer %d is %d wide: 1 to %d units are supported", l, mlp->dims[l], kMaxWidth);
-      return buf;
-    }
-  for (int l = 0; l < L; ++l)   // aeg_wgrad_kernel's 64 x 64 blocks of [W_l | b_l] are its grid.y
-    if ((int64_t)((mlp->dims[l + 1] + 63) / 64) * ((mlp->dims[l] + 1 + 63) / 64) > 65535) {
-      snprintf(buf, sizeof buf, "layer %d (%d x %d) has more than 65535 blocks of 64 x 64 weights", l, mlp->dims[l + 1], mlp->dims[l]);
-      return buf;
-    }
-  for (int l = 0; l < L; ++l)
-    if (mlp->act[l] < CVF_ACT_NONE || mlp->act[l] > CVF_ACT_SOFTPLUS) return "an activation code outside include/cvf.h";
-  int64_t n = 0;
-  for (int l = 0; l < L; ++l) n += (int64_t)mlp->dims[l + 1] * (mlp->dims[l] + 1);
-  if (n != mlp->n_params) return "the flat buffer holds parameters outside the chain";
-  for (int l = 0; l < L; ++l)
-    if (mlp->w_off[0][l] < 0 || mlp->w_off[0][l] + (int64_t)mlp->dims[l + 1] * mlp->dims[l] > n || mlp->b_off[0][l] < 0 ||
-        mlp->b_off[0][l] + (int64_t)mlp->dims[l + 1] > n)
-      return "a layer's parameters lie outside the flat buffer";
   if (!with_encoder) return nullptr;
   if (n_enc_layers < 1 || n_enc_layers >= L) {
     snprintf(buf, sizeof buf, "n_enc_layers=%d out of range (1 to %d)", n_enc_layers, L - 1);
@@ -339,7 +298,7 @@ int regaeg_backward_impl(const cvf_mlp_desc* mlp, const float* theta, const floa
   o.y_in = y_tiled;
   if (regaeg_out(c, o, step_count)) return -1;
 
-  const int R = (int)aeg_rows(mlp, c.NT);
+  const int R = (int)g64_rows(mlp, c.NT);
   float* slab = scratch + c.lay.slab;
   for (int l = L - 1; l >= 0; --l) {
     {  // layer l's gradient from zbar_{l+1} and a_l

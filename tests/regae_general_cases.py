@@ -134,7 +134,7 @@ def n_tiles(B):
 
 
 def slab_rows(d, tiles):
-    """aeg_rows: min(tiles, 256, 128 MiB / (4 n_params)), at least 1."""
+    """g64_rows (csrc/cvf_gemm64.hpp): min(tiles, 256, 128 MiB / (4 n_params)), at least 1."""
     return max(1, min(tiles, MAX_ROWS, SLAB_BYTES // (4 * A.n_params(d))))
 
 
