@@ -32,7 +32,7 @@ import math
 import os
 import types
 from abc import ABC, abstractmethod
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import pandas as pd
@@ -539,6 +539,38 @@ class _FlatParams:
                        "cvf_ef_pack")
 
 
+class _SharedTrunkFlat:
+    """Flat buffer of k scalar nets whose first ``n_shared`` Linear layers are ONE set of parameters (csrc/ef_general.hip:
+    cvf_ef_general_shared_*): the trunk's layers once, then net by net the layers from ``n_shared`` on.  No module aliases it - the
+    owner writes ``theta`` and reads ``grad`` (RegAutoEncoderTask's generator-mode regulariser: :class:`_RegGenerator`)."""
+
+    def __init__(self, dims, acts, k, n_shared, device):
+        L = len(dims) - 1
+        d = _hip.MLPDesc()
+        d.n_nets, d.n_layers = k, L
+        for l in range(L):
+            d.dims[l], d.dims[l + 1], d.act[l] = dims[l], dims[l + 1], int(acts[l])
+        pos = 0
+        for l in range(n_shared):
+            for i in range(k):
+                d.w_off[i][l], d.b_off[i][l] = pos, pos + dims[l + 1] * dims[l]
+            pos += dims[l + 1] * (dims[l] + 1)
+        for i in range(k):
+            for l in range(n_shared, L):
+                d.w_off[i][l], d.b_off[i][l] = pos, pos + dims[l + 1] * dims[l]
+                pos += dims[l + 1] * (dims[l] + 1)
+        d.n_params = pos
+        self.desc, self.n, self.n_shared, self.packed = d, pos, n_shared, None
+        self.theta = torch.zeros(pos, device=device, dtype=torch.float32)
+        self.grad = torch.zeros(pos, device=device, dtype=torch.float32)
+
+    def grad_views(self):
+        return []
+
+    def repack(self):
+        pass
+
+
 class _FusedOptimizer:
     """``optimizer`` attribute of the tasks: Adam / SGD as ONE kernel over the flat buffer (same update rule and
     defaults as the ``torch.optim`` objects built at core.py:163-166), with the parts of the ``torch.optim.Optimizer``
@@ -784,6 +816,7 @@ class _EFRoute(NamedTuple):
     align_inside: bool   # the forward launch can solve the alignment itself (used when the batch is not already aligned)
     unit_rows: bool      # ef16 transfer mode: the paired front launch that leaves the units' rows of the time-lagged sums
     backward: tuple      # (call name = C function, takes packed, takes w_lag, takes q) of the backward launch
+    shared: Optional[int] = None   # general route of an inner task whose nets share their first `shared` layers (cvf_ef_general_shared_*)
 
 
 class _EFWorkspace:
@@ -791,7 +824,7 @@ class _EFWorkspace:
 
     def __init__(self, B, k, d_r, n_params, lag, mlp_desc, device, route):
         lib = _hip.lib()
-        ef16, general = route.kind == "ef16", route.kind == "general"
+        ef16, general, ns = route.kind == "ef16", route.kind == "general", route.shared
         T = _hip.ntiles(B)
         Tt = 2 * T if lag > 0 else T
         f32 = dict(device=device, dtype=torch.float32)
@@ -819,10 +852,12 @@ class _EFWorkspace:
         self._k1_scratch, self.k1_scratch_checked = [None, None], False   # large-molecule alignment scratch, sized on first use
         # hidden activations handed from the forward kernel to the backward kernel (0 floats: shape without hand-off)
         # (the general route, csrc/ef_general.hip: activations, the sweep of g, the tangent chain and the adjoints of every layer)
-        n_saved = (lib.cvf_ef_general_saved_floats(mlp_desc, Tt, lag) if general else
+        n_saved = (lib.cvf_ef_general_shared_saved_floats(mlp_desc, Tt, ns) if ns is not None else
+                   lib.cvf_ef_general_saved_floats(mlp_desc, Tt, lag) if general else
                    lib.cvf_ef16_saved_floats(mlp_desc, Tt) if ef16 else lib.cvf_ef_saved_floats(mlp_desc, Tt))
         self.saved = torch.empty(n_saved, **f32) if n_saved > 0 else None
-        self.slab_rows = lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt)
+        self.slab_rows = (lib.cvf_ef_general_shared_slab_rows(mlp_desc, Tt, ns) if ns is not None else
+                          lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt))
         self.slab = torch.empty(self.slab_rows * n_params, **f32)
         # the 16-frame step at this batch size: > 0 - the front launch leaves the units' rows of the batch sums in `scratch` and
         # cvf_ef16_finish[_dp] adds them; 0 - it sums them itself (generator mode) / cvf_ef_stats does (transfer mode)
@@ -870,7 +905,7 @@ class EigenFunctionTask(TrainingTask):
                  learning_rate=0.01, load_model_filename=None, save_model_every_step=10, sort_eigvals_in_training=True,
                  k=1, batch_size=1000, num_epochs=10, test_ratio=0.2, optimizer_name='Adam',
                  device=torch.device('cuda'), plot_class=None, plot_frequency=0, verbose=True, debug_mode=True,
-                 general_nets=False):
+                 general_nets=False, _shared_trunk=None):
         super().__init__(traj_obj, pp_layer, model, model_path, learning_rate, load_model_filename, save_model_every_step,
                          k, batch_size, num_epochs, test_ratio, optimizer_name, device, plot_class, plot_frequency,
                          verbose, debug_mode)
@@ -889,11 +924,25 @@ class EigenFunctionTask(TrainingTask):
         self.lag_idx = int(lag_idx)
         if self.verbose:
             print('\nEigenfunctions:\n', self.model, flush=True)
-        self.init_model_and_optimizer()
+        # _shared_trunk (private: RegAutoEncoderTask's inner task, _RegGenerator): dict(dims, acts, n_shared) - the k nets share
+        # their first n_shared layers; `model` only states the architecture (it may live on the meta device), the parameters are
+        # the owner's, in a _SharedTrunkFlat, and the step runs the shared launches of csrc/ef_general.hip
+        self._n_shared = None
+        if _shared_trunk is not None:
+            st = _shared_trunk
+            if self.lag_idx != 0:
+                raise NotImplementedError("nets with a shared trunk: the transfer-mode shared step is not built (csrc/ef_general.hip)")
+            self._flat = _SharedTrunkFlat(st["dims"], st["acts"], k, st["n_shared"], self.device)
+            self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
+            if not _hip.lib().cvf_ef_general_shared_supported(self._flat.desc, st["n_shared"]):
+                raise NotImplementedError(f"{_hip.lib().cvf_last_error().decode()} (csrc/ef_general.hip: cvf_ef_general_shared_supported)")
+            self._n_shared = int(st["n_shared"])
+        else:
+            self.init_model_and_optimizer()
         # general_nets: shapes without a kernel instance run the per-layer launches of csrc/ef_general.hip (shapes WITH an
         # instance, padded layouts included, keep their kernels: the option changes nothing for them)
-        self._general = False
-        if self._flat.packed is None and general_nets:
+        self._general = self._n_shared is not None
+        if self._flat.packed is None and general_nets and not self._general:
             if not _hip.lib().cvf_ef_general_supported(self._flat.desc):
                 raise NotImplementedError(f"EigenFunctionTask(general_nets=True) on MI355X: {_hip.lib().cvf_last_error().decode()} "
                                           "(csrc/ef_general.hip: cvf_ef_general_supported)")
@@ -1048,7 +1097,7 @@ class EigenFunctionTask(TrainingTask):
         if self._route_record is None:
             lib, fl, pp, env, gen = _hip.lib(), self._flat, self._pp, os.environ, self.lag_idx == 0
             if self._general:      # (no kernel instance: none of the queries below would say yes)
-                r = _EFRoute("general", False, False, ("cvf_ef_general_backward", False, True, True))
+                r = _EFRoute("general", False, False, ("cvf_ef_general_backward", False, True, True), self._n_shared)
             elif (not self._pipeline and env.get("CVF_NO_EF16" if gen else "CVF_NO_EF16_TRANSFER") is None
                     and bool(lib.cvf_ef16_supported(fl.desc, pp))):
                 r = _EFRoute("ef16", True, not gen and env.get("CVF_NO_TRANSFER_ROWS") is None,
@@ -1247,6 +1296,9 @@ class EigenFunctionTask(TrainingTask):
         if inside:
             self._call("cvf_ef_align_fwd", lib.cvf_ef_align_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X),
                        P(X_lag), ws.B, P(ws.y), P(ws.saved), s)
+        elif self._route.shared is not None:
+            self._call("cvf_ef_general_shared_fwd", lib.cvf_ef_general_shared_fwd, fl.desc, self._route.shared, P(fl.theta), P(ws.feat),
+                       ws.Tt, P(ws.y), P(ws.g), P(ws.saved), s)
         elif self._route.kind == "general":
             self._call("cvf_ef_general_fwd", lib.cvf_ef_general_fwd, fl.desc, P(fl.theta), P(ws.feat), ws.Tt, P(ws.y), P(ws.g), P(ws.saved), s)
         else:
@@ -1265,9 +1317,14 @@ class EigenFunctionTask(TrainingTask):
         that sums the per-block partial gradients applies the Adam update in the same launch."""
         lib, fl, P = _hip.lib(), self._flat, _hip.ptr
         name, packed, lagged, q = self._route.backward
-        self._call(name, getattr(lib, name), self._cfg, fl.desc, P(fl.theta), *([P(fl.packed)] if packed else []), ws.B, P(w),
-                   *([P(w_lag)] if lagged else []), P(ws.feat_in), P(ws.y), *([P(ws.q)] if q else []), P(ws.coef), P(ws.slab),
-                   P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
+        if self._route.shared is not None:   # (generator mode: no w_lag; n_shared follows the description)
+            self._call("cvf_ef_general_shared_backward", lib.cvf_ef_general_shared_backward, self._cfg, fl.desc, self._route.shared,
+                       P(fl.theta), ws.B, P(w), P(ws.feat_in), P(ws.y), P(ws.q), P(ws.coef), P(ws.slab),
+                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
+        else:
+            self._call(name, getattr(lib, name), self._cfg, fl.desc, P(fl.theta), *([P(fl.packed)] if packed else []), ws.B, P(w),
+                       *([P(w_lag)] if lagged else []), P(ws.feat_in), P(ws.y), *([P(ws.q)] if q else []), P(ws.coef), P(ws.slab),
+                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
         local = self._local_only or self._grad_local
         # (the general route's gradient exceeds the peer-to-peer window of cvf_slab_reduce_dp: slab reduction + all-reduce)
         comm = None if local or self._route.kind == "general" else _dist.fused_comm()
@@ -1813,7 +1870,13 @@ class _EncGradPenalty:
     So it runs on the eigenfunction kernels: the encoder's parameters are gathered into the k-net layout, ``cvf_ef_mlp_fwd``
     (y, g = dy/dr) + ``cvf_metric_apply_stats`` (E_i = |g_i|^2 and the batch sums) give the term, ``cvf_ef_backward`` with the
     coefficient vector [0 .. eta_0 / W on the E entries .. 0] + ``cvf_slab_reduce`` give d(eta_0 term)/d(virtual parameters), and
-    the k copies of the shared layers are added back (fixed order) into the encoder's block of the flat gradient."""
+    the k copies of the shared layers are added back (fixed order) into the encoder's block of the flat gradient.
+
+    ``RegAutoEncoderTask(general_nets=True)`` and an encoder without such an instance (any hidden widths up to 4096, 1 to 11
+    hidden layers): the shared-trunk launches of csrc/ef_general.hip (``cvf_ef_general_shared_fwd`` / ``_backward``, DESIGN.md
+    section 4.12) in place of ``cvf_ef_mlp_fwd`` / ``cvf_ef_backward``.  The k virtual nets are described IN PLACE over the
+    encoder's block of the task's flat buffer - hidden layers shared, net i's output layer = row i of the last weight and entry i
+    of the last bias - so nothing is gathered, and the gradient of that block comes back as one vector."""
 
     def __init__(self, task):
         from .nn import _chain_layers
@@ -1846,16 +1909,29 @@ class _EncGradPenalty:
             src += list(range(n_shared)) + list(range(ed.w_off[0][L - 1] + i * h, ed.w_off[0][L - 1] + (i + 1) * h)) + [ed.b_off[0][L - 1] + i]
             pos += per
         d.n_params = pos
-        n_pack = _hip.lib().cvf_ef_pack_floats(d)
-        if k > _hip.MAX_NETS or n_pack <= 0:
+        n_pack = _hip.lib().cvf_ef_pack_floats(d) if k <= _hip.MAX_NETS else 0
+        self.shared = None
+        if n_pack <= 0 and task.general_nets:   # no instance: the nets in place, on the shared-trunk launches
+            for i in range(k):
+                for l in range(L - 1):
+                    d.w_off[i][l], d.b_off[i][l] = ed.w_off[0][l], ed.b_off[0][l]
+                d.w_off[i][L - 1], d.b_off[i][L - 1] = ed.w_off[0][L - 1] + i * dims[L - 1], ed.b_off[0][L - 1] + i
+            d.n_params = pos = ed.b_off[0][L - 1] + k       # the encoder's block of the flat buffer
+            if not _hip.lib().cvf_ef_general_shared_supported(d, L - 1):
+                raise NotImplementedError(f"eta[0] on MI355X (general_nets=True), encoder widths {dims}: "
+                                          f"{_hip.lib().cvf_last_error().decode()}")
+            self.shared = L - 1
+        elif n_pack <= 0:
             raise NotImplementedError(
                 f"eta[0] on MI355X runs on the eigenfunction kernels: encoder widths {dims} need 1 to 3 equal hidden layers of one of "
-                f"{_hip.EF_HIDDEN_WIDTHS} units and at most {_hip.MAX_NETS} latent components")
+                f"{_hip.EF_HIDDEN_WIDTHS} units and at most {_hip.MAX_NETS} latent components (pass general_nets=True to "
+                "RegAutoEncoderTask for other encoders: the shared-trunk kernels of csrc/ef_general.hip)")
         self.desc, self.n, self.per, self.n_shared, self.h = d, pos, per, n_shared, h
         self.last_w, self.last_b = int(ed.w_off[0][L - 1]), int(ed.b_off[0][L - 1])
-        self.src = torch.tensor(src, device=dev, dtype=torch.long)
-        self.theta = torch.zeros(pos, device=dev, dtype=torch.float32)
-        self.packed = torch.zeros(n_pack, device=dev, dtype=torch.float32)
+        if self.shared is None:
+            self.src = torch.tensor(src, device=dev, dtype=torch.long)
+            self.theta = torch.zeros(pos, device=dev, dtype=torch.float32)
+            self.packed = torch.zeros(n_pack, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(pos, device=dev, dtype=torch.float32)
         self.ones = torch.ones(dims[0], device=dev, dtype=torch.float32)
         self.pp = identity_desc(dims[0])
@@ -1872,8 +1948,12 @@ class _EncGradPenalty:
             lib, k, d_r, dev = _hip.lib(), self.k, self.d_r, self.task.device
             T = _hip.ntiles(B)
             f32, f64 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.float64)
-            n_saved = lib.cvf_ef_saved_floats(self.desc, T)
-            rows = lib.cvf_ef_backward_slab_rows(T)
+            if self.shared is not None:
+                n_saved = lib.cvf_ef_general_shared_saved_floats(self.desc, T, self.shared)
+                rows = lib.cvf_ef_general_shared_slab_rows(self.desc, T, self.shared)
+            else:
+                n_saved = lib.cvf_ef_saved_floats(self.desc, T)
+                rows = lib.cvf_ef_backward_slab_rows(T)
             ws = dict(T=T, feat=torch.empty(T * d_r * _hip.TILE, **f32), y=torch.empty(T * k * _hip.TILE, **f32),
                       g=torch.empty(T * k * d_r * _hip.TILE, **f32), q=torch.empty(T * k * d_r * _hip.TILE, **f32),
                       e=torch.empty(T * k * _hip.TILE, **f32),
@@ -1893,11 +1973,16 @@ class _EncGradPenalty:
         fl, k = task._flat, self.k
         B = int(rows.shape[0])
         ws = self._workspace(B)
-        torch.index_select(fl.theta, 0, self.src, out=self.theta)
-        task._call("cvf_ef_pack", lib.cvf_ef_pack, self.desc, P(self.theta), P(self.packed), s)
+        if self.shared is None:
+            torch.index_select(fl.theta, 0, self.src, out=self.theta)
+            task._call("cvf_ef_pack", lib.cvf_ef_pack, self.desc, P(self.theta), P(self.packed), s)
         task._call("cvf_align_feature_fwd", lib.cvf_align_feature_fwd, self.pp, P(rows), B, P(ws["feat"]), None, None, None, s)
-        task._call("cvf_ef_mlp_fwd", lib.cvf_ef_mlp_fwd, self.desc, P(self.theta), P(self.packed), P(ws["feat"]), ws["T"], P(ws["y"]),
-                   P(ws["g"]), P(ws["saved"]), s)
+        if self.shared is not None:   # (the nets read the encoder's block of the flat buffer where it is)
+            task._call("cvf_ef_general_shared_fwd", lib.cvf_ef_general_shared_fwd, self.desc, self.shared, P(fl.theta), P(ws["feat"]),
+                       ws["T"], P(ws["y"]), P(ws["g"]), P(ws["saved"]), s)
+        else:
+            task._call("cvf_ef_mlp_fwd", lib.cvf_ef_mlp_fwd, self.desc, P(self.theta), P(self.packed), P(ws["feat"]), ws["T"], P(ws["y"]),
+                       P(ws["g"]), P(ws["saved"]), s)
         task._call("cvf_metric_apply", lib.cvf_metric_apply_stats, self.pp, P(rows), B, None, P(self.ones), k, P(ws["g"]), P(ws["q"]),
                    P(ws["e"]), None, None, self.cfg, P(w), P(ws["y"]), P(ws["scratch"]), P(ws["stats"]), None, None, s)
         st = ws["stats"]                                   # [W, S1(k), S2(i<=j), E(k)]
@@ -1908,6 +1993,13 @@ class _EncGradPenalty:
         if with_grad:
             ge = ws["coef"][k + k * k:2 * k + k * k]       # [gS1(k), gS2(k*k), gE(k), ...]: d(eta0 term)/dE_i = eta0 / W
             ge.copy_((eta0 / st[0]).expand(k))
+            if self.shared is not None:
+                task._call("cvf_ef_general_shared_backward", lib.cvf_ef_general_shared_backward, self.cfg, self.desc, self.shared,
+                           P(fl.theta), B, P(w), P(ws["feat"]), P(ws["y"]), P(ws["q"]), P(ws["coef"]), P(ws["slab"]), None,
+                           P(ws["saved"]), s)
+                task._call("cvf_slab_reduce", lib.cvf_slab_reduce, P(ws["slab"]), ws["rows"], self.n, P(self.grad), None, s)
+                fl.grad[:self.n] += self.grad     # the encoder's block, its shared layers summed over the nets inside the launch
+                return term
             task._call("cvf_ef_backward", lib.cvf_ef_backward, self.cfg, self.desc, P(self.theta), P(self.packed), B, P(w), None,
                        P(ws["feat"]), P(ws["y"]), P(ws["q"]), P(ws["coef"]), P(ws["slab"]), None, P(ws["saved"]), s)
             task._call("cvf_slab_reduce", lib.cvf_slab_reduce, P(ws["slab"]), ws["rows"], self.n, P(self.grad), None, s)
@@ -1929,7 +2021,12 @@ class _RegGenerator:
     zero-padded to one kernel width, and handed to an inner ``EigenFunctionTask`` - so the step runs on that task's kernels
     (alignment derivative, forward, q = J J^T g, batch sums, loss tail, backward), whichever it picks for the shape.  The
     gradient with respect to the virtual parameters goes back to the module's parameters through the (tiny) map that built
-    them, by autograd on the host-side torch graph: shared layers summed over i, the merged layer by the product rule."""
+    them, by autograd on the host-side torch graph: shared layers summed over i, the merged layer by the product rule.
+
+    ``RegAutoEncoderTask(general_nets=True)`` and a chain without such a layout (1 to 11 hidden layers of up to 4096 units, any
+    of the six activations): the chains are laid out UNPADDED with the trunk - the encoder's hidden layers - stored once
+    (:class:`_SharedTrunkFlat`), and the inner task runs the shared-trunk launches of csrc/ef_general.hip (DESIGN.md section
+    4.12): the trunk runs forward once, and its gradient comes back as one vector, already summed over the nets."""
 
     def __init__(self, task, beta):
         from .nn import _chain_layers
@@ -1948,21 +2045,32 @@ class _RegGenerator:
         hidden = [lin.out_features for lin, _ in self.enc[:-1]] + [lin.out_features for lin, _ in self.regs[0][:-1]]
         for r in self.regs:
             assert [lin.out_features for lin, _ in r] == [lin.out_features for lin, _ in self.regs[0]], "regulariser nets differ in shape"
-        widths = [w for w in _hip.ef_widths(len(hidden)) if w >= max(hidden)] if 1 <= len(hidden) <= 5 else []
-        if not widths or self.K > _hip.MAX_NETS:
-            raise NotImplementedError(
-                f"generator-mode regulariser on MI355X: the chain regulariser o encoder has hidden widths {hidden}; the eigenfunction "
-                f"kernels take 1 to 5 hidden layers of at most {max(_hip.EF_HIDDEN_WIDTHS)} units and at most {_hip.MAX_NETS} nets "
-                "(use lag_tau_reg > 0 - the transfer operator - for other shapes)")
-        self.H = H = widths[0]
         from .nn import ACT_SIGMOID, ACT_SOFTPLUS
-        if act0 in (ACT_SIGMOID, ACT_SOFTPLUS) and any(h != H for h in hidden):   # (zero padding needs act(0) = 0)
-            raise NotImplementedError(f"generator-mode regulariser on MI355X with Sigmoid / Softplus: every hidden width of the chain "
-                                      f"{hidden} must be one kernel width (no zero padding)")
-        self.pdims = [d_r] + [H] * len(hidden) + [1]
+        widths = [w for w in _hip.ef_widths(len(hidden)) if w >= max(hidden)] if 1 <= len(hidden) <= 5 else []
+        why = None
+        if not widths or self.K > _hip.MAX_NETS:
+            why = (f"generator-mode regulariser on MI355X: the chain regulariser o encoder has hidden widths {hidden}; the eigenfunction "
+                   f"kernels take 1 to 5 hidden layers of at most {max(_hip.EF_HIDDEN_WIDTHS)} units and at most {_hip.MAX_NETS} nets "
+                   "(use lag_tau_reg > 0 - the transfer operator - for other shapes)")
+        elif act0 in (ACT_SIGMOID, ACT_SOFTPLUS) and any(h != widths[0] for h in hidden):   # (zero padding needs act(0) = 0)
+            why = (f"generator-mode regulariser on MI355X with Sigmoid / Softplus: every hidden width of the chain "
+                   f"{hidden} must be one kernel width (no zero padding)")
+        # general_nets: a chain without a padded layout runs unpadded, its trunk stored once, on the shared-trunk launches
+        self.shared = why is not None and bool(task.general_nets)
+        if why is not None and not self.shared:
+            raise NotImplementedError(why + ". Pass general_nets=True to RegAutoEncoderTask to run the chain on the shared-trunk "
+                                      "kernels of csrc/ef_general.hip.")
+        self.H = H = None if self.shared else widths[0]
+        self.pdims = [d_r] + (hidden if self.shared else [H] * len(hidden)) + [1]
         act_module = next(mod for mod in m.reg[0]._modules.values() if not isinstance(mod, torch.nn.Linear))
-        with torch.random.fork_rng(devices=[]):   # (the virtual nets' initial values are overwritten: leave the caller's RNG stream alone)
-            model = EigenFunctions(self.pdims, self.K, copy.deepcopy(act_module))
+        shared_trunk = None
+        if self.shared:   # (the inner task keeps the parameters in a _SharedTrunkFlat: the model only states the architecture)
+            shared_trunk = dict(dims=self.pdims, acts=[act0] * len(hidden) + [0], n_shared=Le - 1)
+            with torch.device("meta"):
+                model = EigenFunctions(self.pdims, self.K, copy.deepcopy(act_module))
+        else:
+            with torch.random.fork_rng(devices=[]):   # (the virtual nets' initial values are overwritten: leave the caller's RNG stream alone)
+                model = EigenFunctions(self.pdims, self.K, copy.deepcopy(act_module))
         tok = np.zeros((4,) + tuple(task._traj_host.shape[1:]), dtype=np.float32)
 
         class _Tok:
@@ -1976,9 +2084,15 @@ class _RegGenerator:
         import tempfile
         # (its own scratch log directory: a second SummaryWriter must not open event files in the user's model_path)
         self._logdir = tempfile.mkdtemp(prefix="cvf_reg_generator_")
-        self.inner = EigenFunctionTask(_Tok, task.preprocessing_layer, model, self._logdir, g1 / g0, [float(v) for v in task._eig_w],
-                                       diag_coeff=None, beta=beta, lag_tau=0, learning_rate=task.learning_rate, k=self.K,
-                                       batch_size=task.batch_size, device=task.device, verbose=False, save_model_every_step=0)
+        try:
+            self.inner = EigenFunctionTask(_Tok, task.preprocessing_layer, model, self._logdir, g1 / g0, [float(v) for v in task._eig_w],
+                                           diag_coeff=None, beta=beta, lag_tau=0, learning_rate=task.learning_rate, k=self.K,
+                                           batch_size=task.batch_size, device=task.device, verbose=False, save_model_every_step=0,
+                                           _shared_trunk=shared_trunk)
+        except NotImplementedError as exc:
+            if not self.shared:
+                raise
+            raise NotImplementedError(f"generator-mode regulariser on MI355X (general_nets=True), chain widths {self.pdims}: {exc}") from None
         try:   # nothing is ever logged or stepped through the inner task: close its writer, drop the directory
             close = getattr(self.inner.writer, "close", None)
             if close is not None:
@@ -1999,6 +2113,12 @@ class _RegGenerator:
         """The virtual parameters as a (differentiable) function of the module's: flat, in the inner model's order."""
         pd, out = self.pdims, []
         We, be = self.enc[-1][0].weight, self.enc[-1][0].bias
+        if self.shared:   # the trunk once, then per net the merged layer and the regulariser's remaining layers (_SharedTrunkFlat)
+            out = [t for lin, _ in self.enc[:-1] for t in (lin.weight.reshape(-1), lin.bias)]
+            for r in self.regs:
+                out += [(r[0][0].weight @ We).reshape(-1), r[0][0].weight @ be + r[0][0].bias]
+                out += [t for lin, _ in r[1:] for t in (lin.weight.reshape(-1), lin.bias)]
+            return torch.cat(out)
         for i in range(self.K):
             r = self.regs[i]
             layers = [(lin.weight, lin.bias) for lin, _ in self.enc[:-1]]
@@ -2054,12 +2174,18 @@ class RegAutoEncoderTask(TrainingTask):
     parameters and activations do not fit that kernel's 160 KiB of LDS runs the same three calls layer by layer instead
     (``cvf_regae_general_*``: widths up to 4096 units, the same outputs); a chain past both routes is refused with
     NotImplementedError at construction.
+
+    ``general_nets`` (not in the reference; default False): the two parts that run on the eigenfunction task's kernels - the
+    generator-mode regulariser and ``eta[0]`` - take shapes without a kernel instance too (chains regulariser o encoder and
+    encoders of 1 to 11 hidden layers of up to 4096 units, any of the six activations), on the shared-trunk launches of
+    csrc/ef_general.hip.  Shapes with an instance keep it, bit for bit; without the option other
+    shapes raise NotImplementedError at construction, as before.
     """
 
     def __init__(self, traj_obj, pp_layer, model, model_path, eig_weights=[], learning_rate=0.01, load_model_filename=None,
                  save_model_every_step=10, batch_size=1000, num_epochs=10, test_ratio=0.2, optimizer_name='Adam', alpha=1.0,
                  gamma=[0.0, 0.0], eta=[0.0, 0.0, 0.0], lag_tau_ae=0, lag_tau_reg=0, beta=1.0, device=torch.device('cuda'),
-                 plot_class=None, plot_frequency=0, freeze_encoder=False, verbose=True, debug_mode=True):
+                 plot_class=None, plot_frequency=0, freeze_encoder=False, verbose=True, debug_mode=True, general_nets=False):
         super().__init__(traj_obj, pp_layer, model, model_path, learning_rate, load_model_filename, save_model_every_step,
                          model.encoded_dim, batch_size, num_epochs, test_ratio, optimizer_name, device, plot_class,
                          plot_frequency, verbose, debug_mode)
@@ -2071,6 +2197,9 @@ class RegAutoEncoderTask(TrainingTask):
         self._eig_w = eig_weights
         self._cvec = None
         self.freeze_encoder = freeze_encoder
+        # general_nets: the generator-mode regulariser and eta[0] on shapes without a kernel instance run the shared-trunk launches
+        # of csrc/ef_general.hip (shapes WITH an instance keep it: the option changes nothing for them), as EigenFunctionTask's
+        self.general_nets = bool(general_nets)
         self.traj_dt = traj_obj.dt
         lag_ae_idx, lag_idx = lag_tau_ae / self.traj_dt, lag_tau_reg / self.traj_dt
         assert abs(lag_ae_idx - int(lag_ae_idx)) < 1e-6 and abs(lag_idx - int(lag_idx)) < 1e-6, \

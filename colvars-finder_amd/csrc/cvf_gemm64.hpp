@@ -128,9 +128,11 @@ __device__ __forceinline__ void g64_walk(const f32x4 (&acc)[2][2], const G64Thre
 // rho + rows, ... in that order and, per tile, over `parts` operand pairs, of A (x) [B ; 1] with K = frames (the bias column
 // belongs to part 0).  ael(tile, part, o) / bel(tile, part, i) = this lane's frame of row o < Mo / i < Ki.  Tiles T.. repeat
 // the frames of tiles 0..; frames past B contribute nothing: zero on both operands.
-template <class AElem, class BElem>
+// kNets (csrc/ef_general.hip, shared layers): the parts are those of several nets in a row, `per_net` each - part p belongs to net
+// p / per_net and is that net's part p % per_net, so the bias column belongs to every per_net-th part.  The callers decode p.
+template <bool kNets = false, class AElem, class BElem>
 __device__ __forceinline__ void g64_wgrad_block(float* As, float* Bs, int Mo, int Ki, int64_t n_tiles, int64_t T, int64_t B, int rows,
-                                                int parts, float* w_row, float* b_row, AElem&& ael, BElem&& bel) {
+                                                int parts, float* w_row, float* b_row, AElem&& ael, BElem&& bel, int per_net = 1) {
   const G64Thread t = g64_thread();
   const int rho = blockIdx.x;
   const int nbn = (Ki + 1 + 63) / 64;
@@ -149,7 +151,7 @@ __device__ __forceinline__ void g64_wgrad_block(float* As, float* Bs, int Mo, in
         float x = 0.0f;
         if (valid) {
           if (i < Ki) x = bel(tile, part, i);
-          else if (i == Ki && part == 0) x = 1.0f;   // the bias column: [h ; 1] (a second part has [. ; 0])
+          else if (i == Ki && (kNets ? (part & (per_net - 1)) == 0 : part == 0)) x = 1.0f;   // the bias column: [h ; 1] (a second part has [. ; 0]; per_net is 1 or 2)
         }
         Bs[rr * kGP + t.lane] = x;
       }

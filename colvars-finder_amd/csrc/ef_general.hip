@@ -23,6 +23,16 @@
 // All products run on v_mfma_f32_16x16x4_f32 (the 64 x 64 core of csrc/cvf_gemm64.hpp): fp32 operands, fp32 accumulation.
 // The hand-off between layers goes through the `saved` buffer in HBM (layout: efg_layout).  No atomics: every slab entry is
 // written by one thread, and the sum order of every entry is fixed by the grid, so two runs on the same inputs give the same bits.
+//
+// A SHARED TRUNK (cvf_ef_general_shared_*, generator mode): the k nets have their first n_shared Linear
+// layers in common - w_off[i][l] and b_off[i][l] are the same for every net i when l < n_shared, and the flat buffer holds those
+// blocks once (RegAutoEncoderTask: the chains regulariser_i o encoder, and the rows of the encoder's last layer).  Then
+//   h_l, l < n_shared  does not depend on the net: its forward launch has ONE net in grid z and writes one image, which every
+//                      later launch reads through a view of net stride 0;
+//   u, zdot, zbar, d   of the shared layers depend on the head and stay per net (grid z = k, the shared weights read in place);
+//   dW_l, l < n_shared = sum over the nets of the per-net products: one launch with one net in grid z, whose block walks, per
+//                      tile, the nets 0..k-1 in order into one accumulator and writes the slab entry once, at the shared offset.
+// n_shared = 0 is the launch list of the plain entries.
 #include "cvf_gemm64.hpp"
 
 namespace {
@@ -100,23 +110,27 @@ struct EfgGradArgs {
   int rows;         // slab rows R: row rho sums tiles rho, rho + R, ... in that order
   int act_b2;       // b2h.p != NULL: second B operand = sigma'(b2h) .* b2
   int64_t n_params;
+  int nets;         // nets whose products this block sums, blockIdx.z onwards: 1, or k for a shared layer (grid z = 1)
   EfgView a1, b1, a2, b2, b2h;   // a2.p == NULL: one part (transfer mode)
 };
 
 __global__ __launch_bounds__(256) void efg_wgrad_kernel(const cvf_mlp_desc mlp, EfgGradArgs a, float* __restrict__ slab) {
   __shared__ __attribute__((aligned(16))) float As[64 * kGP];   // [out row][frame]
   __shared__ __attribute__((aligned(16))) float Bs[64 * kGP];   // [in column][frame]
-  const int lane = threadIdx.x & 63, net = blockIdx.z;
+  const int lane = threadIdx.x & 63, net0 = blockIdx.z;
+  const int per = a.a2.p != nullptr ? 2 : 1, sh = per - 1;   // part p: net net0 + (p >> sh), that net's part p & sh
   float* row = slab + (int64_t)blockIdx.x * a.n_params;
-  g64_wgrad_block(
-      As, Bs, a.Mo, a.Ki, a.n_tiles, a.T, a.B, a.rows, a.a2.p != nullptr ? 2 : 1, row + mlp.w_off[net][a.layer],
-      row + mlp.b_off[net][a.layer],
-      [&](int64_t tile, int part, int o) { return at(part == 0 ? a.a1 : a.a2, net, tile, o)[lane]; },
+  g64_wgrad_block<true>(
+      As, Bs, a.Mo, a.Ki, a.n_tiles, a.T, a.B, a.rows, per * a.nets, row + mlp.w_off[net0][a.layer],
+      row + mlp.b_off[net0][a.layer],
+      [&](int64_t tile, int part, int o) { return at((part & sh) == 0 ? a.a1 : a.a2, net0 + (part >> sh), tile, o)[lane]; },
       [&](int64_t tile, int part, int i) {   // the tangent part: sigma'(b2h) .* b2
-        float x = at(part == 0 ? a.b1 : a.b2, net, tile, i)[lane];
-        if (part == 1 && a.b2h.p != nullptr) x *= cvf_act_d1(a.act_b2, at(a.b2h, net, tile, i)[lane]);
+        const int net = net0 + (part >> sh), sub = part & sh;
+        float x = at(sub == 0 ? a.b1 : a.b2, net, tile, i)[lane];
+        if (sub == 1 && a.b2h.p != nullptr) x *= cvf_act_d1(a.act_b2, at(a.b2h, net, tile, i)[lane]);
         return x;
-      });
+      },
+      per);
 }
 
 // alpha = d loss / d y per frame (and gamma = d loss / d (q . g) in generator mode); the layout of `coef` as cvf_ef_backward
@@ -184,12 +198,12 @@ __global__ __launch_bounds__(256) void efg_top_kernel(const cvf_mlp_desc mlp, co
 
 // ---- the `saved` buffer.  Generator mode (n_tiles = T): per hidden layer h_l, u_l (-> d_l), zdot_l (-> zbar_l), then alpha,
 // gamma.  Transfer mode (n_tiles = 2T): h_l per hidden layer, two ping-pong images of zbar (widest layer), alpha.
-// Every image is [net][tile][width][64].
+// Every image is [net][tile][width][64]; with a shared trunk the h_l of the shared layers are [tile][width][64], once.
 struct EfgLayout {
   int64_t h[CVF_MAX_LAYERS], u[CVF_MAX_LAYERS], z[CVF_MAX_LAYERS], zb[2], alpha, gamma, total;
 };
 
-EfgLayout efg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles, bool gen) {
+EfgLayout efg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles, bool gen, int n_shared = 0) {
   EfgLayout L = {};
   const int NH = mlp->n_layers - 1;
   const int64_t per = n_tiles * CVF_TILE * mlp->n_nets;   // floats of one row of every (net, tile)
@@ -197,7 +211,7 @@ EfgLayout efg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles, bool gen) {
   int maxH = 1;
   for (int l = 0; l < NH; ++l) {
     L.h[l] = pos;
-    pos += per * mlp->dims[l + 1];
+    pos += (l < n_shared ? per / mlp->n_nets : per) * mlp->dims[l + 1];
     maxH = mlp->dims[l + 1] > maxH ? mlp->dims[l + 1] : maxH;
   }
   if (gen) {
@@ -221,8 +235,8 @@ EfgLayout efg_layout(const cvf_mlp_desc* mlp, int64_t n_tiles, bool gen) {
   return L;
 }
 
-EfgView img(float* saved, int64_t off, int64_t n_tiles, int width) {
-  return EfgView{saved + off, (int64_t)width * CVF_TILE, n_tiles * width * CVF_TILE};
+EfgView img(float* saved, int64_t off, int64_t n_tiles, int width, bool shared = false) {
+  return EfgView{saved + off, (int64_t)width * CVF_TILE, shared ? 0 : n_tiles * width * CVF_TILE};
 }
 
 const char* efg_why(const cvf_mlp_desc* mlp) {
@@ -242,8 +256,70 @@ const char* efg_why(const cvf_mlp_desc* mlp) {
   return mlp->act[mlp->n_layers - 1] != CVF_ACT_NONE ? "an activation after the output layer" : nullptr;
 }
 
-int launch_layer(const cvf_mlp_desc* mlp, const float* theta, const EfgLayerArgs& a, int64_t n_tiles, hipStream_t s) {
-  dim3 grid((unsigned)n_tiles, (unsigned)((a.M + 63) / 64), (unsigned)mlp->n_nets);
+// The nets with their first n_shared layers in common: the shape checks of efg_why, then the flat buffer - the shared blocks
+// stated once by equal offsets, every block inside the buffer, no two blocks overlapping, and nothing else in it.
+const char* efg_why_shared(const cvf_mlp_desc* mlp, int n_shared) {
+  static thread_local char buf[200];
+  if (mlp == nullptr) return "no net description";
+  if (mlp->n_nets < 1 || mlp->n_nets > CVF_MAX_NETS) {
+    snprintf(buf, sizeof buf, "%d nets: 1 to %d are supported", mlp->n_nets, CVF_MAX_NETS);
+    return buf;
+  }
+  if (mlp->n_layers < 2 || mlp->n_layers > CVF_MAX_LAYERS) {
+    snprintf(buf, sizeof buf, "%d hidden layers: 1 to %d are supported", mlp->n_layers - 1, CVF_MAX_LAYERS - 1);
+    return buf;
+  }
+  const int L = mlp->n_layers, k = mlp->n_nets;
+  if (n_shared < 0 || n_shared > L - 1) {
+    snprintf(buf, sizeof buf, "n_shared = %d: 0 to %d (the hidden layers) can be shared", n_shared, L - 1);
+    return buf;
+  }
+  if (mlp->dims[L] != 1) return "the nets' output must be a scalar";
+  const char* why = g64_why(mlp, L, G64Chain{2, "hidden layer", "nets", false, true}, buf, sizeof buf);
+  if (why != nullptr) return why;
+  if (mlp->act[L - 1] != CVF_ACT_NONE) return "an activation after the output layer";
+  struct Block {
+    int64_t lo, hi;
+    int net, layer;
+  };
+  Block blk[2 * CVF_MAX_NETS * CVF_MAX_LAYERS];
+  int nb = 0;
+  int64_t n = 0;
+  for (int l = 0; l < L; ++l) {
+    const int64_t nw = (int64_t)mlp->dims[l + 1] * mlp->dims[l], nbias = mlp->dims[l + 1];
+    for (int i = 0; i < k; ++i) {
+      if (l < n_shared && i > 0) {
+        if (mlp->w_off[i][l] != mlp->w_off[0][l] || mlp->b_off[i][l] != mlp->b_off[0][l]) {
+          snprintf(buf, sizeof buf, "shared layer %d: net %d's offsets differ from net 0's", l, i);
+          return buf;
+        }
+        continue;
+      }
+      blk[nb++] = Block{mlp->w_off[i][l], mlp->w_off[i][l] + nw, i, l};
+      blk[nb++] = Block{mlp->b_off[i][l], mlp->b_off[i][l] + nbias, i, l};
+      n += nw + nbias;
+    }
+  }
+  if (n != mlp->n_params) {
+    snprintf(buf, sizeof buf, "the flat buffer holds %lld parameters, the nets with %d shared layers %lld", (long long)mlp->n_params,
+             n_shared, (long long)n);
+    return buf;
+  }
+  for (int a = 0; a < nb; ++a)
+    if (blk[a].lo < 0 || blk[a].hi > n) return "a layer's parameters lie outside the flat buffer";
+  for (int a = 0; a < nb; ++a)
+    for (int b = a + 1; b < nb; ++b)
+      if (blk[a].lo < blk[b].hi && blk[b].lo < blk[a].hi) {
+        snprintf(buf, sizeof buf, "the parameters of net %d, layer %d overlap those of net %d, layer %d", blk[a].net, blk[a].layer,
+                 blk[b].net, blk[b].layer);
+        return buf;
+      }
+  return nullptr;
+}
+
+// nets: grid z - all of them, or 1 for the forward launch of a shared layer
+int launch_layer(const cvf_mlp_desc* mlp, const float* theta, const EfgLayerArgs& a, int64_t n_tiles, hipStream_t s, int nets) {
+  dim3 grid((unsigned)n_tiles, (unsigned)((a.M + 63) / 64), (unsigned)nets);
   hipLaunchKernelGGL(efg_layer_kernel, grid, dim3(256), 0, s, *mlp, theta, a);
   return cvf_check_launch("efg_layer_kernel");
 }
@@ -280,29 +356,29 @@ extern "C" int64_t cvf_ef_general_saved_floats(const cvf_mlp_desc* mlp, int64_t 
   return efg_layout(mlp, n_tiles, lag_idx == 0).total;
 }
 
-extern "C" int cvf_ef_general_fwd(const cvf_mlp_desc* mlp, const float* theta, const float* feat_tiled, int64_t n_tiles,
-                                  float* y_tiled, float* g_tiled, float* saved, void* stream) {
-  const char* why = efg_why(mlp);
-  CVF_REQUIRE(why == nullptr, "cvf_ef_general_fwd: %s", why);
-  CVF_REQUIRE(theta && feat_tiled && y_tiled && saved && n_tiles > 0, "cvf_ef_general_fwd: bad argument");
-  hipStream_t s = (hipStream_t)stream;
+namespace {
+
+// the launches of cvf_ef_general_fwd; ns: the first ns layers are shared by the nets (0: none)
+int efg_fwd(const cvf_mlp_desc* mlp, int ns, const float* theta, const float* feat_tiled, int64_t n_tiles, float* y_tiled,
+            float* g_tiled, float* saved, hipStream_t s) {
   const bool gen = g_tiled != nullptr;
   const int NH = mlp->n_layers - 1, k = mlp->n_nets, D = mlp->dims[0];
-  const EfgLayout L = efg_layout(mlp, n_tiles, gen);
+  const EfgLayout L = efg_layout(mlp, n_tiles, gen, ns);
   const EfgView feat{(float*)feat_tiled, (int64_t)D * CVF_TILE, 0};
-  // hidden layers: h_l = sigma(W_l h_{l-1} + b_l)
+  auto H = [&](int l) { return img(saved, L.h[l], n_tiles, mlp->dims[l + 1], l < ns); };
+  // hidden layers: h_l = sigma(W_l h_{l-1} + b_l); a shared layer once, for all nets
   for (int l = 0; l < NH; ++l) {
     EfgLayerArgs a = layer_args(l, 0, mlp->dims[l + 1], mlp->dims[l], 1, EPI_ACT);
     a.act_e = mlp->act[l];
-    a.x = l == 0 ? feat : img(saved, L.h[l - 1], n_tiles, mlp->dims[l]);
-    a.out = img(saved, L.h[l], n_tiles, mlp->dims[l + 1]);
-    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+    a.x = l == 0 ? feat : H(l - 1);
+    a.out = H(l);
+    if (launch_layer(mlp, theta, a, n_tiles, s, l < ns ? 1 : k)) return -1;
   }
   {  // y = W_NH h_{NH-1} + b_NH  -> y_tiled [tile][net][64]
     EfgLayerArgs a = layer_args(NH, 0, 1, mlp->dims[NH], 1, EPI_STORE);
-    a.x = img(saved, L.h[NH - 1], n_tiles, mlp->dims[NH]);
+    a.x = H(NH - 1);
     a.out = EfgView{y_tiled, (int64_t)k * CVF_TILE, CVF_TILE};
-    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+    if (launch_layer(mlp, theta, a, n_tiles, s, k)) return -1;
   }
   if (!gen) return 0;
   // g = dy/dr: u_{l-1} = W_l^T (sigma'(h_l) .* u_l), u_{NH-1} = W_NH^T (a broadcast); u_{-1} = g -> g_tiled [tile][net][d0][64]
@@ -311,32 +387,25 @@ extern "C" int cvf_ef_general_fwd(const cvf_mlp_desc* mlp, const float* theta, c
     a.act_x = mlp->act[l];
     a.x_bcast = l == NH - 1;
     if (l < NH - 1) a.x = img(saved, L.u[l], n_tiles, mlp->dims[l + 1]);
-    a.xh = img(saved, L.h[l], n_tiles, mlp->dims[l + 1]);
+    a.xh = H(l);
     a.out = l > 0 ? img(saved, L.u[l - 1], n_tiles, mlp->dims[l]) : EfgView{g_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
-    if (launch_layer(mlp, theta, a, n_tiles, s)) return -1;
+    if (launch_layer(mlp, theta, a, n_tiles, s, k)) return -1;
   }
   return 0;
 }
 
-extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float* theta, int64_t B,
-                                       const float* w, const float* w_lag, const float* feat_tiled, const float* y_tiled,
-                                       const float* q_tiled, const double* coef, float* slab, int32_t* step_count,
-                                       float* saved, void* stream) {
-  const char* why = efg_why(mlp);
-  CVF_REQUIRE(why == nullptr, "cvf_ef_general_backward: %s", why);
-  CVF_REQUIRE(cfg && theta && w && feat_tiled && y_tiled && coef && slab && saved && B > 0, "cvf_ef_general_backward: bad argument");
-  CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_backward: cfg.k != number of nets");
+// the launches of cvf_ef_general_backward; ns as efg_fwd (ns > 0: generator mode)
+int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const float* theta, int64_t B, const float* w,
+                 const float* w_lag, const float* feat_tiled, const float* y_tiled, const float* q_tiled, const double* coef,
+                 float* slab, int32_t* step_count, float* saved, hipStream_t s) {
   const bool gen = cfg->lag_idx == 0;
-  CVF_REQUIRE(!gen || q_tiled, "cvf_ef_general_backward: generator mode needs q");
-  CVF_REQUIRE(gen || w_lag, "cvf_ef_general_backward: transfer mode needs w_lag");
-  hipStream_t s = (hipStream_t)stream;
   const int NH = mlp->n_layers - 1, k = mlp->n_nets, D = mlp->dims[0];
   const int64_t T = cvf_ntiles(B), nt = gen ? T : 2 * T;
-  const EfgLayout L = efg_layout(mlp, nt, gen);
+  const EfgLayout L = efg_layout(mlp, nt, gen, ns);
   const int R = (int)g64_rows(mlp, nt);
   const EfgView feat{(float*)feat_tiled, (int64_t)D * CVF_TILE, 0};
   const EfgView qv{(float*)q_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
-  auto H = [&](int l) { return img(saved, L.h[l], nt, mlp->dims[l + 1]); };
+  auto H = [&](int l) { return img(saved, L.h[l], nt, mlp->dims[l + 1], l < ns); };
   auto U = [&](int l) { return img(saved, L.u[l], nt, mlp->dims[l + 1]); };
   auto Z = [&](int l) { return gen ? img(saved, L.z[l], nt, mlp->dims[l + 1]) : img(saved, L.zb[l & 1], nt, mlp->dims[l + 1]); };
   const EfgView alpha = img(saved, L.alpha, nt, 1), gamma = img(saved, L.gamma, nt, 1);
@@ -353,7 +422,7 @@ extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc
         a.act_x = mlp->act[l - 1];
       }
       a.out = Z(l);
-      if (launch_layer(mlp, theta, a, nt, s)) return -1;
+      if (launch_layer(mlp, theta, a, nt, s, k)) return -1;
     }
   {
     EfgCoefArgs c = {k, cfg->lag_idx, B, T, nt, alpha, gamma};
@@ -384,8 +453,9 @@ extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc
         g.act_b2 = mlp->act[l - 1];
       }
     }
+    g.nets = l < ns ? k : 1;   // a shared layer: one block sums the nets' products
     const int nb = ((g.Mo + 63) / 64) * ((g.Ki + 1 + 63) / 64);
-    hipLaunchKernelGGL(efg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb, k), dim3(256), 0, s, *mlp, g, slab);
+    hipLaunchKernelGGL(efg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb, l < ns ? 1 : k), dim3(256), 0, s, *mlp, g, slab);
     return cvf_check_launch("efg_wgrad_kernel");
   };
   if (wgrad(NH)) return -1;
@@ -407,7 +477,77 @@ extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc
       a.eu = U(l - 1);
       a.gam = gamma;
     }
-    if (launch_layer(mlp, theta, a, nt, s)) return -1;
+    if (launch_layer(mlp, theta, a, nt, s, k)) return -1;
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int cvf_ef_general_fwd(const cvf_mlp_desc* mlp, const float* theta, const float* feat_tiled, int64_t n_tiles,
+                                  float* y_tiled, float* g_tiled, float* saved, void* stream) {
+  const char* why = efg_why(mlp);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_fwd: %s", why);
+  CVF_REQUIRE(theta && feat_tiled && y_tiled && saved && n_tiles > 0, "cvf_ef_general_fwd: bad argument");
+  return efg_fwd(mlp, 0, theta, feat_tiled, n_tiles, y_tiled, g_tiled, saved, (hipStream_t)stream);
+}
+
+extern "C" int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, const float* theta, int64_t B,
+                                       const float* w, const float* w_lag, const float* feat_tiled, const float* y_tiled,
+                                       const float* q_tiled, const double* coef, float* slab, int32_t* step_count,
+                                       float* saved, void* stream) {
+  const char* why = efg_why(mlp);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_backward: %s", why);
+  CVF_REQUIRE(cfg && theta && w && feat_tiled && y_tiled && coef && slab && saved && B > 0, "cvf_ef_general_backward: bad argument");
+  CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_backward: cfg.k != number of nets");
+  const bool gen = cfg->lag_idx == 0;
+  CVF_REQUIRE(!gen || q_tiled, "cvf_ef_general_backward: generator mode needs q");
+  CVF_REQUIRE(gen || w_lag, "cvf_ef_general_backward: transfer mode needs w_lag");
+  return efg_backward(cfg, mlp, 0, theta, B, w, w_lag, feat_tiled, y_tiled, q_tiled, coef, slab, step_count, saved,
+                      (hipStream_t)stream);
+}
+
+// ---- nets that share their first n_shared layers (generator mode)
+extern "C" int cvf_ef_general_shared_supported(const cvf_mlp_desc* mlp, int n_shared) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  if (why != nullptr) {
+    cvf_set_error("cvf_ef_general_shared: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_ef_general_shared_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared) {
+  if (efg_why_shared(mlp, n_shared) != nullptr) return 0;
+  return g64_rows(mlp, n_tiles);
+}
+
+extern "C" int64_t cvf_ef_general_shared_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared) {
+  if (efg_why_shared(mlp, n_shared) != nullptr || n_tiles < 1) return 0;
+  return efg_layout(mlp, n_tiles, true, n_shared).total;
+}
+
+extern "C" int cvf_ef_general_shared_fwd(const cvf_mlp_desc* mlp, int n_shared, const float* theta, const float* feat_tiled,
+                                         int64_t n_tiles, float* y_tiled, float* g_tiled, float* saved, void* stream) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_shared_fwd: %s", why);
+  CVF_REQUIRE(g_tiled, "cvf_ef_general_shared_fwd: the transfer-mode shared step (no g_tiled) is not built");
+  CVF_REQUIRE(theta && feat_tiled && y_tiled && saved && n_tiles > 0, "cvf_ef_general_shared_fwd: bad argument");
+  return efg_fwd(mlp, n_shared, theta, feat_tiled, n_tiles, y_tiled, g_tiled, saved, (hipStream_t)stream);
+}
+
+extern "C" int cvf_ef_general_shared_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int n_shared, const float* theta,
+                                              int64_t B, const float* w, const float* feat_tiled, const float* y_tiled,
+                                              const float* q_tiled, const double* coef, float* slab, int32_t* step_count,
+                                              float* saved, void* stream) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_shared_backward: %s", why);
+  CVF_REQUIRE(cfg, "cvf_ef_general_shared_backward: bad argument");
+  CVF_REQUIRE(cfg->lag_idx == 0, "cvf_ef_general_shared_backward: the transfer-mode shared step (cfg.lag_idx = %d) is not built",
+              cfg->lag_idx);
+  CVF_REQUIRE(theta && w && feat_tiled && y_tiled && q_tiled && coef && slab && saved && B > 0,
+              "cvf_ef_general_shared_backward: bad argument");
+  CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_shared_backward: cfg.k != number of nets");
+  return efg_backward(cfg, mlp, n_shared, theta, B, w, nullptr, feat_tiled, y_tiled, q_tiled, coef, slab, step_count, saved,
+                      (hipStream_t)stream);
 }

@@ -411,6 +411,35 @@ int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, cons
                             const float* w_lag, const float* feat_tiled, const float* y_tiled, const float* q_tiled,
                             const double* coef, float* slab, int32_t* step_count, float* saved, void* stream);
 
+/* --- The same for k nets that SHARE their first n_shared Linear layers (csrc/ef_general.hip), generator
+ * mode only: the chains reg_i o encoder of RegAutoEncoderTask's regulariser (core.py:990,1008-1022: every reg_i reads the one
+ * encoder) and the k components of the encoder in its gradient-norm penalty (core.py:896-910).  The sharing is stated by the
+ * description: for l < n_shared, w_off[i][l] and b_off[i][l] are the same for every net i, and n_params counts those blocks
+ * once; every other block is disjoint from all the rest, and the blocks fill the flat buffer.  0 <= n_shared <= n_layers - 1
+ * (the hidden layers); shapes and limits as cvf_ef_general_supported.  The shared layers run forward once (one image of h_l for
+ * all nets), their weights are read in place, and their gradient - the sum over the nets - is formed inside one launch, the
+ * nets walked in the order 0..k-1: no atomics, the same inputs give the same bits.  n_shared = 0 is the launch list of the
+ * calls above (and then takes any description those take whose blocks do not overlap).
+ *  cvf_ef_general_shared_supported   : 1, or 0 with the reason in cvf_last_error().
+ *  cvf_ef_general_shared_slab_rows   : as cvf_ef_general_slab_rows (which refuses a description with shared blocks).
+ *  cvf_ef_general_shared_saved_floats: floats of `saved` for n_tiles = T tiles: the h_l of the shared layers once, everything
+ *                                      else per net.
+ *  cvf_ef_general_shared_fwd         : replaces self.model(...) at core.py:996 and the autograd.grad of core.py:1009 (and
+ *                                      core.py:899,903 of the penalty): y_tiled [n_tiles][k][64], g_tiled [n_tiles][k][d0][64]
+ *                                      (required: without it the call would be the transfer-mode step, which is not built).
+ *  cvf_ef_general_shared_backward    : replaces loss.backward() at core.py:1102 for these terms: slab rows of the flat gradient
+ *                                      [rows][n_params], each shared entry written once (follow with cvf_slab_reduce).  A cfg
+ *                                      with lag_idx != 0 is refused by name.
+ * The four calls return a negative code (0 for the sizes), with the reason in cvf_last_error(), before any launch. */
+int cvf_ef_general_shared_supported(const cvf_mlp_desc* mlp, int n_shared);
+int64_t cvf_ef_general_shared_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared);
+int64_t cvf_ef_general_shared_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared);
+int cvf_ef_general_shared_fwd(const cvf_mlp_desc* mlp, int n_shared, const float* theta, const float* feat_tiled, int64_t n_tiles,
+                              float* y_tiled, float* g_tiled, float* saved, void* stream);
+int cvf_ef_general_shared_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int n_shared, const float* theta, int64_t B,
+                                   const float* w, const float* feat_tiled, const float* y_tiled, const float* q_tiled,
+                                   const double* coef, float* slab, int32_t* step_count, float* saved, void* stream);
+
 /* --- AutoEncoder: weighted reconstruction loss and its parameter gradient in one pass
  * (core.py:664-666,708).  feat_rows [n][d0] row-major (the precomputed feature
  * trajectory of core.py:635); idx NULL or [B] frame indices into it; w [B]; inv_wsum =
