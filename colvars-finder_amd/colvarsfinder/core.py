@@ -79,6 +79,43 @@ def _split(n, test_ratio):
     return perm[n_test:], perm[:n_test]
 
 
+def _agreed_split(n, test_ratio, draws, device):
+    """``(idx_train, idx_test)`` of the last of ``draws`` :func:`_split` calls (the eigenfunction task draws twice and keeps the
+    second, core.py:465,468; the autoencoder tasks draw once, core.py:672,1044), every rank brought to rank 0's permutation."""
+    for _ in range(draws):
+        idx_train, idx_test = _split(n, test_ratio)
+    if _dist.world() > 1:
+        both = torch.as_tensor(np.concatenate([idx_train, idx_test]), device=device)
+        _dist.broadcast_(both)
+        both = both.cpu().numpy()
+        idx_train, idx_test = both[:len(idx_train)], both[len(idx_train):]
+    return idx_train, idx_test
+
+
+def _static_batches(n, bs, rank=None, world=None):
+    """The static batches of a permuted set of ``n`` frames - DataLoader(batch_size=bs, drop_last=True, shuffle=False),
+    core.py:470-481 - as this process sees them: ``(pos, nb, ranges)``.  ``pos``: the positions (into the permuted set) it keeps
+    resident - one process: the whole set, the tail that drop_last discards included; a data-parallel job: this rank's slice of
+    every global batch, batch-major (_dist.shard_batches).  ``nb``: frames per local batch; ``ranges``: the batches as row ranges
+    ``(a, b)`` of the resident rows.  No batch when ``bs == 0`` or ``n < bs``."""
+    rank, world = _dist.rank() if rank is None else rank, _dist.world() if world is None else world
+    # (each set by itself: a rank without steps would leave the others waiting)
+    assert bs == 0 or bs >= world, f"batch size {bs} is smaller than the number of ranks {world}"
+    pos, nb = _dist.shard_batches(n, bs, rank, world)
+    ranges = [(j * nb, (j + 1) * nb) for j in range(len(pos) // nb)] if nb > 0 else []
+    return (np.arange(n, dtype=np.int64) if world == 1 else pos), nb, ranges
+
+
+def _batch_weight_sums(w, ranges):
+    """Global weight sum of every batch ``w[a:b]`` as host floats: batches are static (shuffle=False), so their weight sums are
+    known before the first step."""
+    if not ranges:
+        return []
+    sums = torch.stack([w[a:b].sum(dtype=torch.float64) for a, b in ranges])
+    _dist.allreduce_sum_(sums)
+    return [float(v) for v in sums.cpu()]
+
+
 class _AsyncEpochLog:
     """The per-epoch loss rows leave the device through a small ring of pinned buffers, asynchronously: the host side of an
     epoch (``loss_list``, ``_cvec``, the writer's scalars - ``on_epoch(epoch, train_rows, test_rows)``) runs up to
@@ -731,8 +768,8 @@ class TrainingTask(ABC):
         raise TypeError("pp_layer must be torch.nn.Identity or a colvarsfinder.pp.AlignFeatureLayer "
                         f"(PreprocessingANN); the GPU kernels cannot run an arbitrary module ({type(pp).__name__})")
 
-    def init_model_and_optimizer(self):
-        """core.py:145-166: optional restart from ``load_model_filename``; Adam (case-insensitive) else SGD."""
+    def _load_model(self):
+        """core.py:156-161: optional restart from ``load_model_filename``."""
         if self.load_model_filename:
             if os.path.isfile(self.load_model_filename):
                 self.model.load_state_dict(torch.load(self.load_model_filename, map_location="cpu"), strict=False)
@@ -740,8 +777,96 @@ class TrainingTask(ABC):
                     print(f'model parameters loaded from: {self.load_model_filename}')
             elif self.verbose:
                 print(f'model file not found: {self.load_model_filename}')
-        self._flat = _FlatParams(self.model, self.device)
+
+    def _flat_params(self):
+        """The flat HBM buffer the model's parameters alias (RegAutoEncoderTask lays out its own chain)."""
+        return _FlatParams(self.model, self.device)
+
+    def init_model_and_optimizer(self):
+        """core.py:145-166: optional restart from ``load_model_filename``; Adam (case-insensitive) else SGD."""
+        self._load_model()
+        self._flat = self._flat_params()
         self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
+
+    def _dev(self, t, dtype=torch.float32):
+        return None if t is None else torch.as_tensor(t).detach().to(device=self.device, dtype=dtype).contiguous()
+
+    def backward(self):
+        """Fill ``p.grad`` of the module's parameters from the flat gradient of the last step that left one."""
+        for p, gv in self._flat.grad_views():
+            p.grad = gv.clone()
+
+    # -- r(x) of the two autoencoder tasks: computed once per frame, the steps read the rows
+    def _probe_pp(self, frame):
+        """What stands in for the kernels' description of r(x) behind a foreign module: its width ``d_r``, found on one frame."""
+        with torch.no_grad():
+            y = self.preprocessing_layer(torch.as_tensor(frame).to(device=self.device, dtype=torch.float32))
+        return types.SimpleNamespace(d_r=int(y.reshape(1, -1).shape[1]))
+
+    def _features(self, X):
+        """Frames ``X`` (host or device) -> row-major feature rows resident in HBM: K1, or - a module this package has no kernel
+        for - torch, on the device, in bounded chunks."""
+        X = torch.as_tensor(X).detach()
+        if self._foreign_pp:
+            return module_features(self.preprocessing_layer, X, self._pp.d_r, self.device)
+        X = _hip.upload_f32(X, self.device)
+        n = X.shape[0]
+        out = torch.empty(n, self._pp.d_r, device=self.device, dtype=torch.float32)
+        if n > 0:
+            _hip.check(_hip.lib().cvf_align_feature_fwd(self._pp, _hip.ptr(X), n, None, _hip.ptr(out), None,
+                                                        _hip.ptr(_hip.align_scratch(self._pp, n, self.device)), _hip.stream()),
+                       "cvf_align_feature_fwd")
+        return out
+
+    # -- what the three train() loops share around their steps
+    def _announce(self, bs, n, n_batches):
+        """The reference's opening lines (core.py:483-489), rank 0 only; every argument a (train, test) pair."""
+        if _dist.rank() != 0:
+            return
+        print("\nTraining starts.\n%d epochs in total, batch sizes (train/test): %d/%d" % (self.num_epochs, bs[0], bs[1]))
+        print("\nTrain set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
+              (n[0], n_batches[0], n_batches[0] * self.num_epochs), flush=True)
+        print("Test set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
+              (n[1], n_batches[1], n_batches[1] * self.num_epochs), flush=True)
+
+    def _epoch_logs(self, n_tr, n_te, *row):
+        """Device rows the steps of an epoch write their losses to (fp64; one row where a set has no batch)."""
+        return tuple(torch.zeros(max(n_, 1), *row, device=self.device, dtype=torch.float64) for n_ in (n_tr, n_te))
+
+    def _write_epoch_means(self, names, ep, tr, te):
+        """core.py:559-561, 1208-1212: the epoch's mean of every loss column to the writer (NaN where the set has no batch)."""
+        mean_tr = tr.mean(0) if len(tr) else torch.full((len(names),), float("nan"))
+        mean_te = te.mean(0) if len(te) else torch.full((len(names),), float("nan"))
+        for i, name in enumerate(names):
+            self.writer.add_scalar('%s/train' % name, mean_tr[i], ep)
+            self.writer.add_scalar('%s/test' % name, mean_te[i], ep)
+
+    def _due(self, epoch):
+        """``(saving, plotting)``: whether this epoch ends a save period / a plot period (a frequency of 0: never)."""
+        saving = self.save_model_every_step > 0 and epoch % self.save_model_every_step == self.save_model_every_step - 1
+        plotting = self.plot_frequency > 0 and epoch % self.plot_frequency == self.plot_frequency - 1
+        return saving, plotting
+
+    def _save_latest_and_best(self, epoch, last_loss, min_loss):
+        """Save "latest", and "best" where the epoch's last train loss (inf: no train batch) is a strict new minimum
+        (core.py:526-528); returns the minimum so far."""
+        self.save_model(epoch)
+        if last_loss < min_loss:
+            min_loss = last_loss
+            self.save_model(epoch, 'best')
+        return min_loss
+
+    def _plot(self, epoch):
+        """core.py:530-532, 720-722, 1136-1140: the CV model (and the regulariser model where the task has one) to the user's
+        ``plot_class``, rank 0 only."""
+        if self.plot_class is not None and _dist.rank() == 0:
+            cv, reg = self.colvar_model(), self.reg_model()
+            self.plot_class.plot(*((cv,) if reg is None else (cv, reg)), epoch=epoch)
+
+    def _loss_frames(self, names):
+        """core.py:563-566: ``train_loss_df`` / ``test_loss_df``, one row of column means per epoch of ``loss_list``."""
+        self.train_loss_df, self.test_loss_df = (
+            pd.DataFrame(torch.cat([e[i].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(), columns=names) for i in (0, 1))
 
     def save_model(self, epoch, description="latest"):
         """core.py:168-227: ``model.pt`` + per-CV text files (+ TorchScript CV when the layer is scriptable)."""
@@ -1407,9 +1532,6 @@ class EigenFunctionTask(TrainingTask):
         self.optimizer.sync_lr()                       # the captured kernels read the learning rate from a device scalar
         g.replay()
 
-    def _dev(self, t, dtype=torch.float32):
-        return None if t is None else torch.as_tensor(t).detach().to(device=self.device, dtype=dtype).contiguous()
-
     def loss_func(self, X, weight, X_lagged, weight_lagged):
         """core.py:387-457.  Returns ``(loss, eig_vals, non_penalty_loss, penalty, cvec)``; the parameter
         gradient of ``loss`` is obtained with :meth:`backward` (there is no autograd graph)."""
@@ -1432,8 +1554,7 @@ class EigenFunctionTask(TrainingTask):
         """Parameter gradient of the last :meth:`loss_func` call -> ``p.grad`` of the model's parameters."""
         ws, w, w_lag = self._last
         self._backward(ws, w, w_lag)
-        for p, gv in self._flat.grad_views():
-            p.grad = gv.clone()
+        super().backward()
 
     # ---------------------------------------------------------------- training loop
     def train(self):
@@ -1441,36 +1562,25 @@ class EigenFunctionTask(TrainingTask):
         k, lag = self.k, self.lag_idx
         self._flat.repack()
         self.drop_alignment_cache()   # captured steps hold pointers into the previous call's batches, the rows belong to them
-        ll = self._n_frames - lag
-        _split(ll, self.test_ratio)                                  # core.py:465 (drawn, discarded)
-        idx_train, idx_test = _split(ll, self.test_ratio)            # core.py:468
-        world, rank = _dist.world(), _dist.rank()
-        if world > 1:  # every rank must use rank 0's permutation
-            both = torch.as_tensor(np.concatenate([idx_train, idx_test]), device=self.device)
-            _dist.broadcast_(both)
-            both = both.cpu().numpy()
-            idx_train, idx_test = both[:len(idx_train)], both[len(idx_train):]
+        # core.py:465 (drawn, discarded), core.py:468
+        idx_train, idx_test = _agreed_split(self._n_frames - lag, self.test_ratio, 2, self.device)
 
         def resident(idx, bs):
             """Frames (weights, lagged partners) of the permuted set `idx` that this process works on, gathered once in
             batch order, and its batches as row ranges of that copy: DataLoader(batch_size=bs, drop_last=True,
-            shuffle=False), core.py:470-481.  One process: the whole set, gathered on the device from the resident
-            trajectory.  Data-parallel: only this rank's slice of every global batch (_dist.shard_batches), gathered on
-            the host and uploaded - the lagged partners are pre-gathered too, so a frame may live on two ranks."""
+            shuffle=False), core.py:470-481.  One process: the whole set (the tail drop_last discards included), gathered on
+            the device from the resident trajectory.  Data-parallel: only this rank's slice of every global batch
+            (_static_batches), gathered on the host and uploaded - the lagged partners are pre-gathered too, so a frame
+            may live on two ranks."""
+            pos, _, bl = _static_batches(len(idx), bs)
+            rows = np.asarray(idx)[pos]
+            it = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+            w, wl = self._weights[it].contiguous(), self._weights[it + lag].contiguous() if lag > 0 else None
             if not self._sharded:
-                it = torch.as_tensor(idx, device=self.device, dtype=torch.long)
-                X, w = self._traj[it].contiguous(), self._weights[it].contiguous()
-                Xl, wl = (self._traj[it + lag].contiguous(), self._weights[it + lag].contiguous()) if lag > 0 else (None, None)
-                bl = [(s, s + bs) for s in range(0, len(idx) - bs + 1, bs)] if bs > 0 else []
+                X, Xl = self._traj[it].contiguous(), self._traj[it + lag].contiguous() if lag > 0 else None
             else:
-                assert bs == 0 or bs >= world, f"batch size {bs} is smaller than the number of ranks {world}"
-                pos, nb = _dist.shard_batches(len(idx), bs, rank, world)
-                rows = np.asarray(idx)[pos]
-                it = torch.as_tensor(rows, device=self.device, dtype=torch.long)
-                X, w = _hip.upload_f32(self._traj_host.rows(rows), self.device), self._weights[it].contiguous()
-                Xl, wl = ((_hip.upload_f32(self._traj_host.rows(rows + lag), self.device), self._weights[it + lag].contiguous())
-                          if lag > 0 else (None, None))
-                bl = [(j * nb, (j + 1) * nb) for j in range(len(pos) // nb)] if nb > 0 else []
+                X = _hip.upload_f32(self._traj_host.rows(rows), self.device)
+                Xl = _hip.upload_f32(self._traj_host.rows(rows + lag), self.device) if lag > 0 else None
             self.resident_bytes += sum(t.numel() * t.element_size() for t in (X, w, Xl, wl) if t is not None)
             return (X, w, Xl, wl), bl
 
@@ -1482,16 +1592,9 @@ class EigenFunctionTask(TrainingTask):
 
         self.loss_list = []
         min_loss = float("inf")
-        if rank == 0:
-            print("\nTraining starts.\n%d epochs in total, batch sizes (train/test): %d/%d" % (self.num_epochs, bs_train, bs_test))
-            print("\nTrain set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_train), len(tr_batches), len(tr_batches) * self.num_epochs), flush=True)
-            print("Test set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_test), len(te_batches), len(te_batches) * self.num_epochs), flush=True)
+        self._announce((bs_train, bs_test), (len(idx_train), len(idx_test)), (len(tr_batches), len(te_batches)))
         loss_names = ['loss', 'eigen_non_penalty', 'eigen_penalty'] + ['eig_%d' % (i + 1) for i in range(k)]
-        nrow = 3 + 2 * k
-        log_tr = torch.zeros(max(len(tr_batches), 1), nrow, device=self.device, dtype=torch.float64)
-        log_te = torch.zeros(max(len(te_batches), 1), nrow, device=self.device, dtype=torch.float64)
+        log_tr, log_te = self._epoch_logs(len(tr_batches), len(te_batches), 3 + 2 * k)
 
         def sl(data, a, b):
             return tuple(None if t is None else t[a:b] for t in data)
@@ -1502,11 +1605,7 @@ class EigenFunctionTask(TrainingTask):
             if len(tr_batches) > 0:
                 self._cvec = tr[-1, 3 + k:].round().to(torch.long).numpy()
             self.loss_list.append([tr[:, :3 + k].to(dt), te[:, :3 + k].to(dt)])
-            mean_tr = self.loss_list[-1][0].mean(0) if len(tr_batches) else torch.full((3 + k,), float("nan"))
-            mean_te = self.loss_list[-1][1].mean(0) if len(te_batches) else torch.full((3 + k,), float("nan"))
-            for i, name in enumerate(loss_names):
-                self.writer.add_scalar('%s/train' % name, mean_tr[i], ep)
-                self.writer.add_scalar('%s/test' % name, mean_te[i], ep)
+            self._write_epoch_means(loss_names, ep, *self.loss_list[-1])
 
         elog = _AsyncEpochLog(log_tr, log_te, len(tr_batches), len(te_batches), on_epoch)
 
@@ -1528,30 +1627,21 @@ class EigenFunctionTask(TrainingTask):
         steps = [(train_one, it) for it in range(len(tr_batches))] + [(test_one, it) for it in range(len(te_batches))]
         chunks = [steps[c:c + kEpochChunk] for c in range(0, len(steps), kEpochChunk)]
 
-        for epoch in _tqdm(range(self.num_epochs), disable=(rank != 0)):
+        for epoch in _tqdm(range(self.num_epochs), disable=(_dist.rank() != 0)):
             self.model.train()
             for ci, chunk in enumerate(chunks):
                 self._graph_call(("epoch", ci), lambda chunk=chunk: [fn(it) for fn, it in chunk])
             elog.push(epoch)        # (the host reads the epoch's numbers later; epochs that save or plot flush first)
-            saving = self.save_model_every_step > 0 and epoch % self.save_model_every_step == self.save_model_every_step - 1
-            plotting = self.plot_frequency > 0 and epoch % self.plot_frequency == self.plot_frequency - 1
+            saving, plotting = self._due(epoch)
             if saving or plotting:
                 elog.flush_all()
             if saving:
-                self.save_model(epoch)
                 last = float(self.loss_list[-1][0][-1, 0]) if len(tr_batches) > 0 else float("inf")
-                if last < min_loss:                                             # core.py:526-528
-                    min_loss = last
-                    self.save_model(epoch, 'best')
+                min_loss = self._save_latest_and_best(epoch, last, min_loss)
             if plotting:
-                if self.plot_class is not None and rank == 0:
-                    self.plot_class.plot(self.colvar_model(), epoch=epoch)
+                self._plot(epoch)
         elog.flush_all()
-
-        self.train_loss_df = pd.DataFrame(torch.cat([e[0].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                          columns=loss_names)
-        self.test_loss_df = pd.DataFrame(torch.cat([e[1].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                         columns=loss_names)
+        self._loss_frames(loss_names)
 
 
 class AutoEncoderTask(TrainingTask):
@@ -1578,13 +1668,8 @@ class AutoEncoderTask(TrainingTask):
         # task applies it exactly once, to build the feature trajectory - a foreign module is run there with torch, on the
         # device, and the training step (cvf_ae_step on the resident feature rows) is the same either way
         self._foreign_pp = not isinstance(self.preprocessing_layer, (torch.nn.Identity, AlignFeatureLayer))
-        if self._foreign_pp:
-            with torch.no_grad():
-                probe = self.preprocessing_layer(torch.as_tensor(self._traj_host.rows(np.arange(1))).to(device=self.device, dtype=torch.float32))
-            pp = types.SimpleNamespace(d_r=int(probe.reshape(1, -1).shape[1]))
-            self._pp = pp
-        else:
-            self._pp = pp = self._pp_desc(int(np.prod(self._traj_host.shape[1:])))
+        self._pp = pp = (self._probe_pp(self._traj_host.rows(np.arange(1))) if self._foreign_pp else
+                         self._pp_desc(int(np.prod(self._traj_host.shape[1:]))))
         # core.py:635: the feature trajectory r(x) of ALL frames, once.  In a data-parallel job (one process per GPU) each
         # rank computes the features of its own rows only, in train(), once the split is known.
         self._sharded = _dist.world() > 1
@@ -1610,23 +1695,6 @@ class AutoEncoderTask(TrainingTask):
             raise NotImplementedError("AutoEncoderTask: no HIP route trains this chain (%s; %s)"
                                       % (fused, lib.cvf_last_error().decode()))
         return True
-
-    def _features(self, rows):
-        """K1 over host frames -> row-major feature rows resident in HBM."""
-        X = _hip.upload_f32(rows, self.device)
-        n = X.shape[0]
-        if self._foreign_pp:     # a module this package has no kernel for: torch, on the device, in bounded chunks, once
-            out = torch.empty(n, self._pp.d_r, device=self.device, dtype=torch.float32)
-            with torch.no_grad():
-                for s0 in range(0, n, 65536):
-                    out[s0:s0 + 65536] = self.preprocessing_layer(X[s0:s0 + 65536]).reshape(-1, self._pp.d_r)
-            return out
-        out = torch.empty(n, self._pp.d_r, device=self.device, dtype=torch.float32)
-        if n > 0:
-            _hip.check(_hip.lib().cvf_align_feature_fwd(self._pp, _hip.ptr(X), n, None, _hip.ptr(out), None,
-                                                        _hip.ptr(_hip.align_scratch(self._pp, n, self.device)), _hip.stream()),
-                       "cvf_align_feature_fwd")
-        return out
 
     def colvar_model(self):
         """core.py:640-647."""
@@ -1676,39 +1744,23 @@ class AutoEncoderTask(TrainingTask):
         loss = self._step(X, None, weight, with_grad=True)
         return loss.to(torch.get_default_dtype(), copy=True)
 
-    def backward(self):
-        pos = 0
-        for p in self.model.parameters():
-            p.grad = self._flat.grad[pos:pos + p.numel()].view(p.shape).clone()
-            pos += p.numel()
-
     def train(self):
         """core.py:668-744."""
-        n = self._n_frames
-        idx_train, idx_test = _split(n, self.test_ratio)             # core.py:672 (one draw)
-        world, rank = _dist.world(), _dist.rank()
-        if world > 1:
-            both = torch.as_tensor(np.concatenate([idx_train, idx_test]), device=self.device)
-            _dist.broadcast_(both)
-            both = both.cpu().numpy()
-            idx_train, idx_test = both[:len(idx_train)], both[len(idx_train):]
+        idx_train, idx_test = _agreed_split(self._n_frames, self.test_ratio, 1, self.device)   # core.py:672 (one draw)
         bs_train, bs_test = min(self.batch_size, len(idx_train)), min(self.batch_size, len(idx_test))
 
         def resident(idx, bs):
             """(feature rows, per-batch row indices or None, weights, batches) of the permuted set `idx` for this process.
             One process: batches index the resident feature trajectory.  Data-parallel: only this rank's slice of every
-            global batch is uploaded and run through K1 (_dist.shard_batches); its batches are contiguous row ranges."""
-            if not self._sharded:
-                it = torch.as_tensor(idx, device=self.device, dtype=torch.long)
-                bl = [(s, s + bs) for s in range(0, len(idx) - bs + 1, bs)] if bs > 0 else []
-                return self._feature_traj, it, self._weights[it].contiguous(), bl
-            assert bs == 0 or bs >= world, f"batch size {bs} is smaller than the number of ranks {world}"
-            pos, nb = _dist.shard_batches(len(idx), bs, rank, world)
+            global batch is uploaded and run through K1 (_static_batches); its batches are contiguous row ranges."""
+            pos, _, bl = _static_batches(len(idx), bs)
             rows = np.asarray(idx)[pos]
+            it = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+            if not self._sharded:
+                return self._feature_traj, it, self._weights[it].contiguous(), bl
             feat = self._features(self._traj_host.rows(rows))
             self.resident_bytes += feat.numel() * 4
-            wv = self._weights[torch.as_tensor(rows, device=self.device, dtype=torch.long)].contiguous()
-            return feat, None, wv, ([(j * nb, (j + 1) * nb) for j in range(len(pos) // nb)] if nb > 0 else [])
+            return feat, None, self._weights[it].contiguous(), bl
 
         if self._sharded:
             self.resident_bytes = 0
@@ -1720,25 +1772,12 @@ class AutoEncoderTask(TrainingTask):
         def rows_of(feat, it, a, b):
             return (feat, it[a:b]) if it is not None else (feat[a:b], None)
 
-        def inv_wsums(wv, bl):
-            # batches are static (shuffle=False): their weight sums are known before the first step
-            if not bl:
-                return []
-            sums = torch.stack([wv[a:b].sum(dtype=torch.float64) for a, b in bl])
-            _dist.allreduce_sum_(sums)
-            return [1.0 / float(v) for v in sums.cpu()]
-
-        iw_tr, iw_te = inv_wsums(wtr, tr_batches), inv_wsums(wte, te_batches)
+        iw_tr = [1.0 / v for v in _batch_weight_sums(wtr, tr_batches)]
+        iw_te = [1.0 / v for v in _batch_weight_sums(wte, te_batches)]
         self.loss_list = []
         min_loss = float("inf")
-        if rank == 0:
-            print("\nTraining starts.\n%d epochs in total, batch sizes (train/test): %d/%d" % (self.num_epochs, bs_train, bs_test))
-            print("\nTrain set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_train), len(tr_batches), len(tr_batches) * self.num_epochs), flush=True)
-            print("Test set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_test), len(te_batches), len(te_batches) * self.num_epochs), flush=True)
-        log_tr = torch.zeros(max(len(tr_batches), 1), device=self.device, dtype=torch.float64)
-        log_te = torch.zeros(max(len(te_batches), 1), device=self.device, dtype=torch.float64)
+        self._announce((bs_train, bs_test), (len(idx_train), len(idx_test)), (len(tr_batches), len(te_batches)))
+        log_tr, log_te = self._epoch_logs(len(tr_batches), len(te_batches))
 
         def on_epoch(ep, tr, te):
             dt = torch.get_default_dtype()
@@ -1748,33 +1787,25 @@ class AutoEncoderTask(TrainingTask):
             self.writer.add_scalar('Loss/test', te.mean() if len(te) else float("nan"), ep)
 
         elog = _AsyncEpochLog(log_tr, log_te, len(tr_batches), len(te_batches), on_epoch)
-        for epoch in _tqdm(range(self.num_epochs), disable=(rank != 0)):
+        fuse_adam = _dist.world() == 1
+        for epoch in _tqdm(range(self.num_epochs), disable=(_dist.rank() != 0)):
             self.model.train()
             for it, (a, b) in enumerate(tr_batches):
-                log_tr[it] = self._step(*rows_of(ftr, itr, a, b), wtr[a:b], True, iw_tr[it], advance=True,
-                                        fuse_adam=(world == 1))
+                log_tr[it] = self._step(*rows_of(ftr, itr, a, b), wtr[a:b], True, iw_tr[it], advance=True, fuse_adam=fuse_adam)
             self.model.eval()
             for it, (a, b) in enumerate(te_batches):
                 log_te[it] = self._step(*rows_of(fte, ite, a, b), wte[a:b], False, iw_te[it])
             elog.push(epoch)
-            saving = self.save_model_every_step > 0 and epoch % self.save_model_every_step == self.save_model_every_step - 1
-            plotting = self.plot_frequency > 0 and epoch % self.plot_frequency == self.plot_frequency - 1
+            saving, plotting = self._due(epoch)
             if saving or plotting:
                 elog.flush_all()
             if saving:
-                self.save_model(epoch)
                 last = float(self.loss_list[-1][0][-1]) if len(tr_batches) else float("inf")
-                if last < min_loss:
-                    min_loss = last
-                    self.save_model(epoch, 'best')
+                min_loss = self._save_latest_and_best(epoch, last, min_loss)
             if plotting:
-                if self.plot_class is not None and rank == 0:
-                    self.plot_class.plot(self.colvar_model(), epoch=epoch)
+                self._plot(epoch)
         elog.flush_all()
-        self.train_loss_df = pd.DataFrame(torch.cat([e[0].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                          columns=['loss'])
-        self.test_loss_df = pd.DataFrame(torch.cat([e[1].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                         columns=['loss'])
+        self._loss_frames(['loss'])
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -2238,12 +2269,10 @@ class RegAutoEncoderTask(TrainingTask):
             if self.eta[0] > self._eps:
                 raise NotImplementedError("RegAutoEncoderTask on MI355X: the gradient-norm penalty eta[0] needs features = coordinates "
                                           "(Identity or AlignFeatureLayer), not a foreign preprocessing module")
-            with torch.no_grad():
-                y = self.preprocessing_layer(torch.as_tensor(traj[:1]).to(device=self.device, dtype=torch.float32))
-            self._pp = types.SimpleNamespace(d_r=int(y.reshape(1, -1).shape[1]))
+            self._pp = self._probe_pp(traj[:1])
         else:
             self._pp = self._pp_desc(self.tot_dim)
-        self._feature_traj = self._features(torch.as_tensor(traj))
+        self._feature_traj = self._features(traj)
         d = self._flat.desc
         assert self._pp.d_r == d.dims[0] and d.dims[d.n_layers] == d.dims[0] + self.num_reg, \
             'encoder input / decoder output width must equal the feature dimension'
@@ -2269,16 +2298,8 @@ class RegAutoEncoderTask(TrainingTask):
         self._traj = None if self._gen is None else self._gen.inner._frames(traj)
 
     # -- the base class builds the flat buffer from mlp_layout(); this model needs the side-by-side chain
-    def init_model_and_optimizer(self):
-        if self.load_model_filename:
-            if os.path.isfile(self.load_model_filename):
-                self.model.load_state_dict(torch.load(self.load_model_filename, map_location="cpu"), strict=False)
-                if self.verbose:
-                    print(f'model parameters loaded from: {self.load_model_filename}')
-            elif self.verbose:
-                print(f'model file not found: {self.load_model_filename}')
-        self._flat = _RegFlatParams(self.model, self.device, self.freeze_encoder)
-        self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
+    def _flat_params(self):
+        return _RegFlatParams(self.model, self.device, self.freeze_encoder)
 
     def _needs_general(self):
         """False where the fused chain kernel takes the merged chain (cvf_regae_route: a 64-frame tile's chain in LDS), True where
@@ -2292,17 +2313,6 @@ class RegAutoEncoderTask(TrainingTask):
             raise NotImplementedError("RegAutoEncoderTask: no HIP route trains this chain (%s; %s)"
                                       % (fused, lib.cvf_last_error().decode()))
         return True
-
-    def _features(self, X):
-        if self._foreign_pp:
-            return module_features(self.preprocessing_layer, torch.as_tensor(X).detach(), self._pp.d_r, self.device)
-        X = _hip.upload_f32(torch.as_tensor(X).detach(), self.device)
-        n = X.shape[0]
-        out = torch.empty(n, self._pp.d_r, device=self.device, dtype=torch.float32)
-        _hip.check(_hip.lib().cvf_align_feature_fwd(self._pp, _hip.ptr(X), n, None, _hip.ptr(out), None,
-                                                    _hip.ptr(_hip.align_scratch(self._pp, n, self.device)), _hip.stream()),
-                   "cvf_align_feature_fwd")
-        return out
 
     def colvar_model(self):
         """core.py:855-863."""
@@ -2328,14 +2338,14 @@ class RegAutoEncoderTask(TrainingTask):
                 sscratch=torch.zeros(lib.cvf_ef_stats_scratch_doubles(K, 1), device=dev, dtype=torch.float64),
                 loss_vec=torch.zeros(3 + 2 * K, device=dev, dtype=torch.float64),
                 coef=torch.zeros(4 * K + K * K, device=dev, dtype=torch.float64), T=T)
-            if True:   # (small) latent-vector buffers: the public reg_enc_* functions need them whatever eta is
-                k = self.k
-                ws.update(enc=torch.zeros(T * k * 64, device=dev, dtype=torch.float32),
-                          ezero=torch.zeros(T * k * 64, device=dev, dtype=torch.float32),
-                          estats=torch.zeros(lib.cvf_ef_nstats(k, 0), device=dev, dtype=torch.float64),
-                          esscratch=torch.zeros(lib.cvf_ef_stats_scratch_doubles(k, 0), device=dev, dtype=torch.float64),
-                          eterms=torch.zeros(2, device=dev, dtype=torch.float64),
-                          ecoef=torch.zeros(k + k * k, device=dev, dtype=torch.float64))
+            # (small) latent-vector buffers: the public reg_enc_* functions need them whatever eta is
+            k = self.k
+            ws.update(enc=torch.zeros(T * k * 64, device=dev, dtype=torch.float32),
+                      ezero=torch.zeros(T * k * 64, device=dev, dtype=torch.float32),
+                      estats=torch.zeros(lib.cvf_ef_nstats(k, 0), device=dev, dtype=torch.float64),
+                      esscratch=torch.zeros(lib.cvf_ef_stats_scratch_doubles(k, 0), device=dev, dtype=torch.float64),
+                      eterms=torch.zeros(2, device=dev, dtype=torch.float64),
+                      ecoef=torch.zeros(k + k * k, device=dev, dtype=torch.float64))
             self._ws[B] = ws
         return ws
 
@@ -2426,9 +2436,6 @@ class RegAutoEncoderTask(TrainingTask):
 
     # -- the reference's public loss functions, evaluated on raw coordinate batches (forward values; the training
     #    loop below uses the resident feature trajectory instead)
-    def _dev(self, t):
-        return torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).contiguous()
-
     def _terms(self, feat, w, w_lag, lag_ae, lag_reg, alpha, use_reg, use_enc):
         """Forward values with only the named parts of the loss switched on."""
         keep = (self.alpha, self._use_reg, self._use_enc, self.eta)
@@ -2464,11 +2471,6 @@ class RegAutoEncoderTask(TrainingTask):
         cvec = self._cvec_dev.cpu().to(torch.long).numpy()
         return out[4:4 + self.num_reg].to(dt).cpu(), out[2].to(dt), out[3].to(dt), cvec
 
-    def backward(self):
-        """Fill ``p.grad`` of the module's parameters from the flat gradient of the last ``_step(..., with_grad=True)``."""
-        for p, _, gv in self._flat.views:
-            p.grad = gv.clone()
-
     def reg_enc_grad_loss(self, X, weight):
         """core.py:887-910 (forward value)."""
         if self._foreign_pp:
@@ -2491,47 +2493,28 @@ class RegAutoEncoderTask(TrainingTask):
 
     def train(self):
         """core.py:1038-1217."""
-        n = self._feature_traj.shape[0]
-        ll = n - max(self.lag_idx, self.lag_ae_idx)                      # core.py:1042
-        idx_train, idx_test = _split(ll, self.test_ratio)                # core.py:1044 (one draw)
+        ll = self._feature_traj.shape[0] - max(self.lag_idx, self.lag_ae_idx)           # core.py:1042
+        idx_train, idx_test = _agreed_split(ll, self.test_ratio, 1, self.device)         # core.py:1044 (one draw)
         bs_train, bs_test = min(self.batch_size, len(idx_train)), min(self.batch_size, len(idx_test))
-        world, rank = _dist.world(), _dist.rank()
-        if world > 1:   # rank 0's permutation for everyone, then this rank's contiguous slice of every static batch (_dist.shard_batches)
-            both = torch.as_tensor(np.concatenate([idx_train, idx_test]), device=self.device)
-            _dist.broadcast_(both)
-            both = both.cpu().numpy()
-            idx_train, idx_test = both[:len(idx_train)], both[len(idx_train):]
-            assert (bs_train == 0 or bs_train >= world) and (bs_test == 0 or bs_test >= world), \
-                f"batch sizes {bs_train} / {bs_test} smaller than the number of ranks {world}"   # (each set by itself: a rank without steps would leave the others waiting)
-            (ptr, nb_tr), (pte, nb_te) = _dist.shard_batches(len(idx_train), bs_train, rank, world), _dist.shard_batches(len(idx_test), bs_test, rank, world)
-            idx_train, idx_test = np.asarray(idx_train)[ptr], np.asarray(idx_test)[pte]
-        else:
-            nb_tr, nb_te = bs_train, bs_test
-        itr = torch.as_tensor(idx_train, device=self.device, dtype=torch.long)
-        ite = torch.as_tensor(idx_test, device=self.device, dtype=torch.long)
-        wtr, wte = self._weights[itr].contiguous(), self._weights[ite].contiguous()
-        wtr_lag, wte_lag = self._weights[itr + self.lag_idx].contiguous(), self._weights[ite + self.lag_idx].contiguous()
-        tr_batches = [(s, s + nb_tr) for s in range(0, len(idx_train) - nb_tr + 1, nb_tr)] if nb_tr > 0 else []
-        te_batches = [(s, s + nb_te) for s in range(0, len(idx_test) - nb_te + 1, nb_te)] if nb_te > 0 else []
-        # batches are static (shuffle=False): their (global) weight sums are known before the first step
-        wsum_t = torch.stack([wtr[a:b].sum(dtype=torch.float64) for a, b in tr_batches]) if tr_batches else torch.zeros(0, device=self.device, dtype=torch.float64)
-        if world > 1 and len(tr_batches):
-            _dist.allreduce_sum_(wsum_t)
-        wsum_tr = [float(v) for v in wsum_t.cpu()]
+        world = _dist.world()
+
+        def resident(idx, bs):
+            """(rows of the feature trajectory, weights, lagged weights, batches) of the permuted set `idx` for this process: a
+            data-parallel job keeps this rank's contiguous slice of every static batch (_static_batches)."""
+            pos, _, bl = _static_batches(len(idx), bs)
+            it = torch.as_tensor(np.asarray(idx)[pos], device=self.device, dtype=torch.long)
+            return it, self._weights[it].contiguous(), self._weights[it + self.lag_idx].contiguous(), bl
+
+        itr, wtr, wtr_lag, tr_batches = resident(idx_train, bs_train)
+        ite, wte, wte_lag, te_batches = resident(idx_test, bs_test)
+        wsum_tr = _batch_weight_sums(wtr, tr_batches)
         self.loss_list = []
         min_loss = float("inf")
-        if rank == 0:
-            print("\nTraining starts.\n%d epochs in total, batch sizes (train/test): %d/%d" % (self.num_epochs, bs_train, bs_test))
-            print("\nTrain set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_train) * world, len(tr_batches), len(tr_batches) * self.num_epochs), flush=True)
-            print("Test set:\n\t%d data, %d iterations per epoch, %d iterations in total." %
-                  (len(idx_test) * world, len(te_batches), len(te_batches) * self.num_epochs), flush=True)
+        self._announce((bs_train, bs_test), (len(itr) * world, len(ite) * world), (len(tr_batches), len(te_batches)))
         K = self.num_reg
         loss_names = ['loss', 'ae_loss', 'eigen_non_penalty', 'eigen_penalty'] + ['eig_%d' % i for i in range(K)] + \
                      ['encoder_gradient', 'encoder_norm', 'encoder_orthogonality']
-        ncol = len(loss_names)
-        log_tr = torch.zeros(max(len(tr_batches), 1), ncol, device=self.device, dtype=torch.float64)
-        log_te = torch.zeros(max(len(te_batches), 1), ncol, device=self.device, dtype=torch.float64)
+        log_tr, log_te = self._epoch_logs(len(tr_batches), len(te_batches), len(loss_names))
         cvec_log = [torch.zeros(max(K, 1), dtype=torch.float64).pin_memory() for _ in range(4)]   # the ordering, with the ring below
 
         def on_epoch(ep, tr, te):
@@ -2540,33 +2523,24 @@ class RegAutoEncoderTask(TrainingTask):
             if self._use_reg and (tr_batches or te_batches):
                 self._cvec = cvec_log[ep % len(cvec_log)][:K].clone().to(torch.long)          # core.py:1110 (last evaluation)
             self.loss_list.append([tr, te])                                                       # core.py:1202
-            mean_tr = tr.mean(0) if len(tr) else torch.full((ncol,), float("nan"))
-            mean_te = te.mean(0) if len(te) else torch.full((ncol,), float("nan"))
-            for i, name in enumerate(loss_names):                                                 # core.py:1208-1212
-                self.writer.add_scalar('%s/train' % name, mean_tr[i], ep)
-                self.writer.add_scalar('%s/test' % name, mean_te[i], ep)
+            self._write_epoch_means(loss_names, ep, tr, te)                                       # core.py:1208-1212
 
         elog = _AsyncEpochLog(log_tr, log_te, len(tr_batches), len(te_batches), on_epoch)
         dp = _dist.collectives()
-        for epoch in _tqdm(range(self.num_epochs), disable=(rank != 0)):
+        for epoch in _tqdm(range(self.num_epochs), disable=(_dist.rank() != 0)):
             self.model.train()
             for it, (a, b) in enumerate(tr_batches):
                 self._step(self._feature_traj, itr[a:b], wtr[a:b], wtr_lag[a:b], self.lag_ae_idx, self.lag_idx, with_grad=True,
                            advance=True, wsum=wsum_tr[it], out=log_tr[it], dp=dp)
-            saving = self.save_model_every_step > 0 and epoch % self.save_model_every_step == self.save_model_every_step - 1
-            plotting = self.plot_frequency > 0 and epoch % self.plot_frequency == self.plot_frequency - 1
+            saving, plotting = self._due(epoch)
             if saving or plotting:                       # (order of the reference: save / plot before the test pass, core.py:1130-1140)
                 if self._use_reg and tr_batches:
                     self._cvec = self._cvec_dev.cpu().to(torch.long)
             if saving:
-                self.save_model(epoch)
                 last = float(log_tr[len(tr_batches) - 1, 0]) if tr_batches else float("inf")
-                if last < min_loss:
-                    min_loss = last
-                    self.save_model(epoch, 'best')
+                min_loss = self._save_latest_and_best(epoch, last, min_loss)
             if plotting:
-                if self.plot_class is not None and rank == 0:
-                    self.plot_class.plot(self.colvar_model(), self.reg_model(), epoch=epoch)
+                self._plot(epoch)
             for it, (a, b) in enumerate(te_batches):
                 self._step(self._feature_traj, ite[a:b], wte[a:b], wte_lag[a:b], self.lag_ae_idx, self.lag_idx, with_grad=False,
                            out=log_te[it], dp=dp)
@@ -2575,7 +2549,4 @@ class RegAutoEncoderTask(TrainingTask):
                 cvec_log[epoch % len(cvec_log)].copy_(self._cvec_dev, non_blocking=True)
             elog.push(epoch)
         elog.flush_all()
-        self.train_loss_df = pd.DataFrame(torch.cat([e[0].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                          columns=loss_names)
-        self.test_loss_df = pd.DataFrame(torch.cat([e[1].mean(dim=0, keepdim=True) for e in self.loss_list]).numpy(),
-                                         columns=loss_names)
+        self._loss_frames(loss_names)
