@@ -242,6 +242,7 @@ static int ef_stats_impl(const cvf_ef_cfg* cfg, int64_t B, const float* w, const
   CVF_REQUIRE(cfg->k >= 1 && cfg->k <= CVF_MAX_NETS, "cvf_ef_stats: k=%d out of range", cfg->k);
   if (cfg->lag_idx == 0) CVF_REQUIRE(e_tiled, "cvf_ef_stats: generator mode needs e_tiled");
   else CVF_REQUIRE(w_lag && y_lag_tiled, "cvf_ef_stats: transfer mode needs lagged inputs");
+  CVF_REQUIRE(loss_vec == nullptr || coef != nullptr, "cvf_ef_stats: loss_vec without coef");   // (before the first launch: a refused call runs nothing)
   const int ns = cvf_ef_nstats(cfg->k, cfg->lag_idx);
   const int64_t T = cvf_ntiles(B);
   const int G = (int)(T < kStatBlocks ? T : kStatBlocks);
@@ -258,7 +259,6 @@ static int ef_stats_impl(const cvf_ef_cfg* cfg, int64_t B, const float* w, const
   });
   int rc = cvf_check_launch("ef_stats_partial_kernel");
   if (rc) return rc;
-  CVF_REQUIRE(loss_vec == nullptr || coef != nullptr, "cvf_ef_stats: loss_vec without coef");
   return cvf_ef_stats_finish_ll(cfg, G, 0, scratch, stats, loss_vec, coef, s, ll);
 }
 extern "C" int cvf_ef_stats(const cvf_ef_cfg* cfg, int64_t B, const float* w, const float* y_tiled, const float* e_tiled,

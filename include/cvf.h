@@ -150,7 +150,11 @@ int cvf_ef_nstats(int k, int lag_idx);
 /* loss vector written by cvf_ef_loss: [loss, npl, pen, eig_sorted(k), cvec(k) as doubles] */
 #define CVF_LOSS_LEN(k) (3 + 2 * (k))
 /* coefficient vector written by cvf_ef_loss and read by cvf_ef_backward:
- * [gS1(k), gS2(k*k symmetric full), gE_or_gT(k), gS1'(k), gS2'_ii(k)] */
+ * [gS1(k), gS2(k*k symmetric full), gE_or_gT(k), gS1'(k), gS2'_ii(k)]
+ * Each entry is the partial derivative of the loss with respect to the sum of that name, eigenvalues and cvec held constant.
+ * gS2 is [i][j] row-major and symmetric by convention: gS2[i][j] = gS2[j][i] = d loss / d S2(min(i,j), max(i,j)), the derivative
+ * with respect to the ONE stored sum, in both places (not halved).  gS1' and gS2'_ii are 0 in generator mode.  W and W' have no
+ * entry (the weights do not depend on the parameters). */
 #define CVF_COEF_LEN(k) (4 * (k) + (k) * (k))
 
 /* Adam scalars + state for the fused "reduce the gradient and update" calls (single-process runs, where no
@@ -259,7 +263,10 @@ int cvf_ef_fwd_metric_stats(const cvf_mlp_desc* mlp, const float* theta, const f
                             const float* w, double* scratch, double* stats, double* loss_vec, double* coef, void* stream);
 
 /* With stats == NULL the fused launches stop after leaving cvf_ef_fused_stats_rows() (> 0 required) rows of per-tile
- * sums in `scratch`; cvf_ef_stats_finish_rows adds them in a fixed order (and evaluates cvf_ef_loss when loss_vec != NULL). */
+ * sums in `scratch`; cvf_ef_stats_finish_rows adds them in a fixed order (and evaluates cvf_ef_loss when loss_vec != NULL).
+ * Rows read by cvf_ef_stats_finish_rows: partial [n_rows][cvf_ef_nstats(k, lag_idx)] doubles, row-major (statistic i of row r at
+ * partial[r * ns + i]), each row in the layout of the statistics vector above.  With loss_vec == NULL neither loss_vec nor coef
+ * is touched. */
 /* Transfer-operator mode (lag_tau > 0; core.py:403,414): alignment + features + nets forward in one launch for the frames x
  * and their lagged partners x_lag (may be NULL: T tiles only) -> feat_tiled [2T][d_r][64] (tiles T.. = lagged), y_tiled
  * [2T][k][64], saved (cvf_ef_saved_floats(mlp, 2T); may be NULL).  Same shapes as cvf_ef_align_fwd_metric_supported().
@@ -293,7 +300,10 @@ int64_t cvf_ef16_scratch_doubles(int64_t B, int k);
 int64_t cvf_ef16_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles);
 /* With stats == NULL cvf_ef16_front stops after leaving cvf_ef16_rows(B) (> 0 required) rows of per-unit batch sums in `scratch`;
  * cvf_ef16_finish adds them in a fixed order (and evaluates cvf_ef_loss when loss_vec != NULL).  Two calls = two launches that
- * can be timed apart; one call with stats != NULL does both. */
+ * can be timed apart; one call with stats != NULL does both.
+ * Rows read by cvf_ef16_finish: statistic-major, scratch [cvf_ef_nstats(k, lag_idx)][cvf_ef16_rows(B)] doubles (statistic i of
+ * unit r at scratch[i * rows + r]); rows = 4 * ceil(B / 64), at most 16384 (cvf_ef16_rows returns 0 above, and the call is
+ * refused).  With loss_vec == NULL neither loss_vec nor coef is touched. */
 int64_t cvf_ef16_rows(int64_t B);
 int cvf_ef16_finish(const cvf_ef_cfg* cfg, int64_t B, const double* scratch, double* stats, double* loss_vec, double* coef,
                     void* stream);
