@@ -28,6 +28,9 @@ FEAT_ANGLE, FEAT_BOND, FEAT_DIHEDRAL, FEAT_POSITION = 0, 1, 2, 3
 PP_IDENTITY, PP_ALIGN, PP_FACTORED, PP_FEATURES = 0, 1, 2, 3
 FEATURES_MAX_SLOT, FEATURES_MAX_REF = 4096, 6144   # CVF_PP_FEATURES limits (include/cvf.h, csrc/k1_features.hip)
 PP_ALIGN_CONTIG, PP_PURE_POSITION, PP_SLOT_BATCHED = 1, 2, 4
+# cvf_align_feature_route (include/cvf.h): slice / pipe codes are the base + NI
+K1_ROUTE_SMALL, K1_ROUTE_GATHER_CONTIG, K1_ROUTE_GATHER, K1_ROUTE_CAPTURE_VEC4, K1_ROUTE_CAPTURE = 0, 1, 2, 3, 4
+K1_ROUTE_SLICE, K1_ROUTE_PIPE = 10, 20
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcvf_hip.so")
@@ -66,6 +69,7 @@ _SIGNATURES = {
     "cvf_align_feature_scratch_bytes": (C.c_int64, [C.POINTER(PPDesc), C.c_int64]),
     "cvf_align_feature_fwd": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "cvf_align_feature_route": (C.c_int, [C.POINTER(PPDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "cvf_align_feature_vjp": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "cvf_align_feature_vjp_rows": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,

@@ -79,10 +79,15 @@ class AlignFeatureLayer(torch.nn.Module):
         align_weights: optional ``[n_align]`` non-negative per-atom weights w_b of the alignment (masses, say): the
             frame's weighted centroid goes to the reference's and the rotation minimises
             ``sum_b w_b |(x_b - c) R - ref_b|^2``.  ``None`` = the uniform weights of molann's layer.  Weighted layers
-            run on the general kernels only (at most 64 atoms per frame).
+            of at most 64 atoms run on the general lane-per-frame kernels; larger ones need ``weights_any_size``.
+        weights_any_size: opt-in, like ``general_nets=True`` of the tasks: a weighted layer of MORE than 64 atoms is built for
+            the streaming kernels of large molecules (csrc/k1_large.hip and the large-frame derivative kernels), which take
+            the weights at any size.  The table flags (contiguous align set, batched slot records) are kept - they describe
+            the tables, not the weights.  With at most 64 atoms the option changes nothing; without it such a layer is
+            refused as before.
     """
 
-    def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None):
+    def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None, weights_any_size=False):
         super().__init__()
         self.aligned = align_idx is not None
         if not self.aligned:
@@ -119,14 +124,18 @@ class AlignFeatureLayer(torch.nn.Module):
         # centroid and pre-multiplied by them (include/cvf.h, cvf_pp_desc.align_w) - the covariance
         # sum_b w_b (x_b - c) (x) ref_b is then the same loop as the unweighted one
         w_hat = None
+        weighted_large = align_weights is not None and bool(weights_any_size) and 3 * n_atoms > 192
         if align_weights is not None:
             w = np.asarray(align_weights, dtype=np.float64).reshape(-1)
             assert w.shape == (len(align_idx),), f"align_weights must be [{len(align_idx)}], got {w.shape}"
             assert np.all(np.isfinite(w)) and np.all(w >= 0) and np.count_nonzero(w) >= 3, \
                 "align_weights must be finite, non-negative, with at least 3 non-zero entries"
-            assert 3 * n_atoms <= 192, "weighted alignment is built for frames of at most 64 atoms"
+            assert weighted_large or 3 * n_atoms <= 192, "weighted alignment is built for frames of at most 64 atoms"
             w_hat = w * (len(w) / w.sum())
-            flags = 0   # the fast layouts assume uniform weights
+            if weighted_large:   # the streaming kernels: the table flags stay, PURE_POSITION means nothing there
+                flags &= _hip.PP_ALIGN_CONTIG
+            else:
+                flags = 0   # the fast layouts assume uniform weights
         self._flags = flags
         # per-atom tables for the streaming kernel of large molecules (include/cvf.h): which ref row an atom aligns
         # to, and the compact "slot" of every atom some feature reads
@@ -145,7 +154,7 @@ class AlignFeatureLayer(torch.nn.Module):
         # free; type -1 entries are padding)
         by_type = sorted(rec_slot, key=lambda r: r[0])
         rec_slot = _batch_records(by_type)
-        if w_hat is None and self.aligned:
+        if (w_hat is None or weighted_large) and self.aligned:
             self._flags |= _hip.PP_SLOT_BATCHED
         self._n_rec_slot = len(rec_slot)
         self._n_slot = len(used)
@@ -327,8 +336,9 @@ class FeatureLayer:
 class AlignmentLayer:
     """``AlignmentLayer(align_atom_group, input_atom_group)`` (main.ipynb:345)."""
 
-    def __init__(self, align_atom_group, input_atom_group, weights=None):
+    def __init__(self, align_atom_group, input_atom_group, weights=None, weights_any_size=False):
         self.weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+        self.weights_any_size = bool(weights_any_size)   # (AlignFeatureLayer: weighted layers of more than 64 atoms, opt-in)
         self.align_ix = _ix(align_atom_group)
         self.input_ix = _ix(input_atom_group)
         lut = {int(g): i for i, g in enumerate(self.input_ix)}
@@ -355,7 +365,8 @@ class PreprocessingANN(AlignFeatureLayer):
             return
         assert np.array_equal(align_layer.input_ix, feature_layer.input_ix), "align and feature layers use different input atoms"
         super().__init__(len(align_layer.input_ix), align_layer.local_idx, align_layer.ref_c, feature_layer.local,
-                         feature_layer.use_angle_value, align_weights=getattr(align_layer, "weights", None))
+                         feature_layer.use_angle_value, align_weights=getattr(align_layer, "weights", None),
+                         weights_any_size=getattr(align_layer, "weights_any_size", False))
 
 
 def identity_desc(n_coord):

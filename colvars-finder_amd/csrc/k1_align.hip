@@ -691,8 +691,8 @@ extern "C" int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int6
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
               "cvf_align_feature_fwd: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
-  CVF_REQUIRE(!pp->align_w || (pp->flags == 0 && pp->n_coord <= kLanePerFrameMaxCoord),
-              "cvf_align_feature_fwd: per-atom alignment weights need flags == 0 and at most %d coordinates per frame",
+  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
+              "cvf_align_feature_fwd: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
               kLanePerFrameMaxCoord);
   if (pp->n_coord > kLanePerFrameMaxCoord) {
     return cvf_k1_large_launch(pp, x, B, feat_tiled, feat_rows, aux_tiled, (float*)scratch, s);
@@ -793,8 +793,8 @@ static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, c
     return cvf_features_metric_launch(pp, x, B, a, k, g_tiled, q_tiled, e_tiled, s);
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
   CVF_REQUIRE(aux_tiled, "cvf_metric_apply: align mode needs aux");
-  CVF_REQUIRE(!pp->align_w || (pp->flags == 0 && pp->n_coord <= kLanePerFrameMaxCoord),
-              "cvf_metric_apply: per-atom alignment weights need flags == 0 and at most %d coordinates per frame",
+  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
+              "cvf_metric_apply: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
               kLanePerFrameMaxCoord);
   if (pp->n_coord > kLanePerFrameMaxCoord) {
     CVF_REQUIRE(slot_xyz && dense && pp->rec_slot && pp->slot_atom && pp->atom_align && pp->n_slot > 0,

@@ -27,7 +27,10 @@ __device__ __forceinline__ int64_t k1_group_of_block(bool same_xcd) {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + ix;
 }
 
-template <bool CONTIG>
+// WEIGHTED (all three streaming kernels below): per-atom alignment weights (cvf_pp_desc.align_w, mean 1; ref_c holds w_b (ref_b - weighted
+// centroid) already): the centroid is sum_b w_b x_b / n_align, so the three centroid sums take w_b x_b and nothing else changes -
+// H = sum x (x) ref_c - c (x) sum ref_c as before.  The uniform twins are the code they were.
+template <bool CONTIG, bool WEIGHTED>
 __global__ __launch_bounds__(64 * kGroup) void k1_large_gather_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B,
                                                                float* __restrict__ feat_tiled, float* __restrict__ feat_rows,
                                                                float* __restrict__ aux_tiled) {
@@ -53,7 +56,12 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_gather_kernel(cvf_pp_des
     const float r0 = pp.ref_c[3 * b], r1 = pp.ref_c[3 * b + 1], r2 = pp.ref_c[3 * b + 2];
     const double d0 = (double)x0, d1 = (double)x1, d2 = (double)x2;
     const double e0 = (double)r0, e1 = (double)r1, e2 = (double)r2;
-    acc[0] += d0; acc[1] += d1; acc[2] += d2;
+    if (WEIGHTED) {
+      const double wb = (double)pp.align_w[b];
+      acc[0] = fma(wb, d0, acc[0]); acc[1] = fma(wb, d1, acc[1]); acc[2] = fma(wb, d2, acc[2]);
+    } else {
+      acc[0] += d0; acc[1] += d1; acc[2] += d2;
+    }
     acc[3] = fma(d0, e0, acc[3]); acc[4] = fma(d0, e1, acc[4]); acc[5] = fma(d0, e2, acc[5]);
     acc[6] = fma(d1, e0, acc[6]); acc[7] = fma(d1, e1, acc[7]); acc[8] = fma(d1, e2, acc[8]);
     acc[9] = fma(d2, e0, acc[9]); acc[10] = fma(d2, e1, acc[10]); acc[11] = fma(d2, e2, acc[11]);
@@ -147,10 +155,16 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_gather_kernel(cvf_pp_des
 struct Acc15 {
   double v[15];
 };
-__device__ __forceinline__ void acc_atom(Acc15& A, float x0, float x1, float x2, float r0, float r1, float r2) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void acc_atom(Acc15& A, float x0, float x1, float x2, float r0, float r1, float r2, float wb) {
   const double d0 = (double)x0, d1 = (double)x1, d2 = (double)x2;
   const double e0 = (double)r0, e1 = (double)r1, e2 = (double)r2;
-  A.v[0] += d0; A.v[1] += d1; A.v[2] += d2;
+  if (WEIGHTED) {
+    const double wd = (double)wb;
+    A.v[0] = fma(wd, d0, A.v[0]); A.v[1] = fma(wd, d1, A.v[1]); A.v[2] = fma(wd, d2, A.v[2]);
+  } else {
+    A.v[0] += d0; A.v[1] += d1; A.v[2] += d2;
+  }
   A.v[3] = fma(d0, e0, A.v[3]); A.v[4] = fma(d0, e1, A.v[4]); A.v[5] = fma(d0, e2, A.v[5]);
   A.v[6] = fma(d1, e0, A.v[6]); A.v[7] = fma(d1, e1, A.v[7]); A.v[8] = fma(d1, e2, A.v[8]);
   A.v[9] = fma(d2, e0, A.v[9]); A.v[10] = fma(d2, e1, A.v[10]); A.v[11] = fma(d2, e2, A.v[11]);
@@ -304,22 +318,27 @@ __device__ __forceinline__ void large_solve_features(const cvf_pp_desc& pp, int6
 }
 
 // fp32 partial sums of the same fifteen quantities over a few atoms (see the VEC4 loop)
-__device__ __forceinline__ void part_first(float (&s)[15], float x0, float x1, float x2, float r0, float r1, float r2) {
-  s[0] = x0; s[1] = x1; s[2] = x2;
+// (WEIGHTED: the centroid sums take w x)
+template <bool WEIGHTED>
+__device__ __forceinline__ void part_first(float (&s)[15], float x0, float x1, float x2, float r0, float r1, float r2, float wb) {
+  if (WEIGHTED) { s[0] = wb * x0; s[1] = wb * x1; s[2] = wb * x2; }
+  else { s[0] = x0; s[1] = x1; s[2] = x2; }
   s[3] = x0 * r0; s[4] = x0 * r1; s[5] = x0 * r2;
   s[6] = x1 * r0; s[7] = x1 * r1; s[8] = x1 * r2;
   s[9] = x2 * r0; s[10] = x2 * r1; s[11] = x2 * r2;
   s[12] = r0; s[13] = r1; s[14] = r2;
 }
-__device__ __forceinline__ void part_next(float (&s)[15], float x0, float x1, float x2, float r0, float r1, float r2) {
-  s[0] += x0; s[1] += x1; s[2] += x2;
+template <bool WEIGHTED>
+__device__ __forceinline__ void part_next(float (&s)[15], float x0, float x1, float x2, float r0, float r1, float r2, float wb) {
+  if (WEIGHTED) { s[0] = fmaf(wb, x0, s[0]); s[1] = fmaf(wb, x1, s[1]); s[2] = fmaf(wb, x2, s[2]); }
+  else { s[0] += x0; s[1] += x1; s[2] += x2; }
   s[3] = fmaf(x0, r0, s[3]); s[4] = fmaf(x0, r1, s[4]); s[5] = fmaf(x0, r2, s[5]);
   s[6] = fmaf(x1, r0, s[6]); s[7] = fmaf(x1, r1, s[7]); s[8] = fmaf(x1, r2, s[8]);
   s[9] = fmaf(x2, r0, s[9]); s[10] = fmaf(x2, r1, s[10]); s[11] = fmaf(x2, r2, s[11]);
   s[12] += r0; s[13] += r1; s[14] += r2;
 }
 
-template <bool VEC4>
+template <bool VEC4, bool WEIGHTED>
 __global__ __launch_bounds__(64 * kGroup) void k1_large_capture_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B,
                                                                        float* __restrict__ feat_tiled,
                                                                        float* __restrict__ feat_rows,
@@ -355,11 +374,13 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_capture_kernel(cvf_pp_de
         // tools/stream_probe.hip reads 6.3 TB/s with the same load pattern).  A partial sum of four products of
         // O(1e3) magnitude carries ~4e-4 absolute rounding; over 1250 of them that is 1e-8 of the covariance entries.
         const float4 p = r4[3 * g], q = r4[3 * g + 1], r = r4[3 * g + 2];
+        const float4 one = {1.0f, 1.0f, 1.0f, 1.0f};
+        const float4 wv = WEIGHTED ? reinterpret_cast<const float4*>(pp.align_w)[g] : one;   // (the launch checked its alignment)
         float s[15];
-        part_first(s, a.x, a.y, a.z, p.x, p.y, p.z);
-        part_next(s, a.w, b.x, b.y, p.w, q.x, q.y);
-        part_next(s, b.z, b.w, c.x, q.z, q.w, r.x);
-        part_next(s, c.y, c.z, c.w, r.y, r.z, r.w);
+        part_first<WEIGHTED>(s, a.x, a.y, a.z, p.x, p.y, p.z, wv.x);
+        part_next<WEIGHTED>(s, a.w, b.x, b.y, p.w, q.x, q.y, wv.y);
+        part_next<WEIGHTED>(s, b.z, b.w, c.x, q.z, q.w, r.x, wv.z);
+        part_next<WEIGHTED>(s, c.y, c.z, c.w, r.y, r.z, r.w, wv.w);
 #pragma unroll
         for (int i = 0; i < 15; ++i) A.v[i] += (double)s[i];
       }
@@ -374,7 +395,7 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_capture_kernel(cvf_pp_de
       const float x0 = xf[3 * a], x1 = xf[3 * a + 1], x2 = xf[3 * a + 2];
       const int b = pp.atom_align[a];
       const int sl = pp.atom_slot[a];
-      if (b >= 0) acc_atom(A, x0, x1, x2, pp.ref_c[3 * b], pp.ref_c[3 * b + 1], pp.ref_c[3 * b + 2]);
+      if (b >= 0) acc_atom<WEIGHTED>(A, x0, x1, x2, pp.ref_c[3 * b], pp.ref_c[3 * b + 1], pp.ref_c[3 * b + 2], WEIGHTED ? pp.align_w[b] : 1.0f);
       if (sl >= 0) { capL[3 * sl] = x0; capL[3 * sl + 1] = x1; capL[3 * sl + 2] = x2; }
     }
   }
@@ -406,7 +427,8 @@ __global__ __launch_bounds__(64 * kGroup) void k1_large_capture_kernel(cvf_pp_de
 // (min. 4 waves per SIMD = 128 registers = TWO workgroups per CU, which this kernel's loop without prefetch relies on.  Round 4's first edits of
 //  the tail took it to 130 registers - 3 waves per SIMD, ONE 8-wave workgroup per CU - unnoticed for most of the round: 1131-1221 us per 100 000
 //  frames of 5000 atoms instead of 1078-1153.  NI = 4 (6145..8192 atoms) would spill 17 registers at 128 and stays at one workgroup per CU.)
-template <int NI, bool NT>
+// WEIGHTED: the lane's mask (1 on the align set) becomes the four weights of its four atoms (0 off the set) - three registers more per NI.
+template <int NI, bool NT, bool WEIGHTED>
 __global__ __launch_bounds__(64 * kGroup, NI <= 3 ? 4 : 2) void k1_large_slice_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B,
                                                                      float* __restrict__ feat_tiled,
                                                                      float* __restrict__ feat_rows,
@@ -433,6 +455,7 @@ __global__ __launch_bounds__(64 * kGroup, NI <= 3 ? 4 : 2) void k1_large_slice_k
   int4 sl[NI];
   int gi[NI];
   float mk[NI];
+  float4 wk[WEIGHTED ? NI : 1];
   float rs0 = 0.0f, rs1 = 0.0f, rs2 = 0.0f;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
@@ -446,6 +469,10 @@ __global__ __launch_bounds__(64 * kGroup, NI <= 3 ? 4 : 2) void k1_large_slice_k
     rq[i] = al ? q : z;
     rr[i] = al ? r : z;
     mk[i] = al ? 1.0f : 0.0f;
+    if (WEIGHTED) {
+      const float4 wv = reinterpret_cast<const float4*>(pp.align_w)[ga];   // (the launch checked its alignment)
+      wk[WEIGHTED ? i : 0] = al ? wv : z;
+    }
     const int4 sv = s4[gi[i]];
     sl[i] = valid ? sv : int4{-1, -1, -1, -1};
     rs0 += rp[i].x + rp[i].w + rq[i].z + rr[i].y;
@@ -480,16 +507,17 @@ __global__ __launch_bounds__(64 * kGroup, NI <= 3 ? 4 : 2) void k1_large_slice_k
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       // (rows of atoms outside the align set are zero, their coordinates are masked out of the centroid)
-      auto atom4 = [&](float x0, float x1, float x2, float r0, float r1, float r2) {
-        s[0] = fmaf(mk[i], x0, s[0]); s[1] = fmaf(mk[i], x1, s[1]); s[2] = fmaf(mk[i], x2, s[2]);
+      auto atom4 = [&](float x0, float x1, float x2, float r0, float r1, float r2, float m) {
+        s[0] = fmaf(m, x0, s[0]); s[1] = fmaf(m, x1, s[1]); s[2] = fmaf(m, x2, s[2]);
         s[3] = fmaf(x0, r0, s[3]); s[4] = fmaf(x0, r1, s[4]); s[5] = fmaf(x0, r2, s[5]);
         s[6] = fmaf(x1, r0, s[6]); s[7] = fmaf(x1, r1, s[7]); s[8] = fmaf(x1, r2, s[8]);
         s[9] = fmaf(x2, r0, s[9]); s[10] = fmaf(x2, r1, s[10]); s[11] = fmaf(x2, r2, s[11]);
       };
-      atom4(a[i].x, a[i].y, a[i].z, rp[i].x, rp[i].y, rp[i].z);
-      atom4(a[i].w, b[i].x, b[i].y, rp[i].w, rq[i].x, rq[i].y);
-      atom4(b[i].z, b[i].w, c[i].x, rq[i].z, rq[i].w, rr[i].x);
-      atom4(c[i].y, c[i].z, c[i].w, rr[i].y, rr[i].z, rr[i].w);
+      const int iw = WEIGHTED ? i : 0;
+      atom4(a[i].x, a[i].y, a[i].z, rp[i].x, rp[i].y, rp[i].z, WEIGHTED ? wk[iw].x : mk[i]);
+      atom4(a[i].w, b[i].x, b[i].y, rp[i].w, rq[i].x, rq[i].y, WEIGHTED ? wk[iw].y : mk[i]);
+      atom4(b[i].z, b[i].w, c[i].x, rq[i].z, rq[i].w, rr[i].x, WEIGHTED ? wk[iw].z : mk[i]);
+      atom4(c[i].y, c[i].z, c[i].w, rr[i].y, rr[i].z, rr[i].w, WEIGHTED ? wk[iw].w : mk[i]);
       if (sl[i].x >= 0) { capL[3 * sl[i].x] = a[i].x; capL[3 * sl[i].x + 1] = a[i].y; capL[3 * sl[i].x + 2] = a[i].z; }
       if (sl[i].y >= 0) { capL[3 * sl[i].y] = a[i].w; capL[3 * sl[i].y + 1] = b[i].x; capL[3 * sl[i].y + 2] = b[i].y; }
       if (sl[i].z >= 0) { capL[3 * sl[i].z] = b[i].z; capL[3 * sl[i].z + 1] = b[i].w; capL[3 * sl[i].z + 2] = c[i].x; }
@@ -1025,10 +1053,108 @@ size_t cvf_k1_large_scratch_bytes(const cvf_pp_desc* pp, int64_t B) {
   return capture_ok(pp, true) ? (size_t)cvf_ntiles(B) * CVF_TILE * pp->n_slot * 3 * sizeof(float) : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Which kernel family and instance a streaming launch takes (host arithmetic; cvf_align_feature_route answers with it and
+// cvf_k1_large_launch launches by it).  x16 / rows16: the coordinate and row-major output pointers are 16-byte aligned.
+namespace {
+struct K1Plan {
+  int code;            // CVF_K1_ROUTE_*
+  int ni;              // slice / pipe: groups of 4 atoms per lane
+  int64_t groups;      // frame groups of kGroup
+  size_t lds;          // dynamic LDS bytes
+  int64_t nquads, grid;   // pipe
+  int rounds;             // pipe
+};
+}  // namespace
+
+static int k1_large_plan(const cvf_pp_desc* pp, int64_t B, bool tiled, bool rows, bool aux, bool scratch, bool x16, bool rows16,
+                         K1Plan* P) {
+  const bool contig = (pp->flags & CVF_PP_ALIGN_CONTIG) != 0;
+  // per-atom alignment weights (cvf_pp_desc.align_w): the WEIGHTED twins of the gather, capture and slice kernels; never the pipelined
+  // kernel (its gain is -1 .. -4 % on one output flavour: not worth a fourth weighted family)
+  const bool weighted = pp->align_w != nullptr;
+  P->ni = 0;
+  P->nquads = P->grid = 0;
+  P->rounds = -1;
+  P->groups = tiled || aux || scratch ? cvf_ntiles(B) * (CVF_TILE / kGroup) : (B + kGroup - 1) / kGroup;
+  const int64_t groups = P->groups;
+  const bool staged = tiled || rows;   // features leave through an LDS staging area
+  if (capture_ok(pp, staged)) {
+    const size_t ldsc = ((size_t)kGroup * pp->n_slot * 3 + (staged ? (size_t)pp->d_r * kGroup : 0)) * sizeof(float);
+    P->lds = ldsc;
+    const int N = pp->n_coord / 3;
+    // (align_w: one 16-byte load per four align atoms in the vectorised instances, like ref_c and atom_slot)
+    const bool vec4 = contig && (N % 4 == 0) && (pp->n_align % 4 == 0) && x16 && (((uintptr_t)pp->ref_c & 15) == 0) &&
+                      (((uintptr_t)pp->atom_slot & 15) == 0) && (!weighted || ((uintptr_t)pp->align_w & 15) == 0);
+    const int ni = (N / 4 + 64 * kGroup - 1) / (64 * kGroup);
+    // (the slice kernel stages its reductions in the feature staging area: needs the tiled output's buffer)
+    const bool slice = vec4 && ni <= 4 && staged && (size_t)pp->d_r * kGroup >= (size_t)kGroup * 4 * 68 &&
+                       getenv("CVF_K1_NOSLICE") == nullptr;
+    // large batches: the pipelined kernel (one resident workgroup per CU; streaming waves + tail waves).  It needs two capture
+    // buffers in LDS and enough groups per workgroup for the overlap to matter; CVF_K1_NOPIPE=1: developer switch (A/B).
+    const int ncu = cvf_cu_count();
+    const size_t lds_pipe = (2 * (size_t)kGroup * pp->n_slot * 3 + (size_t)pp->d_r * kGroup + (size_t)kStream * 4 * kRedPitchP +
+                             6 * (size_t)(pp->n_rec_slot > 0 ? pp->n_rec_slot : pp->n_rec)) * sizeof(float);   // (+ 14.4 KB of static arrays: 160 KB in all)
+    // Where it pays against the one-group-per-workgroup kernel at two workgroups per CU (tools/k1_ab2.sh, both in one lease, two kinds of box,
+    // us per launch pipelined / other): tiled features only - 16 000 frames 194 / 192, 24 000: 279 / 284, 32 768: 372 / 383, 100 000: 1065-1118 /
+    // 1078-1153; with the generator-mode outputs (slot copy: 11 % of the bytes, written whole by either kernel) - 16 000: 225 / 218, 50 000: 675 / 667,
+    // 100 000: 1254-1336 / 1240-1343 (by box: from 1.3 % faster to 7 % slower); row-major output alone (one 12-KB run per group either way):
+    // 1067-1123 / 1032-1110.  So: tiled features alone from 24 576 frames on; never with the generator-mode outputs or for the row-major output.
+    // (developer switches: CVF_K1_PIPE_MIN_GROUPS - with single groups only below four groups per compute unit: 2000 frames 41 us / 34, 8000: 120 / 113;
+    //  CVF_K1_NOPIPE)
+    const int64_t pipe_min = getenv("CVF_K1_PIPE_MIN_GROUPS") ? atoll(getenv("CVF_K1_PIPE_MIN_GROUPS")) : -1;
+    const int64_t pipe_from = pipe_min >= 0 ? pipe_min : (!tiled || aux || scratch ? INT64_MAX : 12 * (int64_t)ncu);
+    if (!weighted && vec4 && ni <= 3 && staged && groups >= pipe_from && lds_pipe <= 145 * 1024 && 3 * pp->n_slot < 0xffff && pp->d_r <= 384 &&
+        (tiled || rows16) && getenv("CVF_K1_NOPIPE") == nullptr) {
+      const int64_t nquads = (groups + 3) / 4;   // (tiled outputs: groups is a multiple of 8)
+      // quads only, or whole rounds of quads and the groups behind them one at a time - whichever gives the busiest workgroup fewer groups;
+      // fewer than four groups per compute unit: single groups only
+      int64_t grid = nquads < ncu ? nquads : ncu;
+      const int64_t r_all = (nquads + grid - 1) / grid, r_full = nquads / grid;
+      const int64_t left = groups - 4 * grid * r_full, with_singles = 4 * r_full + (left + grid - 1) / grid;
+      int rounds = r_full >= 1 && with_singles < 4 * r_all ? (int)r_full : -1;
+      if (groups < 4 * (int64_t)ncu) {
+        grid = groups < ncu ? groups : ncu;
+        rounds = 0;
+      }
+      P->ni = ni;
+      P->lds = lds_pipe;
+      P->nquads = nquads;
+      P->grid = grid;
+      P->rounds = rounds;
+      return P->code = CVF_K1_ROUTE_PIPE + ni;
+    }
+    if (slice) {
+      P->ni = ni;
+      return P->code = CVF_K1_ROUTE_SLICE + ni;
+    }
+    return P->code = vec4 ? CVF_K1_ROUTE_CAPTURE_VEC4 : CVF_K1_ROUTE_CAPTURE;
+  }
+  P->lds = tiled ? (size_t)pp->d_r * kGroup * sizeof(float) : 0;
+  CVF_REQUIRE(P->lds <= 96 * 1024, "cvf_align_feature_fwd: %d features do not fit the staging buffer", pp->d_r);
+  return P->code = contig ? CVF_K1_ROUTE_GATHER_CONTIG : CVF_K1_ROUTE_GATHER;
+}
+
+extern "C" int cvf_align_feature_route(const cvf_pp_desc* pp, int64_t B, int has_tiled, int has_rows, int has_aux, int has_scratch) {
+  CVF_REQUIRE(pp && B > 0, "cvf_align_feature_route: null descriptor or empty batch (B=%lld)", (long long)B);
+  CVF_REQUIRE(has_tiled || has_rows, "cvf_align_feature_route: no output buffer");
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "cvf_align_feature_route: CVF_PP_ALIGN descriptors only (mode %d)", pp->mode);
+  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
+              "cvf_align_feature_route: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
+  if (pp->n_coord <= 192) {
+    CVF_REQUIRE(!pp->align_w || pp->flags == 0,
+                "cvf_align_feature_route: per-atom alignment weights on frames of at most 192 coordinates need flags == 0");
+    return CVF_K1_ROUTE_SMALL;
+  }
+  K1Plan P;
+  // (the compact feature-atom copy is written only where the capturing kernels run: cvf_align_feature_scratch_bytes answers 0 otherwise)
+  return k1_large_plan(pp, B, has_tiled != 0, has_rows != 0, has_aux != 0, has_scratch != 0 && cvf_k1_large_scratch_bytes(pp, B) > 0,
+                       true, true, &P);
+}
+
 // called from cvf_align_feature_fwd (k1_align.hip) when the frame does not fit the lane-per-frame tile
 int cvf_k1_large_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows,
                         float* aux_tiled, float* slot_xyz, hipStream_t s) {
-  const bool contig = (pp->flags & CVF_PP_ALIGN_CONTIG) != 0;
   // CVF_K1_XCD=1: the frame groups of a 64-frame tile on ONE XCD (their 32-byte pieces of the tiled rows meet in one L2); 0 / unset:
   // blockIdx order (developer switch: bench.py's A/B of the two)
   const int xcd_env = getenv("CVF_K1_XCD") ? atoi(getenv("CVF_K1_XCD")) : -1;
@@ -1041,108 +1167,82 @@ int cvf_k1_large_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float*
     if (!told) fprintf(stderr, "[cvf] CVF_K1_XCD=%d: developer timing probe - the outputs of cvf_align_feature_fwd are WRONG\n", same_xcd);
     told = true;
   }
-  const int64_t groups = feat_tiled || aux_tiled || slot_xyz ? cvf_ntiles(B) * (CVF_TILE / kGroup) : (B + kGroup - 1) / kGroup;
-  const bool staged = feat_tiled != nullptr || feat_rows != nullptr;   // features leave through an LDS staging area
-  if (capture_ok(pp, staged)) {
-    const size_t ldsc = ((size_t)kGroup * pp->n_slot * 3 + (staged ? (size_t)pp->d_r * kGroup : 0)) * sizeof(float);
-    {
-      const int N = pp->n_coord / 3;
-      const bool vec4 = contig && (N % 4 == 0) && (pp->n_align % 4 == 0) && (((uintptr_t)x & 15) == 0) &&
-                        (((uintptr_t)pp->ref_c & 15) == 0) && (((uintptr_t)pp->atom_slot & 15) == 0);
-      if (ldsc > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void*)k1_large_capture_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
-        (void)hipFuncSetAttribute((const void*)k1_large_capture_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
+  K1Plan P;
+  const int code = k1_large_plan(pp, B, feat_tiled != nullptr, feat_rows != nullptr, aux_tiled != nullptr, slot_xyz != nullptr,
+                                 ((uintptr_t)x & 15) == 0, ((uintptr_t)feat_rows & 15) == 0, &P);
+  if (code < 0) return code;
+  const bool weighted = pp->align_w != nullptr;
+  const int64_t groups = P.groups;
+  if (code > CVF_K1_ROUTE_PIPE) {
+    auto go = [&](auto kernel) {
+      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
+      const int probe = getenv("CVF_K1_PIPE_PROBE") ? atoi(getenv("CVF_K1_PIPE_PROBE")) : 0;
+      if (probe != 0) {
+        static bool told = false;
+        if (!told) fprintf(stderr, "[cvf] CVF_K1_PIPE_PROBE=%d: developer timing probe - the outputs of cvf_align_feature_fwd are WRONG\n", probe);
+        told = true;
       }
-      const int ni = (N / 4 + 64 * kGroup - 1) / (64 * kGroup);
-      // (the slice kernel stages its reductions in the feature staging area: needs the tiled output's buffer)
-      const bool slice = vec4 && ni <= 4 && staged && (size_t)pp->d_r * kGroup >= (size_t)kGroup * 4 * 68 &&
-                         getenv("CVF_K1_NOSLICE") == nullptr;
-      // large batches: the pipelined kernel (one resident workgroup per CU; streaming waves + tail waves).  It needs two capture
-      // buffers in LDS and enough groups per workgroup for the overlap to matter; CVF_K1_NOPIPE=1: developer switch (A/B).
-      const int ncu = cvf_cu_count();
-      const size_t lds_pipe = (2 * (size_t)kGroup * pp->n_slot * 3 + (size_t)pp->d_r * kGroup + (size_t)kStream * 4 * kRedPitchP +
-                               6 * (size_t)(pp->n_rec_slot > 0 ? pp->n_rec_slot : pp->n_rec)) * sizeof(float);   // (+ 14.4 KB of static arrays: 160 KB in all)
-      // Where it pays against the one-group-per-workgroup kernel at two workgroups per CU (tools/k1_ab2.sh, both in one lease, two kinds of box,
-      // us per launch pipelined / other): tiled features only - 16 000 frames 194 / 192, 24 000: 279 / 284, 32 768: 372 / 383, 100 000: 1065-1118 /
-      // 1078-1153; with the generator-mode outputs (slot copy: 11 % of the bytes, written whole by either kernel) - 16 000: 225 / 218, 50 000: 675 / 667,
-      // 100 000: 1254-1336 / 1240-1343 (by box: from 1.3 % faster to 7 % slower); row-major output alone (one 12-KB run per group either way):
-      // 1067-1123 / 1032-1110.  So: tiled features alone from 24 576 frames on; never with the generator-mode outputs or for the row-major output.
-      // (developer switches: CVF_K1_PIPE_MIN_GROUPS - with single groups only below four groups per compute unit: 2000 frames 41 us / 34, 8000: 120 / 113;
-      //  CVF_K1_NOPIPE)
-      const int64_t pipe_min = getenv("CVF_K1_PIPE_MIN_GROUPS") ? atoll(getenv("CVF_K1_PIPE_MIN_GROUPS")) : -1;
-      const int64_t pipe_from = pipe_min >= 0 ? pipe_min : (feat_tiled == nullptr || aux_tiled || slot_xyz ? INT64_MAX : 12 * (int64_t)ncu);
-      if (vec4 && ni <= 3 && staged && groups >= pipe_from && lds_pipe <= 145 * 1024 && 3 * pp->n_slot < 0xffff && pp->d_r <= 384 &&
-          (feat_tiled != nullptr || ((uintptr_t)feat_rows & 15) == 0) && getenv("CVF_K1_NOPIPE") == nullptr) {
-        const int64_t nquads = (groups + 3) / 4;   // (tiled outputs: groups is a multiple of 8)
-        // quads only, or whole rounds of quads and the groups behind them one at a time - whichever gives the busiest workgroup fewer groups;
-        // fewer than four groups per compute unit: single groups only
-        int64_t grid = nquads < ncu ? nquads : ncu;
-        const int64_t r_all = (nquads + grid - 1) / grid, r_full = nquads / grid;
-        const int64_t left = groups - 4 * grid * r_full, with_singles = 4 * r_full + (left + grid - 1) / grid;
-        int rounds = r_full >= 1 && with_singles < 4 * r_all ? (int)r_full : -1;
-        if (groups < 4 * (int64_t)ncu) {
-          grid = groups < ncu ? groups : ncu;
-          rounds = 0;
-        }
-        auto go = [&](auto kernel) {
-          (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe);
-          const int probe = getenv("CVF_K1_PIPE_PROBE") ? atoi(getenv("CVF_K1_PIPE_PROBE")) : 0;
-          if (probe != 0) {
-            static bool told = false;
-            if (!told) fprintf(stderr, "[cvf] CVF_K1_PIPE_PROBE=%d: developer timing probe - the outputs of cvf_align_feature_fwd are WRONG\n", probe);
-            told = true;
-          }
-          hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * (kStream + kTail)), lds_pipe, s, *pp, x, B, nquads, groups, rounds,
-                             feat_tiled, feat_rows, aux_tiled, slot_xyz, probe);
-        };
-        if (ni == 1) go(k1_large_pipe_kernel<1>);
-        else if (ni == 2) go(k1_large_pipe_kernel<2>);
-        else go(k1_large_pipe_kernel<3>);
-        return cvf_check_launch("k1_large_pipe_kernel");
-      }
-      if (slice) {
-        auto go = [&](auto kernel) {
-          if (ldsc > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
-          hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * kGroup), ldsc, s, *pp, x, B, feat_tiled, feat_rows, aux_tiled,
-                             slot_xyz, same_xcd);
-        };
-        // non-temporal coordinate loads, a developer switch: measured 1592 us against 1065 us (0.48 vs 0.72 of 8 TB/s) for
-        // 100 000 frames of 5000 atoms (tools/bench_k1_c5.py) - the plain loads stay the default
-        static const bool nt = getenv("CVF_K1_NT") != nullptr && atoi(getenv("CVF_K1_NT")) != 0;
-        if (nt) {
-          if (ni == 1) go(k1_large_slice_kernel<1, true>);
-          else if (ni == 2) go(k1_large_slice_kernel<2, true>);
-          else if (ni == 3) go(k1_large_slice_kernel<3, true>);
-          else go(k1_large_slice_kernel<4, true>);
-        } else {
-          if (ni == 1) go(k1_large_slice_kernel<1, false>);
-          else if (ni == 2) go(k1_large_slice_kernel<2, false>);
-          else if (ni == 3) go(k1_large_slice_kernel<3, false>);
-          else go(k1_large_slice_kernel<4, false>);
-        }
-        return cvf_check_launch("k1_large_slice_kernel");
-      }
-      if (vec4)
-        hipLaunchKernelGGL(k1_large_capture_kernel<true>, dim3((unsigned)groups), dim3(64 * kGroup), ldsc, s, *pp, x, B,
-                           feat_tiled, feat_rows, aux_tiled, slot_xyz, same_xcd);
-      else
-        hipLaunchKernelGGL(k1_large_capture_kernel<false>, dim3((unsigned)groups), dim3(64 * kGroup), ldsc, s, *pp, x, B,
-                           feat_tiled, feat_rows, aux_tiled, slot_xyz, same_xcd);
-      return cvf_check_launch("k1_large_capture_kernel");
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64 * (kStream + kTail)), P.lds, s, *pp, x, B, P.nquads, groups, P.rounds,
+                         feat_tiled, feat_rows, aux_tiled, slot_xyz, probe);
+    };
+    if (P.ni == 1) go(k1_large_pipe_kernel<1>);
+    else if (P.ni == 2) go(k1_large_pipe_kernel<2>);
+    else go(k1_large_pipe_kernel<3>);
+    return cvf_check_launch("k1_large_pipe_kernel");
+  }
+  if (code > CVF_K1_ROUTE_SLICE) {
+    auto go = [&](auto kernel) {
+      if (P.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * kGroup), P.lds, s, *pp, x, B, feat_tiled, feat_rows, aux_tiled,
+                         slot_xyz, same_xcd);
+    };
+    // non-temporal coordinate loads, a developer switch: measured 1592 us against 1065 us (0.48 vs 0.72 of 8 TB/s) for
+    // 100 000 frames of 5000 atoms (tools/bench_k1_c5.py) - the plain loads stay the default (uniform weights only)
+    static const bool nt = getenv("CVF_K1_NT") != nullptr && atoi(getenv("CVF_K1_NT")) != 0;
+    if (weighted) {
+      if (P.ni == 1) go(k1_large_slice_kernel<1, false, true>);
+      else if (P.ni == 2) go(k1_large_slice_kernel<2, false, true>);
+      else if (P.ni == 3) go(k1_large_slice_kernel<3, false, true>);
+      else go(k1_large_slice_kernel<4, false, true>);
+    } else if (nt) {
+      if (P.ni == 1) go(k1_large_slice_kernel<1, true, false>);
+      else if (P.ni == 2) go(k1_large_slice_kernel<2, true, false>);
+      else if (P.ni == 3) go(k1_large_slice_kernel<3, true, false>);
+      else go(k1_large_slice_kernel<4, true, false>);
+    } else {
+      if (P.ni == 1) go(k1_large_slice_kernel<1, false, false>);
+      else if (P.ni == 2) go(k1_large_slice_kernel<2, false, false>);
+      else if (P.ni == 3) go(k1_large_slice_kernel<3, false, false>);
+      else go(k1_large_slice_kernel<4, false, false>);
     }
+    return cvf_check_launch("k1_large_slice_kernel");
   }
-  const size_t lds = feat_tiled ? (size_t)pp->d_r * kGroup * sizeof(float) : 0;
-  CVF_REQUIRE(lds <= 96 * 1024, "cvf_align_feature_fwd: %d features do not fit the staging buffer", pp->d_r);
-  if (lds > 48 * 1024) {
-    (void)hipFuncSetAttribute((const void*)k1_large_gather_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)k1_large_gather_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (code == CVF_K1_ROUTE_CAPTURE_VEC4 || code == CVF_K1_ROUTE_CAPTURE) {
+    auto go = [&](auto kernel) {
+      if (P.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * kGroup), P.lds, s, *pp, x, B, feat_tiled, feat_rows, aux_tiled,
+                         slot_xyz, same_xcd);
+    };
+    if (code == CVF_K1_ROUTE_CAPTURE_VEC4) {
+      if (weighted) go(k1_large_capture_kernel<true, true>);
+      else go(k1_large_capture_kernel<true, false>);
+    } else {
+      if (weighted) go(k1_large_capture_kernel<false, true>);
+      else go(k1_large_capture_kernel<false, false>);
+    }
+    return cvf_check_launch("k1_large_capture_kernel");
   }
-  if (contig)
-    hipLaunchKernelGGL(k1_large_gather_kernel<true>, dim3((unsigned)groups), dim3(64 * kGroup), lds, s, *pp, x, B, feat_tiled, feat_rows,
-                       aux_tiled);
-  else
-    hipLaunchKernelGGL(k1_large_gather_kernel<false>, dim3((unsigned)groups), dim3(64 * kGroup), lds, s, *pp, x, B, feat_tiled, feat_rows,
-                       aux_tiled);
+  auto go = [&](auto kernel) {
+    if (P.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * kGroup), P.lds, s, *pp, x, B, feat_tiled, feat_rows, aux_tiled);
+  };
+  if (code == CVF_K1_ROUTE_GATHER_CONTIG) {
+    if (weighted) go(k1_large_gather_kernel<true, true>);
+    else go(k1_large_gather_kernel<true, false>);
+  } else {
+    if (weighted) go(k1_large_gather_kernel<false, true>);
+    else go(k1_large_gather_kernel<false, false>);
+  }
   return cvf_check_launch("k1_large_gather_kernel");
 }
 

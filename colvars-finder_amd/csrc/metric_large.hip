@@ -10,6 +10,12 @@
 //     E_dense   = sum_c ( Z_c. T2[c] Z_c.^T - 2 shift_c Z_c. T1[c] + shift_c^2 T0[c] )
 //     usum_dense[c] = Z_c. T1[c] - shift_c T0[c]          dH_dense[c][j] = Z_c. T2[c][.][j] - shift_c T1[c][j]
 // so a frame costs O(n_slot + n_rec) work instead of O(N).
+// Per-atom alignment weights (cvf_pp_desc.align_w = w, mean 1; ref = ref_c as stored = w_b (ref_b - weighted centroid)): the centroid is
+// c = sum_b w_b x_b / n_align, hence d_b = Z ref_b - w_b shift and the centroid's tangent dc = sum_b w_b u_b / n_align, and the same closed
+// forms hold with
+//     T0[c] = sum_b a_bc w_b^2      T1[c][j] = sum_b a_bc w_b ref_bj      T2, R1 as above (ref pre-weighted)
+// (E_dense: sum_b a_bc (Z_c. ref_b - w_b shift_c)^2; usum_dense: sum_b w_b a_bc d_bc; dH_dense: sum_b a_bc d_bc ref_bj).  In phase B the
+// slot's weight multiplies shift and enters usp (the w-weighted sum for dc); dHp = sum (a s) (x) ref takes no weight.
 //
 // Work decomposition (round 3; rounds 1-2 ran one wave per frame with the records over the lanes and scattered into per-frame
 // slot accumulators in LDS - 8 waves per CU, dependent read-modify-write chains, 117 us for 2000 frames x 6 nets):
@@ -297,8 +303,8 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
     usd[cc] = zt1 - sh[cc] * T0[cc];
     E += quad - 2.0f * sh[cc] * zt1 + sh[cc] * sh[cc] * T0[cc];
   }
-  // ---- phase B: slots.  s_t = sum of the slot's rows; u_t = a_t .* (s_t + d_t), d_t = al_t (Z ref_t - shift), into its first
-  // row.  Accumulated: Es = sum a s^2, usp = sum al a s, dHp = sum (al a s) (x) ref - the cross term 2 sum a s d of E follows
+  // ---- phase B: slots.  s_t = sum of the slot's rows; u_t = a_t .* (s_t + d_t), d_t = Z ref_t - al_t shift, into its first
+  // row.  Accumulated: Es = sum a s^2, usp = sum al a s, dHp = sum (a s) (x) ref - the cross term 2 sum a s d of E follows
   // from the last two (2 sum_c (Z_c. dHp_c - shift_c usp_c)) after the reduction.  Three slots per iteration, their LDS reads
   // requested together.
   const MatCols Zc = mat_cols(Z);
@@ -342,13 +348,13 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       const bool valid = sl0 + LG * j < ns;
       const float mv = valid ? 1.0f : 0.0f;
       const V3 at = v3(mv * c0[j].x, mv * c0[j].y, mv * c0[j].z), rf = v3(c0[j].w, c1[j].x, c1[j].y);
-      const float al = c1[j].z;   // 1 on the align set, else 0 (then rf = 0 as well)
+      const float al = c1[j].z;   // the atom's alignment weight: 1 (uniform) or w_t on the align set, else 0 (then rf = 0 as well)
       const V3 as = v3(at.x * st[j].x, at.y * st[j].y, at.z * st[j].z);
       Es += as.x * st[j].x + as.y * st[j].y + as.z * st[j].z;
       const V3 asl = al * as;
       usp_xy += f2{asl.x, asl.y};
       usp_z += asl.z;
-      outer_acc(dHo, asl, rf);
+      outer_acc(dHo, as, rf);     // (no weight: ref_c carries it; rf = 0 off the align set)
       f2 dxy = f2{-al * sh[0], -al * sh[1]};
       float dz = -al * sh[2];
       mat_times_acc(Zc, rf, dxy, dz);
@@ -442,12 +448,15 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
   }
 }
 
-// dense[42] = T0[3], T1[3][3], T2[3][3][3], R1[3] in fp64; one block
-__global__ void metric_dense_kernel(cvf_pp_desc pp, const float* __restrict__ a, double* __restrict__ dense) {
-  __shared__ double red[42];
+// dense[42] = T0[3], T1[3][3], T2[3][3][3], R1[3] in fp64; one block.  WEIGHTED (per-atom alignment weights w = align_w, ref_c
+// pre-weighted): T0 = sum a w^2, T1 = sum a w ref, T2 and R1 as they are, the slots' align column = w (header of this file).
+// The waves' sums meet in a FIXED order (they used to meet in an LDS atomicAdd, in the order the waves happened to arrive: the last
+// bits of the moments changed from call to call) - two calls give the same bits, and align_w = NULL the bits of align_w = all ones.
+constexpr int kDenseThreads = 256;
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kDenseThreads) void metric_dense_kernel(cvf_pp_desc pp, const float* __restrict__ a, double* __restrict__ dense) {
+  __shared__ double red[kDenseThreads / 64][42];
   const int tid = threadIdx.x;
-  if (tid < 42) red[tid] = 0.0;
-  __syncthreads();
   double acc[42];
 #pragma unroll
   for (int i = 0; i < 42; ++i) acc[i] = 0.0;
@@ -459,12 +468,15 @@ __global__ void metric_dense_kernel(cvf_pp_desc pp, const float* __restrict__ a,
       r[j] = (double)pp.ref_c[3 * b + j];
       aw[j] = (double)a[3 * atom + j];
     }
+    const double wb = WEIGHTED ? (double)pp.align_w[b] : 1.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      acc[c] += aw[c];
+      if (WEIGHTED) acc[c] += aw[c] * wb * wb;
+      else acc[c] += aw[c];
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        acc[3 + 3 * c + j] += aw[c] * r[j];
+        if (WEIGHTED) acc[3 + 3 * c + j] += aw[c] * wb * r[j];
+        else acc[3 + 3 * c + j] += aw[c] * r[j];
 #pragma unroll
         for (int kk = 0; kk < 3; ++kk) acc[12 + 9 * c + 3 * j + kk] += aw[c] * r[j] * r[kk];
       }
@@ -474,10 +486,15 @@ __global__ void metric_dense_kernel(cvf_pp_desc pp, const float* __restrict__ a,
 #pragma unroll
   for (int i = 0; i < 42; ++i) {
     const double sv = wave_sum(acc[i]);
-    if ((tid & 63) == 0) atomicAdd(&red[i], sv);
+    if ((tid & 63) == 0) red[tid >> 6][i] = sv;
   }
   __syncthreads();
-  if (tid < 42) dense[tid] = red[tid];
+  if (tid < 42) {
+    double t = red[0][tid];
+#pragma unroll
+    for (int w = 1; w < kDenseThreads / 64; ++w) t += red[w][tid];
+    dense[tid] = t;
+  }
   // the derivative kernel's per-slot constants behind the moments: [n_slot][8] floats (see metric_rows_kernel)
   if (pp.slot_row != nullptr) {
     float* sc0 = reinterpret_cast<float*>(dense + 42);
@@ -489,7 +506,7 @@ __global__ void metric_dense_kernel(cvf_pp_desc pp, const float* __restrict__ a,
       float* sc = sc0 + 8 * sl;
       sc[0] = a[3 * atom]; sc[1] = a[3 * atom + 1]; sc[2] = a[3 * atom + 2];
       sc[3] = b >= 0 ? pp.ref_c[3 * bc] : 0.0f; sc[4] = b >= 0 ? pp.ref_c[3 * bc + 1] : 0.0f; sc[5] = b >= 0 ? pp.ref_c[3 * bc + 2] : 0.0f;
-      sc[6] = b >= 0 ? 1.0f : 0.0f;
+      sc[6] = b >= 0 ? (WEIGHTED ? pp.align_w[bc] : 1.0f) : 0.0f;
       sc[7] = __builtin_bit_cast(float, r0 | ((r1 - r0) << 20));
     }
   }
@@ -576,6 +593,7 @@ extern "C" int cvf_metric_dense_tensors(const cvf_pp_desc* pp, const float* a, d
   //  per-slot row counts when it builds the tables - colvarsfinder/pp.py derivative_table_limits)
   CVF_REQUIRE(pp->slot_row == nullptr || (pp->n_slot < 65536 && pp->n_ref < 65536 && pp->n_ref >= pp->n_slot),
               "cvf_metric_dense_tensors: %d slots / %d contribution rows do not fit the tables' 16-bit fields", pp->n_slot, pp->n_ref);
-  hipLaunchKernelGGL(metric_dense_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *pp, a, dense);
+  if (pp->align_w) hipLaunchKernelGGL(metric_dense_kernel<true>, dim3(1), dim3(kDenseThreads), 0, (hipStream_t)stream, *pp, a, dense);
+  else hipLaunchKernelGGL(metric_dense_kernel<false>, dim3(1), dim3(kDenseThreads), 0, (hipStream_t)stream, *pp, a, dense);
   return cvf_check_launch("metric_dense_kernel");
 }

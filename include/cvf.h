@@ -100,8 +100,14 @@ typedef struct cvf_pp_desc {
   int32_t n_rec_slot;        /* entries of rec_slot (0: n_rec, unbatched) */
   /* optional per-atom alignment weights ("weighted Kabsch": the rotation and translation minimise
    * sum_b w_b |(x_b - c) R - ref_b|^2, c = sum_b w_b x_b / sum_b w_b).  NULL = uniform weights.  When set:
-   *   align_w[b] = n_align * w_b / sum w   (mean 1), and ref_c[b] = align_w[b] * (ref_b - weighted centroid of ref),
-   * flags must be 0 and 3 N must fit the lane-per-frame kernels (the layouts built for speed assume uniform weights). */
+   *   align_w[b] = n_align * w_b / sum w   (mean 1), and ref_c[b] = align_w[b] * (ref_b - weighted centroid of ref).
+   *   n_coord <= 192 (the lane-per-frame kernels): flags must be 0 (the layouts built for speed assume uniform weights).
+   *   n_coord  > 192 (the streaming kernels, csrc/k1_large.hip): accepted with any combination of CVF_PP_ALIGN_CONTIG /
+   *     CVF_PP_SLOT_BATCHED - the flags describe the tables, not the weights - by cvf_align_feature_fwd,
+   *     cvf_align_feature_vjp[_rows], cvf_metric_apply[_stats] and cvf_metric_dense_tensors.  The vectorised instances of the
+   *     streaming kernels read four weights per 16-byte load: align_w must then be 16-byte aligned like ref_c and atom_slot,
+   *     otherwise the launch takes a scalar instance (cvf_align_feature_route tells which).
+   * The fused and 16-frame launches (cvf_ef16_*, cvf_ef_[align_]fwd_metric_*) do not take weights; their predicates answer 0. */
   const float* align_w;      /* [n_align] or NULL */
   /* large molecules, derivative kernel (cvf_metric_apply; csrc/metric_large.hip): the scatter J^T g -> feature atoms as a table
    * of rows.  Every (record, atom position) pair owns one row; the rows of one slot are contiguous:
@@ -186,6 +192,23 @@ const char* cvf_last_error(void);
 int64_t cvf_align_feature_scratch_bytes(const cvf_pp_desc* pp, int64_t B); /* 0 for small molecules */
 int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows,
                           float* aux_tiled, void* scratch, void* stream);
+/* Which kernel cvf_align_feature_fwd launches for a CVF_PP_ALIGN descriptor, a batch size and a set of outputs (has_* != 0: that
+ * buffer is passed; has_scratch counts only where cvf_align_feature_scratch_bytes() > 0).  Host arithmetic only, no launch;
+ * cvf_align_feature_fwd decides by the same function, and the developer environment switches it reads (CVF_K1_NOSLICE, CVF_K1_NOPIPE,
+ * CVF_K1_PIPE_MIN_GROUPS) are honoured here too.  `x` and `feat_rows` are taken to be 16-byte aligned (torch allocations are); a
+ * misaligned `x` takes the scalar capture / gather instances instead.  Per-atom weights (align_w) have their own instances of the
+ * gather, capture and slice kernels and never take the pipelined kernel.  Returns one of the codes below, or a negative value (and
+ * cvf_last_error()) for a descriptor cvf_align_feature_fwd refuses. */
+enum {
+  CVF_K1_ROUTE_SMALL = 0,         /* n_coord <= 192: the lane-per-frame kernels (csrc/k1_align.hip) */
+  CVF_K1_ROUTE_GATHER_CONTIG = 1, /* k1_large_gather_kernel<CONTIG = true>: feature atoms re-read after the streaming pass */
+  CVF_K1_ROUTE_GATHER = 2,        /* k1_large_gather_kernel<CONTIG = false> */
+  CVF_K1_ROUTE_CAPTURE_VEC4 = 3,  /* k1_large_capture_kernel<VEC4 = true>: one wave per frame, 16-byte loads */
+  CVF_K1_ROUTE_CAPTURE = 4,       /* k1_large_capture_kernel<VEC4 = false>: 4-byte loads, any align set */
+  CVF_K1_ROUTE_SLICE = 10,        /* + NI = 11..14: k1_large_slice_kernel<NI> (NI = ceil(N / 2048) groups of four atoms per lane) */
+  CVF_K1_ROUTE_PIPE = 20          /* + NI = 21..23: k1_large_pipe_kernel<NI> (uniform weights only) */
+};
+int cvf_align_feature_route(const cvf_pp_desc* pp, int64_t B, int has_tiled, int has_rows, int has_aux, int has_scratch);
 
 /* --- VJP of K1: dL/dx of the alignment + feature map, gx_rows[b] = J(x_b)^T g_rows[b] (csrc/k1_vjp.hip).  What autograd
  * computes through pp_layer when the reference differentiates a loss or a CV with respect to the coordinates (core.py:418-426).
@@ -226,7 +249,12 @@ int cvf_metric_apply_stats(const cvf_pp_desc* pp, const float* x, int64_t B, con
 /* large molecules only (slot_xyz / dense may be NULL otherwise): dense[cvf_metric_dense_doubles(pp)], prepared once per (pp, a):
  * dense[0..41] = moments of (a, ref) over the align atoms, T0[c] = sum a_bc, T1[c][j] = sum a_bc ref_bj,
  * T2[c][j][k] = sum a_bc ref_bj ref_bk, R1[j] = sum ref_bj (fp64); behind them n_slot x 8 floats of per-slot constants
- * (a, ref, align flag, rows of the slot) for the derivative kernel. */
+ * (a, ref, align flag, rows of the slot) for the derivative kernel.
+ * With per-atom weights (w = align_w, 1 when NULL; ref = ref_c as stored, i.e. pre-weighted) the moments are
+ *   T0[c] = sum a_bc w_b^2,  T1[c][j] = sum a_bc w_b ref_bj,  T2[c][j][k] = sum a_bc ref_bj ref_bk,  R1[j] = sum ref_bj
+ * and column 6 of the per-slot constants holds w_b (0 off the align set) instead of 1 / 0: with d_b = Z ref_b - w_b shift and the
+ * centroid's tangent dc = sum_b w_b u_b / n_align the closed forms of csrc/metric_large.hip keep their shape.  align_w = NULL gives the
+ * bits of align_w = all ones. */
 int64_t cvf_metric_dense_doubles(const cvf_pp_desc* pp);
 int cvf_metric_dense_tensors(const cvf_pp_desc* pp, const float* a, double* dense, void* stream);
 /* The CV metric tensor per frame from cvf_metric_apply's input and output: m_rows[b][i][j] = g_i . q_j = (J A J^T)_ij in CV
