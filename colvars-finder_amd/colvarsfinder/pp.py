@@ -85,10 +85,20 @@ class AlignFeatureLayer(torch.nn.Module):
             the weights at any size.  The table flags (contiguous align set, batched slot records) are kept - they describe
             the tables, not the weights.  With at most 64 atoms the option changes nothing; without it such a layer is
             refused as before.
+        second_order: ``None`` (default) or ``"cotangent"``; also a settable attribute (``layer.second_order = "cotangent"``,
+            the way to set it on a :class:`PreprocessingANN`).  ``None``: the layer is differentiable to first order and its
+            backward raises under ``create_graph=True``.  ``"cotangent"``: the backward ``gx = J(x)^T g`` is itself recorded,
+            as a function of its cotangent ``g`` - enough for every loss of the coordinate gradient
+            ``L(grad_x f_theta(r(x)))`` that is differentiated in the net's parameters, because the layer has none and
+            ``g -> J(x)^T g`` is linear (its derivative is the HIP Jacobian-vector product ``cvf_align_feature_jvp``).  The
+            other half of the second derivative, the curvature term ``d/dx (v^T J(x)^T g)``, is NOT built: a backward that
+            reaches ``x`` through this path fills ``x.grad`` with NaN instead of a number that would be silently wrong.
     """
 
-    def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None, weights_any_size=False):
+    def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None, weights_any_size=False,
+                 second_order=None):
         super().__init__()
+        self.second_order = second_order
         self.aligned = align_idx is not None
         if not self.aligned:
             assert ref_pos is None, "ref_pos without align_idx: a layer without alignment has no reference structure"
@@ -197,6 +207,16 @@ class AlignFeatureLayer(torch.nn.Module):
         self.register_buffer("ref_c", torch.tensor(ref_c, dtype=torch.float32))
         self.register_buffer("rec", torch.tensor(rec, dtype=torch.int32).reshape(-1, 6))
 
+    @property
+    def second_order(self):
+        return self.__dict__.get("_second_order")   # (a layer pickled before the option existed: None)
+
+    @second_order.setter
+    def second_order(self, value):
+        if value not in _SECOND_ORDER:
+            raise ValueError(f"second_order must be one of {_SECOND_ORDER}, got {value!r}")
+        self._second_order = value
+
     def derivative_table_limits(self):
         """None, or why the large-molecule derivative kernel (csrc/metric_large.hip: metric_rows_kernel) cannot take this feature
         list: its tables pack a record's slots and rows into 16-bit fields, a record's position among its atom's rows into 8 bits
@@ -241,15 +261,22 @@ class AlignFeatureLayer(torch.nn.Module):
 
         Differentiable in ``x`` to first order, like molann's layer: when ``x`` requires grad (and grad mode is on) the call
         records a graph whose backward runs the HIP vector-Jacobian product ``cvf_align_feature_vjp`` and returns ``dL/dx`` in
-        ``x``'s type and on ``x``'s device.  Second derivatives are not built (the backward raises under ``create_graph=True``):
-        ``colvar_model()`` with a grad-requiring input and ``export.ScriptableAlignFeature`` have them.  The training tasks
-        use the analytic derivative kernels and call this layer without a graph."""
+        ``x``'s type and on ``x``'s device.  Forward mode works the same way: under ``torch.autograd.forward_ad`` a dual input
+        gives a dual output whose tangent ``J(x) v`` is the HIP Jacobian-vector product ``cvf_align_feature_jvp``, in the
+        input's type and on its device.
+
+        Full second derivatives are not built.  By default (``second_order=None``) the backward raises under
+        ``create_graph=True``; ``colvar_model()`` with a grad-requiring input and ``export.ScriptableAlignFeature`` have them.
+        With ``second_order="cotangent"`` the backward is recorded as a function of its cotangent, which is all that a loss of
+        ``grad_x f_theta(layer(x))`` needs for its gradient in ``theta``; ``x.grad`` after such a backward is NaN (the curvature
+        term of the layer is missing, and NaN rather than a wrong number says so).  The training tasks use the analytic
+        derivative kernels and call this layer without a graph."""
         x = torch.as_tensor(x)
         dev = _hip.require_gpu(self.rec.device)   # raises when the layer was never moved to a GPU: there is no CPU path
         assert x.dim() == 3 and x.shape[1] == self.n_atoms and x.shape[2] == 3, \
             f"expected [B,{self.n_atoms},3], got {tuple(x.shape)}"
         src_dev, src_dt = x.device, (x.dtype if x.dtype.is_floating_point else torch.float32)
-        if x.requires_grad and torch.is_grad_enabled():
+        if (x.requires_grad and torch.is_grad_enabled()) or _has_tangent(x):
             # the conversions stay on the graph: a CPU fp64 input receives a CPU fp64 gradient
             xd = x.to(device=dev, dtype=torch.float32).contiguous()
             out = _AlignFeatureFn.apply(xd, self)
@@ -269,12 +296,56 @@ class AlignFeatureLayer(torch.nn.Module):
 _NO_DOUBLE_BACKWARD = ("AlignFeatureLayer: second derivatives through the HIP alignment + feature layer are not built (its "
                        "backward ran with create_graph=True); differentiate twice through colvar_model() called with a "
                        "grad-requiring input, or through export.ScriptableAlignFeature(layer), which are written with torch "
-                       "operators")
+                       "operators. A loss of the coordinate gradient that is differentiated in the net's parameters only "
+                       "runs on the HIP layer with layer.second_order = 'cotangent' (x.grad is then NaN)")
+_SECOND_ORDER = (None, "cotangent")
+
+
+def _primal(t):
+    """``t`` without its forward-mode tangent (the reverse-mode graph stays)."""
+    return torch.autograd.forward_ad.unpack_dual(t).primal
+
+
+def _has_tangent(t):
+    return torch.autograd.forward_ad.unpack_dual(t).tangent is not None
+
+
+def _poison(x):
+    """The gradient the cotangent-path Functions return for ``x``: NaN in ``x``'s shape, one scalar expanded.  The curvature
+    term d/dx (v^T J(x)^T g) is not built, and a silent zero there would be a wrong number."""
+    return torch.full((), float("nan"), device=x.device, dtype=x.dtype).expand(x.shape)
+
+
+def _vjp_call(layer, x, aux, g):
+    """``cvf_align_feature_vjp``: ``gx = J(x)^T g`` on the forward's aux rows, in ``x``'s shape."""
+    B = x.shape[0]
+    gx = torch.empty_like(x)
+    if B > 0:
+        g = g.to(device=x.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(x.device):
+            _hip.check(_hip.lib().cvf_align_feature_vjp(layer.pp_desc(), _hip.ptr(x), B, _hip.ptr(aux), _hip.ptr(g),
+                                                        _hip.ptr(gx), _hip.stream()), "cvf_align_feature_vjp")
+    return gx
+
+
+def _jvp_call(layer, x, aux, v):
+    """``cvf_align_feature_jvp``: ``q = J(x) v`` on the forward's aux rows, ``[B, d_r]``."""
+    B = x.shape[0]
+    q = torch.empty(B, layer.d_r, device=x.device, dtype=torch.float32)
+    if B > 0:
+        v = v.to(device=x.device, dtype=torch.float32).reshape(x.shape).contiguous()
+        with torch.cuda.device(x.device):
+            _hip.check(_hip.lib().cvf_align_feature_jvp(layer.pp_desc(), _hip.ptr(x), B, _hip.ptr(aux), _hip.ptr(v),
+                                                        _hip.ptr(q), _hip.stream()), "cvf_align_feature_jvp")
+    return q
 
 
 class _AlignFeatureFn(torch.autograd.Function):
     """``r(x)`` with its first derivative: forward = ``cvf_align_feature_fwd`` (features as rows, plus the per-frame aux rows
-    R / centroid / Kinv), backward = ``cvf_align_feature_vjp`` on those aux rows.  ``x``: fp32, contiguous, on the layer's GPU."""
+    R / centroid / Kinv), backward = ``cvf_align_feature_vjp`` on those aux rows, jvp (forward-mode AD) =
+    ``cvf_align_feature_jvp`` on them.  ``x``: fp32, contiguous, on the layer's GPU.
+
+    With ``layer.second_order == "cotangent"`` the backward is itself a graph node (:class:`_AlignVjpFn`)."""
 
     @staticmethod
     def forward(ctx, x, layer):
@@ -288,22 +359,58 @@ class _AlignFeatureFn(torch.autograd.Function):
                 _hip.check(_hip.lib().cvf_align_feature_fwd(desc, _hip.ptr(x), B, None, _hip.ptr(out), _hip.ptr(aux),
                                                             _hip.ptr(scratch), _hip.stream()), "cvf_align_feature_fwd")
         ctx.save_for_backward(x, aux)
+        ctx.save_for_forward(x, aux)
         ctx.layer = layer
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
+        x, aux = ctx.saved_tensors
+        if ctx.layer.second_order == "cotangent":
+            return _AlignVjpFn.apply(grad_out, x, aux, ctx.layer), None
         if torch.is_grad_enabled():
             raise RuntimeError(_NO_DOUBLE_BACKWARD)
+        return _vjp_call(ctx.layer, x, aux, grad_out), None
+
+    @staticmethod
+    def jvp(ctx, x_t, _):
         x, aux = ctx.saved_tensors
-        layer, B = ctx.layer, x.shape[0]
-        gx = torch.empty_like(x)
-        if B > 0:
-            g = grad_out.to(device=x.device, dtype=torch.float32).contiguous()
-            with torch.cuda.device(x.device):
-                _hip.check(_hip.lib().cvf_align_feature_vjp(layer.pp_desc(), _hip.ptr(x), B, _hip.ptr(aux), _hip.ptr(g),
-                                                            _hip.ptr(gx), _hip.stream()), "cvf_align_feature_vjp")
-        return gx, None
+        return _AlignJvpFn.apply(x_t, _primal(x), aux, ctx.layer)
+
+
+class _AlignVjpFn(torch.autograd.Function):
+    """``(g, x, aux) -> gx = J(x)^T g`` as a graph node (``second_order="cotangent"``).  Linear in ``g``: its backward returns
+    ``J(x) v`` for ``g`` (:class:`_AlignJvpFn`, whose backward is this Function again - the pair is closed under any order of
+    differentiation in ``g`` / ``v``) and NaN for ``x``: the curvature term is not built."""
+
+    @staticmethod
+    def forward(ctx, g, x, aux, layer):
+        ctx.save_for_backward(x, aux)
+        ctx.layer = layer
+        return _vjp_call(layer, x, aux, g)
+
+    @staticmethod
+    def backward(ctx, v):
+        x, aux = ctx.saved_tensors
+        q = _AlignJvpFn.apply(v, x, aux, ctx.layer) if ctx.needs_input_grad[0] else None
+        return q, (_poison(x) if ctx.needs_input_grad[1] else None), None, None
+
+
+class _AlignJvpFn(torch.autograd.Function):
+    """``(v, x, aux) -> q = J(x) v`` as a graph node: the tangent of forward-mode AD through the layer and the derivative of
+    :class:`_AlignVjpFn` in its cotangent.  Its backward returns ``J(x)^T g`` for ``v`` and NaN for ``x``."""
+
+    @staticmethod
+    def forward(ctx, v, x, aux, layer):
+        ctx.save_for_backward(x, aux)
+        ctx.layer = layer
+        return _jvp_call(layer, x, aux, v)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, aux = ctx.saved_tensors
+        gx = _AlignVjpFn.apply(g, x, aux, ctx.layer) if ctx.needs_input_grad[0] else None
+        return gx, (_poison(x) if ctx.needs_input_grad[1] else None), None, None
 
 
 class FeatureLayer:

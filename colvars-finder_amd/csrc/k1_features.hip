@@ -1,5 +1,5 @@
 // CVF_PP_FEATURES (include/cvf.h): features of the RAW coordinates - no alignment, no centroid, no rotation.  Forward, J^T g
-// (one row and k rows) and the generator's metric q = J A J^T g, E = g^T J A J^T g, for frames of ANY atom count: what bounds a
+// (one row and k rows), J u (one tangent) and the generator's metric q = J A J^T g, E = g^T J A J^T g, for frames of ANY atom count: what bounds a
 // launch is the feature list (n_slot distinct feature atoms, n_ref (record, atom) pairs), never 3 N.
 //
 // One decomposition for the three kernels.  A workgroup of 256 threads owns G consecutive frames of one 64-frame tile (G a power
@@ -256,6 +256,38 @@ __global__ __launch_bounds__(kFeatThreads) void features_metric_kernel(cvf_pp_de
   }
 }
 
+// ------------------------------------------------------------------------------------
+// JVP: q_rows[b] = J(x_b) u_rows[b] (cvf_align_feature_jvp), the transpose of features_vjp_kernel: the feature atoms of x AND of
+// u are staged through slot_atom (no other atom of either is read), then one (record, frame) per item - a position record copies
+// its atom's tangent, the others go through invariant_jvp on the geometry features_vjp_kernel evaluates.  Every output of every
+// record is written once, straight to its row (as features_fwd_kernel writes feat_rows); no sums across items, no atomics.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kFeatThreads) void features_jvp_kernel(cvf_pp_desc pp, const float* __restrict__ x, int64_t B, int lg,
+                                                                     const float* __restrict__ u_rows, float* __restrict__ q_rows) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  const Group g = group_of(lg);
+  if (g.f0 >= B) return;
+  float* us = xs + 3 * (pp.n_slot << lg);
+  stage_slots(pp, x, B, g, xs);
+  stage_slots(pp, u_rows, B, g, us);
+  __syncthreads();
+  for (int e = threadIdx.x; e < (pp.n_mrec << lg); e += kFeatThreads) {
+    const int r = e >> lg, f = e & (g.G - 1);
+    if (g.f0 + f >= B) continue;   // only rows < B are written
+    const MRec m = load_mrec(pp.mrec, r);
+    float* q = q_rows + (g.f0 + f) * pp.d_r + m.out;
+    if (m.type == CVF_FEAT_POSITION) {
+      const V3 u = img_get(us, m.s[0], f, g.G);
+      q[0] = u.x;
+      q[1] = u.y;
+      q[2] = u.z;
+    } else if (m.type >= 0) {
+      invariant_jvp<true>(m.type, pp.use_angle_value != 0, [&](int kk) { return img_get(xs, m.s[kk], f, g.G); },
+                          [&](int kk) { return img_get(us, m.s[kk], f, g.G); }, [&](int j, float v) { q[j] = v; });
+    }
+  }
+}
+
 struct FeatPlan {
   int lg;
   size_t lds;
@@ -304,6 +336,13 @@ int cvf_features_vjp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, in
   CVF_REQUIRE(x, "cvf_align_feature_vjp: CVF_PP_FEATURES needs x");
   const FeatPlan p = feat_plan(((size_t)pp->n_slot + pp->n_ref) * 12);
   return features_launch(features_vjp_kernel, "features_vjp_kernel", B, p, s, *pp, x, B, p.lg, k, g_rows, gx_rows);
+}
+
+int cvf_features_jvp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* u_rows, float* q_rows, hipStream_t s) {
+  if (int rc = features_check(pp, "cvf_align_feature_jvp", true)) return rc;
+  CVF_REQUIRE(x, "cvf_align_feature_jvp: CVF_PP_FEATURES needs x");
+  const FeatPlan p = feat_plan((size_t)pp->n_slot * 24);   // the feature atoms of x and of u
+  return features_launch(features_jvp_kernel, "features_jvp_kernel", B, p, s, *pp, x, B, p.lg, u_rows, q_rows);
 }
 
 int cvf_features_metric_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, int k, const float* g_tiled,

@@ -229,6 +229,20 @@ int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int64_t B, cons
 int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, int k,
                                const float* g_rows, float* gx_rows, void* stream);
 
+/* --- JVP of K1 (csrc/k1_jvp.hip; CVF_PP_FEATURES: csrc/k1_features.hip).
+ * q_rows[b] = J(x_b) u_rows[b]: the directional derivative of r(x) (cvf_align_feature_fwd) along u.
+ * u_rows [B][n_coord], q_rows [B][d_r], aux_tiled as written by cvf_align_feature_fwd for the same x
+ * (NULL for CVF_PP_IDENTITY / CVF_PP_FEATURES).  The transpose of cvf_align_feature_vjp: same descriptors (frames of more than
+ * 192 coordinates need slot_atom and mrec), same CVF_FEATURES_MAX_SLOT / CVF_FEATURES_MAX_REF limits, CVF_PP_IDENTITY a copy,
+ * CVF_PP_FACTORED refused.  Of x and u only the align atoms and the atoms some feature reads are loaded into the arithmetic:
+ * whatever u holds elsewhere (NaN included) does not reach q.  With ubar = sum_b w_b u_b / n_align, dH = sum_b (u_b - ubar) (x) ref_b
+ * and dR = R [Kinv ax(R^T dH)]x, a position record gives (u_a - ubar) R + (x_a - c) dR and a bond / angle / dihedral record the
+ * sum of its gradient vectors times its atoms' tangents.  What forward-mode differentiation through the layer computes, and the
+ * derivative of cvf_align_feature_vjp in its cotangent (the map g -> J^T g is linear).
+ * No allocation, no host synchronisation, no atomics: two calls give the same bits.  B == 0 returns 0; only rows < B are written. */
+int cvf_align_feature_jvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
+                          const float* u_rows, float* q_rows, void* stream);
+
 /* --- K2+K3: per frame and net, q = J A J^T g and E = g^T J A J^T g with J the Jacobian
  * of r at the frame and A = diag(a).  Replaces the k autograd.grad calls through
  * pp_layer at core.py:424 and the a-weighted square sums at core.py:426,438; the
