@@ -3,6 +3,13 @@ csrc/ef_general.hip (cvf_ef_general_fwd / cvf_ef_general_backward) - against the
 tests/test_ef_sweep_gpu.py::test_step_vs_fp64_oracle.  Every oracle case also asserts the launches the step took: the general
 forward and backward are there, the instance kernels (cvf_ef_mlp_fwd, cvf_ef_backward) are not.
 
+This module goes through the task, at the task's shapes: hidden widths 16 to 256 (none at an edge of the kernels' 64-row block or
+32-deep K stage), 30, 45 or 384 input features, batches of 600 frames and more (one of 5), and it compares the loss, the
+eigenvalues and the reduced gradient.  The kernels' block edges - widths and d0 at 1/31/32/33/63/64/65, the bias column of the
+weight gradient across a 64-column block, more tiles than slab rows against the oracle, a slab row that sums base and lagged
+tiles, y_tiled and g_tiled themselves - belong to tests/test_ef_general_edges_gpu.py (table: tests/ef_general_cases.py), which
+drives the C entries directly.
+
 Bars (relative errors; the gradient's as a share of its largest entry) are about THREE TIMES the worst achieved error of the
 group, within the project's ceilings of 1e-4 (loss, eigenvalues) and 3e-4 (gradient):
 
