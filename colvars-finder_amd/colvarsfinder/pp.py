@@ -85,14 +85,20 @@ class AlignFeatureLayer(torch.nn.Module):
             the weights at any size.  The table flags (contiguous align set, batched slot records) are kept - they describe
             the tables, not the weights.  With at most 64 atoms the option changes nothing; without it such a layer is
             refused as before.
-        second_order: ``None`` (default) or ``"cotangent"``; also a settable attribute (``layer.second_order = "cotangent"``,
-            the way to set it on a :class:`PreprocessingANN`).  ``None``: the layer is differentiable to first order and its
-            backward raises under ``create_graph=True``.  ``"cotangent"``: the backward ``gx = J(x)^T g`` is itself recorded,
-            as a function of its cotangent ``g`` - enough for every loss of the coordinate gradient
-            ``L(grad_x f_theta(r(x)))`` that is differentiated in the net's parameters, because the layer has none and
+        second_order: ``None`` (default), ``"cotangent"`` or ``"complete"``; also a settable attribute
+            (``layer.second_order = "complete"``, the way to set it on a :class:`PreprocessingANN`).  ``None``: the layer is
+            differentiable to first order and its backward raises under ``create_graph=True``.  ``"cotangent"``: the backward
+            ``gx = J(x)^T g`` is itself recorded, as a function of its cotangent ``g`` - enough for every loss of the coordinate
+            gradient ``L(grad_x f_theta(r(x)))`` that is differentiated in the net's parameters, because the layer has none and
             ``g -> J(x)^T g`` is linear (its derivative is the HIP Jacobian-vector product ``cvf_align_feature_jvp``).  The
-            other half of the second derivative, the curvature term ``d/dx (v^T J(x)^T g)``, is NOT built: a backward that
+            other half of the second derivative, the curvature term ``d/dx (v^T J(x)^T g)``, is left out: a backward that
             reaches ``x`` through this path fills ``x.grad`` with NaN instead of a number that would be silently wrong.
+            ``"complete"``: the curvature term is there as well, from the HIP Hessian-vector product
+            ``cvf_align_feature_hvp`` - a double backward gives exact gradients in the coordinates too (a trainable module in
+            front of the layer under a gradient loss, ``grad_x |grad_x xi|^2``, a Hessian of ``xi`` row by row), and
+            ``torch.autograd.forward_ad`` over the backward works.  The gradients that reach the layer through the cotangent
+            are those of ``"cotangent"``, bit for bit.  Third derivatives are not built: differentiating the curvature term
+            once more raises.
     """
 
     def __init__(self, n_atoms, align_idx, ref_pos, features, use_angle_value=False, align_weights=None, weights_any_size=False,
@@ -265,12 +271,13 @@ class AlignFeatureLayer(torch.nn.Module):
         gives a dual output whose tangent ``J(x) v`` is the HIP Jacobian-vector product ``cvf_align_feature_jvp``, in the
         input's type and on its device.
 
-        Full second derivatives are not built.  By default (``second_order=None``) the backward raises under
-        ``create_graph=True``; ``colvar_model()`` with a grad-requiring input and ``export.ScriptableAlignFeature`` have them.
+        Second derivatives are opt-in.  By default (``second_order=None``) the backward raises under ``create_graph=True``;
+        ``colvar_model()`` with a grad-requiring input and ``export.ScriptableAlignFeature`` have them in torch operators.
         With ``second_order="cotangent"`` the backward is recorded as a function of its cotangent, which is all that a loss of
         ``grad_x f_theta(layer(x))`` needs for its gradient in ``theta``; ``x.grad`` after such a backward is NaN (the curvature
-        term of the layer is missing, and NaN rather than a wrong number says so).  The training tasks use the analytic
-        derivative kernels and call this layer without a graph."""
+        term of the layer is left out, and NaN rather than a wrong number says so).  With ``second_order="complete"`` the
+        curvature term comes from the HIP Hessian-vector product ``cvf_align_feature_hvp`` and ``x.grad`` is exact; third
+        derivatives raise.  The training tasks use the analytic derivative kernels and call this layer without a graph."""
         x = torch.as_tensor(x)
         dev = _hip.require_gpu(self.rec.device)   # raises when the layer was never moved to a GPU: there is no CPU path
         assert x.dim() == 3 and x.shape[1] == self.n_atoms and x.shape[2] == 3, \
@@ -297,8 +304,13 @@ _NO_DOUBLE_BACKWARD = ("AlignFeatureLayer: second derivatives through the HIP al
                        "backward ran with create_graph=True); differentiate twice through colvar_model() called with a "
                        "grad-requiring input, or through export.ScriptableAlignFeature(layer), which are written with torch "
                        "operators. A loss of the coordinate gradient that is differentiated in the net's parameters only "
-                       "runs on the HIP layer with layer.second_order = 'cotangent' (x.grad is then NaN)")
-_SECOND_ORDER = (None, "cotangent")
+                       "runs on the HIP layer with layer.second_order = 'cotangent' (x.grad is then NaN); "
+                       "layer.second_order = 'complete' adds the curvature term (cvf_align_feature_hvp), so that the "
+                       "coordinates receive their exact second-order gradient as well")
+_NO_THIRD_ORDER = ("AlignFeatureLayer: third derivatives through the HIP alignment + feature layer are not built (the "
+                   "Hessian-vector product cvf_align_feature_hvp of second_order='complete' was differentiated once more); "
+                   "export.ScriptableAlignFeature(layer), written with torch operators, differentiates to any order")
+_SECOND_ORDER = (None, "cotangent", "complete")
 
 
 def _primal(t):
@@ -340,12 +352,32 @@ def _jvp_call(layer, x, aux, v):
     return q
 
 
+def _hvp_call(layer, x, aux, g, v):
+    """``cvf_align_feature_hvp``: ``h = d/dx <g, J(x) v>`` on the forward's aux rows, in ``x``'s shape."""
+    B = x.shape[0]
+    h = torch.empty_like(x)
+    if B > 0:
+        g = g.to(device=x.device, dtype=torch.float32).contiguous()
+        v = v.to(device=x.device, dtype=torch.float32).reshape(x.shape).contiguous()
+        with torch.cuda.device(x.device):
+            _hip.check(_hip.lib().cvf_align_feature_hvp(layer.pp_desc(), _hip.ptr(x), B, _hip.ptr(aux), _hip.ptr(g), _hip.ptr(v),
+                                                        _hip.ptr(h), _hip.stream()), "cvf_align_feature_hvp")
+    return h
+
+
+def _curvature(layer, g, v, x, aux):
+    """What the cotangent-path Functions return for ``x``: ``d/dx <g, J(x) v>`` under ``second_order="complete"``, else NaN."""
+    if layer.second_order == "complete":
+        return _AlignHvpFn.apply(g, v, x, aux, layer)
+    return _poison(x)
+
+
 class _AlignFeatureFn(torch.autograd.Function):
     """``r(x)`` with its first derivative: forward = ``cvf_align_feature_fwd`` (features as rows, plus the per-frame aux rows
     R / centroid / Kinv), backward = ``cvf_align_feature_vjp`` on those aux rows, jvp (forward-mode AD) =
     ``cvf_align_feature_jvp`` on them.  ``x``: fp32, contiguous, on the layer's GPU.
 
-    With ``layer.second_order == "cotangent"`` the backward is itself a graph node (:class:`_AlignVjpFn`)."""
+    With ``layer.second_order`` set (``"cotangent"`` / ``"complete"``) the backward is itself a graph node (:class:`_AlignVjpFn`)."""
 
     @staticmethod
     def forward(ctx, x, layer):
@@ -366,7 +398,7 @@ class _AlignFeatureFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         x, aux = ctx.saved_tensors
-        if ctx.layer.second_order == "cotangent":
+        if ctx.layer.second_order is not None:
             return _AlignVjpFn.apply(grad_out, x, aux, ctx.layer), None
         if torch.is_grad_enabled():
             raise RuntimeError(_NO_DOUBLE_BACKWARD)
@@ -379,38 +411,66 @@ class _AlignFeatureFn(torch.autograd.Function):
 
 
 class _AlignVjpFn(torch.autograd.Function):
-    """``(g, x, aux) -> gx = J(x)^T g`` as a graph node (``second_order="cotangent"``).  Linear in ``g``: its backward returns
-    ``J(x) v`` for ``g`` (:class:`_AlignJvpFn`, whose backward is this Function again - the pair is closed under any order of
-    differentiation in ``g`` / ``v``) and NaN for ``x``: the curvature term is not built."""
+    """``(g, x, aux) -> gx = J(x)^T g`` as a graph node (``second_order="cotangent"`` / ``"complete"``).  Linear in ``g``: its
+    backward returns ``J(x) v`` for ``g`` (:class:`_AlignJvpFn`, whose backward is this Function again - the pair is closed under
+    any order of differentiation in ``g`` / ``v``).  For ``x`` it returns the curvature term ``d/dx <g, J(x) v>``
+    (:class:`_AlignHvpFn`) under ``"complete"`` and NaN under ``"cotangent"``, where that term is left out.  Its jvp (forward
+    mode over the backward) is ``J(x)^T g_t + d/dx <g, J(x) x_t>``."""
 
     @staticmethod
     def forward(ctx, g, x, aux, layer):
-        ctx.save_for_backward(x, aux)
+        ctx.save_for_backward(x, aux, g)
+        ctx.save_for_forward(x, aux, g)
         ctx.layer = layer
         return _vjp_call(layer, x, aux, g)
 
     @staticmethod
     def backward(ctx, v):
-        x, aux = ctx.saved_tensors
+        x, aux, g = ctx.saved_tensors
         q = _AlignJvpFn.apply(v, x, aux, ctx.layer) if ctx.needs_input_grad[0] else None
-        return q, (_poison(x) if ctx.needs_input_grad[1] else None), None, None
+        return q, (_curvature(ctx.layer, g, v, x, aux) if ctx.needs_input_grad[1] else None), None, None
+
+    @staticmethod
+    def jvp(ctx, g_t, x_t, _aux_t, _):
+        x, aux, g = (_primal(t) for t in ctx.saved_tensors)
+        out = _AlignVjpFn.apply(g_t, x, aux, ctx.layer) if g_t is not None else None
+        if x_t is not None:
+            if ctx.layer.second_order != "complete":
+                raise RuntimeError(_NO_DOUBLE_BACKWARD)
+            h = _AlignHvpFn.apply(g, x_t, x, aux, ctx.layer)
+            out = h if out is None else out + h
+        return out
 
 
 class _AlignJvpFn(torch.autograd.Function):
     """``(v, x, aux) -> q = J(x) v`` as a graph node: the tangent of forward-mode AD through the layer and the derivative of
-    :class:`_AlignVjpFn` in its cotangent.  Its backward returns ``J(x)^T g`` for ``v`` and NaN for ``x``."""
+    :class:`_AlignVjpFn` in its cotangent.  Its backward returns ``J(x)^T g`` for ``v``; for ``x`` the curvature term
+    ``d/dx <g, J(x) v>`` under ``second_order="complete"``, else NaN."""
 
     @staticmethod
     def forward(ctx, v, x, aux, layer):
-        ctx.save_for_backward(x, aux)
+        ctx.save_for_backward(x, aux, v)
         ctx.layer = layer
         return _jvp_call(layer, x, aux, v)
 
     @staticmethod
     def backward(ctx, g):
-        x, aux = ctx.saved_tensors
+        x, aux, v = ctx.saved_tensors
         gx = _AlignVjpFn.apply(g, x, aux, ctx.layer) if ctx.needs_input_grad[0] else None
-        return gx, (_poison(x) if ctx.needs_input_grad[1] else None), None, None
+        return gx, (_curvature(ctx.layer, g, v, x, aux) if ctx.needs_input_grad[1] else None), None, None
+
+
+class _AlignHvpFn(torch.autograd.Function):
+    """``(g, v, x, aux) -> h = d/dx <g, J(x) v>`` (``cvf_align_feature_hvp``): the curvature term of the layer's second
+    derivative under ``second_order="complete"``.  Third derivatives are not built: its backward raises."""
+
+    @staticmethod
+    def forward(ctx, g, v, x, aux, layer):
+        return _hvp_call(layer, x, aux, g, v)
+
+    @staticmethod
+    def backward(ctx, _):
+        raise RuntimeError(_NO_THIRD_ORDER)
 
 
 class FeatureLayer:

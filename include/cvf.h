@@ -243,6 +243,21 @@ int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x, int64_t B,
 int cvf_align_feature_jvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
                           const float* u_rows, float* q_rows, void* stream);
 
+/* --- Hessian-vector product of K1 (csrc/k1_hvp.hip).
+ * h_rows[b] = d/dx <g_rows[b], J(x_b) u_rows[b]> = (sum_i g_i Hess r_i(x_b)) u_rows[b]: the derivative along u of
+ * cvf_align_feature_vjp's result, symmetric in u - the curvature term of a double backward through the layer.
+ * g_rows [B][d_r], u_rows [B][n_coord], h_rows [B][n_coord], fully written; aux_tiled as written by cvf_align_feature_fwd for the
+ * same x (NULL for CVF_PP_IDENTITY / CVF_PP_FEATURES).  Same descriptors as cvf_align_feature_vjp (frames of more than 192
+ * coordinates need the slot and contribution-row tables, n_ref * 12 bytes within the LDS), same CVF_FEATURES_MAX_SLOT /
+ * CVF_FEATURES_MAX_REF limits; CVF_PP_IDENTITY writes zeros (its Hessian is 0), CVF_PP_FACTORED is refused.  Position records
+ * contribute the derivative along u of R g_a and of Z ref_b - w_b shift (the rotation's and the centroid's second derivative, on
+ * the aux rows and the covariance sum_b (x_b - c) (x) ref_b recomputed over the align atoms); bond / angle / dihedral records the
+ * derivative along u of their gradient vectors times their adjoint.  Of x and u only the align atoms and the atoms some feature
+ * reads are loaded into the arithmetic: whatever u holds elsewhere (NaN included) does not reach h, and h is exactly 0 there.
+ * No allocation, no host synchronisation, no atomics: two calls give the same bits.  B == 0 returns 0 and writes nothing. */
+int cvf_align_feature_hvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
+                          const float* g_rows, const float* u_rows, float* h_rows, void* stream);
+
 /* --- K2+K3: per frame and net, q = J A J^T g and E = g^T J A J^T g with J the Jacobian
  * of r at the frame and A = diag(a).  Replaces the k autograd.grad calls through
  * pp_layer at core.py:424 and the a-weighted square sums at core.py:426,438; the
