@@ -218,6 +218,20 @@ _SIGNATURES["cvf_regae_general_scratch_floats"] = _SIGNATURES["cvf_regae_scratch
 _SIGNATURES["cvf_regae_general_forward"] = _SIGNATURES["cvf_regae_forward"]
 _SIGNATURES["cvf_regae_general_backward"] = _SIGNATURES["cvf_regae_backward"]
 _SIGNATURES["cvf_regae_general_backward_reuse"] = _SIGNATURES["cvf_regae_backward"]
+# ... and its twin for decoder / regulariser nets of different depths adds (n_dec_layers, n_reg_layers) behind n_enc_layers
+
+
+def _with_depths(sig):
+    res, args = sig
+    at = max(i for i, a in enumerate(args) if a is C.c_int) + 1       # n_enc_layers is the last int of these lists
+    return res, args[:at] + [C.c_int, C.c_int] + args[at:]
+
+
+_SIGNATURES["cvf_regae_ragged_supported"] = _with_depths(_SIGNATURES["cvf_regae_general_supported"])
+_SIGNATURES["cvf_regae_ragged_scratch_floats"] = (C.c_int64, [C.POINTER(MLPDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int])
+_SIGNATURES["cvf_regae_ragged_forward"] = _with_depths(_SIGNATURES["cvf_regae_forward"])
+_SIGNATURES["cvf_regae_ragged_backward"] = _with_depths(_SIGNATURES["cvf_regae_backward"])
+_SIGNATURES["cvf_regae_ragged_backward_reuse"] = _with_depths(_SIGNATURES["cvf_regae_backward"])
 # the isotropic-metric forms of the two front calls take the arguments of their general twins
 _SIGNATURES["cvf_ef16_front_iso"] = _SIGNATURES["cvf_ef16_front"]
 _SIGNATURES["cvf_ef16_front_rows_iso"] = _SIGNATURES["cvf_ef16_front_rows"]

@@ -1828,8 +1828,9 @@ class _RegFlatParams:
         K, Ld = len(regs), len(dec)
         for r in regs:
             if len(r) != Ld or any(ra != da for (_, ra), (_, da) in zip(r, dec)):
-                raise NotImplementedError("the MI355X path runs decoder and regulariser nets side by side: they must have the "
-                                          "same number of layers (as in the reference's notebooks)")
+                raise NotImplementedError("this layout runs decoder and regulariser nets side by side, layer for layer: they must have "
+                                          "the same number of layers and activations (nets of different depths take "
+                                          "_RegRaggedFlatParams and the cvf_regae_ragged_* calls, as RegAutoEncoderTask chooses)")
             if r[-1][0].out_features != 1:
                 raise NotImplementedError("regulariser nets must be scalar-valued")
         assert len(enc) + Ld <= _hip.MAX_LAYERS, f"at most {_hip.MAX_LAYERS} layers (encoder + decoder)"
@@ -1889,6 +1890,84 @@ class _RegFlatParams:
 
     def grad_views(self):
         return [(p, gv) for p, _, gv in self.views]
+
+
+class _RegRaggedFlatParams(_RegFlatParams):
+    """:class:`_RegFlatParams` for a decoder of ``Ld`` and regulariser nets of ``Lr != Ld`` Linear layers (``n_dec`` / ``n_reg``): the
+    chain of ``cvf_regae_ragged_*`` (include/cvf.h), ``n_enc + max(Ld, Lr)`` layers.  Merged layer m holds the rows of the groups
+    still alive at depth m, the deeper group's first (``dec_deep``: ``[dec_m | reg_1,m | .. | reg_K,m]``, else the K nets and then
+    the decoder).  The shallower group's last layer has no activation and its rows stay in that layer's image; the next layer
+    reads the rows before them, so its matrix is dense ``[out][live rows]`` - no column is ever stored for a finished row.  The
+    chain ends in the deeper group's outputs.  Aliasing, ``mask`` and ``grad_views`` are :class:`_RegFlatParams`'s."""
+
+    def __init__(self, model, device, freeze_encoder=False):
+        from .nn import _chain_layers
+        model.to(device=device, dtype=torch.float32)
+        enc, dec = _chain_layers(model.encoder), _chain_layers(model.decoder)
+        regs = [_chain_layers(r) for r in model.reg]
+        K, Ld, Lr = len(regs), len(dec), len(regs[0])
+        assert K > 0 and Ld != Lr, "equal depths are _RegFlatParams's"
+        for r in regs:
+            if [(lin.in_features, lin.out_features, a) for lin, a in r] != [(lin.in_features, lin.out_features, a) for lin, a in regs[0]]:
+                raise NotImplementedError("the regulariser nets must share one reg_layer_dims and one activation")
+            if r[-1][0].out_features != 1:
+                raise NotImplementedError("regulariser nets must be scalar-valued")
+        self.dec_deep = Ld > Lr
+        deep, shallow = ([dec], regs) if self.dec_deep else (regs, [dec])
+        Ls, Lmax = min(Ld, Lr), max(Ld, Lr)
+        # the two groups run through the same epilogue up to the layer that ends the shallower one, whose rows take none
+        if any(shallow[0][m][1] != deep[0][m][1] for m in range(Ls - 1)) or shallow[0][Ls - 1][1] != 0:
+            raise NotImplementedError("decoder and regulariser nets of different depths (csrc/regae_general.hip: cvf_regae_ragged_*) "
+                                      "must share the activation between their layers and have none behind their last ones")
+        assert len(enc) + Lmax <= _hip.MAX_LAYERS, f"at most {_hip.MAX_LAYERS} layers (encoder + the deeper of decoder and regulariser nets)"
+        self.n_dec, self.n_reg, self.K = Ld, Lr, K
+        alive = lambda m: deep + (shallow if m < Ls else [])
+        shapes = [(lin.out_features, lin.in_features, act) for lin, act in enc]
+        for m in range(Lmax):
+            fin = dec[0][0].in_features if m == 0 else sum(ch[m][0].in_features for ch in alive(m))
+            shapes.append((sum(ch[m][0].out_features for ch in alive(m)), fin, deep[0][m][1]))
+        self.n = sum(fo * fi + fo for fo, fi, _ in shapes)
+        self.theta = torch.zeros(self.n, device=device, dtype=torch.float32)
+        self.grad = torch.zeros(self.n, device=device, dtype=torch.float32)
+        self.mask = torch.zeros(self.n, device=device, dtype=torch.float32)
+        self.packed = None
+        d = _hip.MLPDesc()
+        d.n_nets, d.n_layers, d.n_params = 1, len(shapes), self.n
+        self.views = []   # (parameter, view of theta, view of grad)
+
+        def alias(p, region, r0, r1, c0=None, c1=None, frozen=False):
+            tv, gv, mv = (region(t)[r0:r1] if c0 is None else region(t)[r0:r1, c0:c1] for t in (self.theta, self.grad, self.mask))
+            tv.copy_(p.data)
+            mv.fill_(0.0 if frozen else 1.0)
+            p.data = tv
+            self.views.append((p, tv, gv))
+
+        pos = 0
+        d.dims[0] = shapes[0][1]
+        for l, (fo, fi, act) in enumerate(shapes):
+            d.dims[l + 1], d.act[l] = fo, int(act)      # (dims[l] is the image's width: fi + the finished rows behind a live prefix)
+            d.w_off[0][l], d.b_off[0][l] = pos, pos + fo * fi
+            wreg = (lambda t, a=pos, fo=fo, fi=fi: t[a:a + fo * fi].view(fo, fi))
+            breg = (lambda t, a=pos + fo * fi, fo=fo: t[a:a + fo])
+            if l < len(enc):
+                lin = enc[l][0]
+                alias(lin.weight, wreg, 0, fo, 0, fi, frozen=freeze_encoder)
+                alias(lin.bias, breg, 0, fo, frozen=freeze_encoder)
+            else:
+                m = l - len(enc)
+                r0 = c0 = 0
+                for chain in alive(m):
+                    lin = chain[m][0]
+                    cw = lin.in_features
+                    if m == 0:
+                        alias(lin.weight, wreg, r0, r0 + lin.out_features, 0, cw)       # every block reads the latent vector
+                    else:
+                        alias(lin.weight, wreg, r0, r0 + lin.out_features, c0, c0 + cw)
+                        c0 += cw
+                    alias(lin.bias, breg, r0, r0 + lin.out_features)
+                    r0 += lin.out_features
+            pos += fo * fi + fo
+        self.desc = d
 
 
 class _EncGradPenalty:
@@ -2204,7 +2283,9 @@ class RegAutoEncoderTask(TrainingTask):
     again, output gradients, parameter gradient on the matrix cores, fixed-order reduction, Adam).  A merged chain whose
     parameters and activations do not fit that kernel's 160 KiB of LDS runs the same three calls layer by layer instead
     (``cvf_regae_general_*``: widths up to 4096 units, the same outputs); a chain past both routes is refused with
-    NotImplementedError at construction.
+    NotImplementedError at construction.  Decoder and regulariser nets may have different numbers of layers (nn.py:137-154
+    builds the chains independently; the K nets share one ``reg_layer_dims``): that chain (:class:`_RegRaggedFlatParams`) always
+    runs layer by layer (``cvf_regae_ragged_*``), with every option.
 
     ``general_nets`` (not in the reference; default False): the two parts that run on the eigenfunction task's kernels - the
     generator-mode regulariser and ``eta[0]`` - take shapes without a kernel instance too (chains regulariser o encoder and
@@ -2274,8 +2355,8 @@ class RegAutoEncoderTask(TrainingTask):
             self._pp = self._pp_desc(self.tot_dim)
         self._feature_traj = self._features(traj)
         d = self._flat.desc
-        assert self._pp.d_r == d.dims[0] and d.dims[d.n_layers] == d.dims[0] + self.num_reg, \
-            'encoder input / decoder output width must equal the feature dimension'
+        d_out = self.model.decoder[-1].out_features if self._depths else d.dims[d.n_layers] - self.num_reg
+        assert self._pp.d_r == d.dims[0] and d_out == d.dims[0], 'encoder input / decoder output width must equal the feature dimension'
         if self.verbose:
             print('\nShape of trajectory data array:\n {}'.format(tuple(traj.shape)), flush=True)
         cfg = _hip.EFCfg()
@@ -2298,14 +2379,24 @@ class RegAutoEncoderTask(TrainingTask):
         self._traj = None if self._gen is None else self._gen.inner._frames(traj)
 
     # -- the base class builds the flat buffer from mlp_layout(); this model needs the side-by-side chain
+    #    (decoder and regulariser nets of different depths: the ragged one, cvf_regae_ragged_*)
     def _flat_params(self):
-        return _RegFlatParams(self.model, self.device, self.freeze_encoder)
+        from .nn import _chain_layers
+        depths = {len(_chain_layers(net)) for net in [self.model.decoder] + (list(self.model.reg) if self.model.num_reg > 0 else [])}
+        flat = (_RegFlatParams if len(depths) == 1 else _RegRaggedFlatParams)(self.model, self.device, self.freeze_encoder)
+        # (n_dec_layers, n_reg_layers) behind n_enc_layers in every cvf_regae_ragged_* call; () on the equal-depth routes
+        self._depths = (flat.n_dec, flat.n_reg) if isinstance(flat, _RegRaggedFlatParams) else ()
+        return flat
 
     def _needs_general(self):
         """False where the fused chain kernel takes the merged chain (cvf_regae_route: a 64-frame tile's chain in LDS), True where
         only the per-layer route of csrc/regae_general.hip does - then for every pass, loss-only ones included; a chain past both
         is refused here, at construction.  (The layout with a gradient is the larger one: where it fits, the forward pass does.)"""
         lib, fl = _hip.lib(), self._flat
+        if self._depths:   # different depths always go per layer (the fused kernel runs the two groups layer for layer)
+            if lib.cvf_regae_ragged_supported(fl.desc, self.num_reg, self._n_enc_layers, *self._depths) != 1:
+                raise NotImplementedError("RegAutoEncoderTask: no HIP route trains this chain (%s)" % lib.cvf_last_error().decode())
+            return True
         if lib.cvf_regae_route(fl.desc, 1, None) >= 0:
             return False
         fused = lib.cvf_last_error().decode()
@@ -2329,9 +2420,12 @@ class RegAutoEncoderTask(TrainingTask):
         if ws is None:
             lib, K, dev = _hip.lib(), max(self.num_reg, 1), self.device
             T = _hip.ntiles(B)
-            size = lib.cvf_regae_general_scratch_floats if self._general else lib.cvf_regae_scratch_floats
+            if self._depths:
+                size = lib.cvf_regae_ragged_scratch_floats(self._flat.desc, B, self.num_reg, self._n_enc_layers, *self._depths)
+            else:
+                size = (lib.cvf_regae_general_scratch_floats if self._general else lib.cvf_regae_scratch_floats)(self._flat.desc, B)
             ws = dict(
-                scratch=torch.empty(size(self._flat.desc, B), device=dev, dtype=torch.float32),
+                scratch=torch.empty(size, device=dev, dtype=torch.float32),
                 y=torch.zeros(2 * T * K * 64, device=dev, dtype=torch.float32),
                 out2=torch.zeros(3, device=dev, dtype=torch.float64),
                 stats=torch.zeros(lib.cvf_ef_nstats(K, 1), device=dev, dtype=torch.float64),
@@ -2369,14 +2463,17 @@ class RegAutoEncoderTask(TrainingTask):
         eta1 = float(self.eta[1]) if self.eta[1] > self._eps else 0.0
         eta2 = float(self.eta[2]) if self.eta[2] > self._eps else 0.0
         # (with a gradient to follow, the statistics pass leaves its activations in the scratch buffer for the gradient pass)
-        if self._general:
+        if self._depths:
+            fwd = fwd_keep = lib.cvf_regae_ragged_forward
+            bwd_reuse = lib.cvf_regae_ragged_backward_reuse
+        elif self._general:
             fwd = fwd_keep = lib.cvf_regae_general_forward
             bwd_reuse = lib.cvf_regae_general_backward_reuse
         else:
             fwd, fwd_keep, bwd_reuse = lib.cvf_regae_forward, lib.cvf_regae_forward_keep, lib.cvf_regae_backward_reuse
         self._call("cvf_regae_forward", fwd_keep if with_grad else fwd, fl.desc, P(fl.theta),
                    P(feat), P(idx), B, lag_ae, lag_reg if use_reg else 0, K, P(w), P(ws["scratch"]), P(ws["y"]), self._n_enc_layers,
-                   P(ws["enc"]) if use_enc else None, P(ws["out2"]), _hip.stream())
+                   *self._depths, P(ws["enc"]) if use_enc else None, P(ws["out2"]), _hip.stream())
         if dp:
             self._allreduce("allreduce_batch_sums", ws["out2"])     # [sum w err, sum w, (ratio: recomputed by cvf_regae_loss_row)]
         if use_enc:   # core.py:912-971: weighted means / variances / covariances of the latent vector, then the two penalties
@@ -2413,7 +2510,7 @@ class RegAutoEncoderTask(TrainingTask):
             self._call("cvf_regae_backward", bwd_reuse, fl.desc, P(fl.theta), P(feat), P(idx), B, lag_ae,
                        lag_reg if use_reg else 0, K, P(w), P(w_lag) if use_reg else None, alpha / wsum,
                        float(self.gamma[0]) if use_reg else 0.0, P(ws["y"]) if use_reg else None,
-                       P(ws["coef"]) if use_reg else None, self._n_enc_layers, P(ws["ecoef"]) if use_enc else None,
+                       P(ws["coef"]) if use_reg else None, self._n_enc_layers, *self._depths, P(ws["ecoef"]) if use_enc else None,
                        P(ws["scratch"]), P(fl.grad), P(fl.mask),
                        P(self.optimizer.step_count) if advance else None, adam, _hip.stream())
         if gen is not None:

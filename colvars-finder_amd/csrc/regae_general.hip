@@ -17,6 +17,10 @@
 // and every gradient product of those frames vanishes: aeg_wgrad_kernel is told that all frames of the 2 T tiles are valid.
 // No atomics.  Nothing is read from scratch that the same call did not write, apart from the hand-off from
 // cvf_regae_general_forward to cvf_regae_general_backward_reuse (the images a_0..a_{L-1} and the chain's output).
+//
+// A decoder and regulariser nets of DIFFERENT depths (cvf_regae_ragged_*, the second half of this file; the chain of
+// _RegRaggedFlatParams) run on the same kernels: regaeg_out_kernel takes the reconstruction and the heads as two views, which the
+// calls above point into the one image Z(L) and the ragged calls into the images where the two groups end.
 #include "aeg_kernels.hpp"
 
 int cvf_slab_reduce_impl(const float* slab, int64_t n_rows, int64_t n_params, float* grad, const float* mask,
@@ -25,8 +29,19 @@ int cvf_slab_reduce_impl(const float* slab, int64_t n_rows, int64_t n_params, fl
 
 namespace {
 
+// One group's rows of an image: where its values are read and (with a gradient) where its adjoint goes.  The two coincide in the
+// chain's last image (Z(L): zbar_L takes the output's place) and differ for the rows a shallower group has finished in an inner
+// image (a_ls -> zbar_ls, the ragged chains below).
+struct RegaegView {
+  const float* in;   // NULL: these rows are not this launch's
+  float* zb;
+  int64_t is, zs;    // tile strides
+  int act;           // the activation behind these rows
+};
+
 struct RegaegOutArgs {
-  int d0, K, act;            // reconstruction rows, heads, the last layer's activation
+  int d0, K;                 // reconstruction rows, heads
+  RegaegView rec, head;      // [d0][64] and [K][64] per tile
   int with_grad;
   int64_t T, B;              // base tiles (tiles T.. are the lagged ones), frames
   int64_t lag_t;             // reconstruction target row = idx + lag_t
@@ -45,9 +60,8 @@ struct RegaegOutArgs {
 
 // One tile's outputs.  Reconstruction rows go 64 at a time through an LDS transpose of the target rows (read along the features,
 // as aeg_gather_kernel reads its input); wave j takes rows j, j + 4, ... of a chunk and the four waves' sums of a frame are
-// added in the order 0, 1, 2, 3 (aeg_err_kernel's rule).
-__global__ __launch_bounds__(256) void regaeg_out_kernel(float* __restrict__ out, RegaegOutArgs a, double* __restrict__ partial,
-                                                         int32_t* __restrict__ step) {
+// added in the order 0, 1, 2, 3 (aeg_err_kernel's rule).  The loss pairs and the step counter go with the reconstruction's launch.
+__global__ __launch_bounds__(256) void regaeg_out_kernel(RegaegOutArgs a, double* __restrict__ partial, int32_t* __restrict__ step) {
   __shared__ float S[CVF_TILE * kTP];   // [frame][feature] of the target rows
   __shared__ double part[4][CVF_TILE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -57,10 +71,11 @@ __global__ __launch_bounds__(256) void regaeg_out_kernel(float* __restrict__ out
   const int64_t frame = t0 * CVF_TILE + lane;
   const bool valid = frame < a.B;
   const float wraw = valid ? a.w[frame] : 0.0f;
-  const int dL = a.d0 + a.K;
-  float* op = out + tile * dL * CVF_TILE;
+  const bool do_rec = a.rec.in != nullptr;
 
-  if (!lagged) {
+  if (do_rec && !lagged) {
+    const float* ip = a.rec.in + tile * a.rec.is;
+    float* zp = a.rec.zb + tile * a.rec.zs;
     const float s = (float)(2.0 * (double)wraw * a.mse_scale);
     double e = 0.0;
     for (int c0 = 0; c0 < a.d0; c0 += 64) {
@@ -80,10 +95,10 @@ __global__ __launch_bounds__(256) void regaeg_out_kernel(float* __restrict__ out
       for (int it = 0; it < 16; ++it) {
         const int c = wave + 4 * it, i = c0 + c;
         if (i < a.d0) {
-          const float o = op[(int64_t)i * CVF_TILE + lane];
+          const float o = ip[(int64_t)i * CVF_TILE + lane];
           const float d = o - S[lane * kTP + c];
           if (valid) e += (double)d * (double)d;
-          if (a.with_grad) op[(int64_t)i * CVF_TILE + lane] = valid ? s * d * cvf_act_d1(a.act, o) : 0.0f;
+          if (a.with_grad) zp[(int64_t)i * CVF_TILE + lane] = valid ? s * d * cvf_act_d1(a.rec.act, o) : 0.0f;
         }
       }
       __syncthreads();
@@ -92,27 +107,31 @@ __global__ __launch_bounds__(256) void regaeg_out_kernel(float* __restrict__ out
     if (a.enc_out != nullptr)
       for (int j = wave; j < a.k_enc; j += 4)
         a.enc_out[(t0 * a.k_enc + j) * CVF_TILE + lane] = a.enc_img[(tile * a.k_enc + j) * CVF_TILE + lane];
-  } else if (a.with_grad) {
-    for (int i = wave; i < a.d0; i += 4) op[(int64_t)i * CVF_TILE + lane] = 0.0f;   // no reconstruction error on the lagged rows
+  } else if (do_rec && a.with_grad) {
+    float* zp = a.rec.zb + tile * a.rec.zs;
+    for (int i = wave; i < a.d0; i += 4) zp[(int64_t)i * CVF_TILE + lane] = 0.0f;   // no reconstruction error on the lagged rows
   }
 
   // regulariser head i: its value, and the output gradient of the transfer-operator loss (ae_mfma_kernel's, csrc/ae.hip)
-  for (int i = wave; i < a.K; i += 4) {
-    const int64_t o = (int64_t)(a.d0 + i) * CVF_TILE + lane;
-    const float y = op[o];
-    if (a.y_out != nullptr) a.y_out[(tile * a.K + i) * CVF_TILE + lane] = y;
-    if (!a.with_grad) continue;
-    float zb = 0.0f;
-    if (a.coef != nullptr && valid) {
-      const float* yb = a.y_in + t0 * a.K * CVF_TILE + lane;
-      const float* yl = a.y_in + (a.T + t0) * a.K * CVF_TILE + lane;
-      const double g = g64_transfer_grad(a.coef, a.K, i, yb, yl, lagged, wraw, lagged ? a.w_lag[frame] : 0.0f);
-      zb = (float)(a.head_scale * g) * cvf_act_d1(a.act, y);
+  if (a.head.in != nullptr) {
+    const float* ip = a.head.in + tile * a.head.is + lane;
+    float* zp = a.head.zb + tile * a.head.zs + lane;
+    for (int i = wave; i < a.K; i += 4) {
+      const float y = ip[(int64_t)i * CVF_TILE];
+      if (a.y_out != nullptr) a.y_out[(tile * a.K + i) * CVF_TILE + lane] = y;
+      if (!a.with_grad) continue;
+      float zb = 0.0f;
+      if (a.coef != nullptr && valid) {
+        const float* yb = a.y_in + t0 * a.K * CVF_TILE + lane;
+        const float* yl = a.y_in + (a.T + t0) * a.K * CVF_TILE + lane;
+        const double g = g64_transfer_grad(a.coef, a.K, i, yb, yl, lagged, wraw, lagged ? a.w_lag[frame] : 0.0f);
+        zb = (float)(a.head_scale * g) * cvf_act_d1(a.head.act, y);
+      }
+      zp[(int64_t)i * CVF_TILE] = zb;
     }
-    op[o] = zb;
   }
 
-  if (lagged) return;
+  if (!do_rec || lagged) return;
   __syncthreads();
   if (wave == 0) {
     const double err = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
@@ -262,10 +281,14 @@ int regaeg_chain_forward(const RegaegCall& c, const float* feat_rows, const int6
 
 int regaeg_out(const RegaegCall& c, RegaegOutArgs o, int32_t* step_count) {
   const cvf_mlp_desc* mlp = c.mlp;
+  const int L = mlp->n_layers;
   o.d0 = mlp->dims[0];
-  o.act = mlp->act[mlp->n_layers - 1];
   o.T = c.T;
-  hipLaunchKernelGGL(regaeg_out_kernel, dim3((unsigned)c.NT), dim3(256), 0, c.s, c.Z(mlp->n_layers), o, c.partial(), step_count);
+  // [reconstruction | y_1..y_K] in the one image Z(L), in place
+  o.rec = RegaegView{c.Z(L), c.Z(L), c.ts(L), c.ts(L), mlp->act[L - 1]};
+  o.head = o.rec;
+  o.head.in = o.head.zb = c.Z(L) + (int64_t)o.d0 * CVF_TILE;
+  hipLaunchKernelGGL(regaeg_out_kernel, dim3((unsigned)c.NT), dim3(256), 0, c.s, o, c.partial(), step_count);
   return cvf_check_launch("regaeg_out_kernel");
 }
 
@@ -351,7 +374,289 @@ int regaeg_backward_impl(const cvf_mlp_desc* mlp, const float* theta, const floa
   return cvf_slab_reduce_impl(slab, R, mlp->n_params, grad, mask, adam != nullptr ? &ad : nullptr, stream);
 }
 
+// ---- decoder and regulariser nets of different depths (cvf_regae_ragged_*; core._RegRaggedFlatParams builds the chain).  Behind
+// the encoder the deeper group's rows come first in every merged layer, so that once the shallower group has ended (in image
+// ls = n_enc + min(Ld, Lr), as its last `fin` rows: d_0 reconstruction rows or K heads, without activation) the next layer reads
+// the live prefix of that image: its matrix is dense [dims[ls + 1]][dims[ls] - fin], and every other layer's [dims[l + 1]][dims[l]].
+// The finished rows stay in the saved image a_ls; their adjoint is seeded into zbar_ls after the transposed product that writes
+// the live rows of zbar_ls and before the weight-gradient launch that reads all of it.
+struct RagShape {
+  int L, ne, ls, fin;
+  bool dec_deep;   // the decoder is the deeper group: the chain ends in the reconstruction, the heads end in image ls
+  int in(const cvf_mlp_desc* mlp, int l) const { return l == ls ? mlp->dims[l] - fin : mlp->dims[l]; }   // columns of W_l
+};
+
+// regaeg_why's limits for the ragged chain; fills `sh` when the answer is NULL
+const char* rag_why(const cvf_mlp_desc* mlp, int K, int n_enc, int n_dec, int n_reg, RagShape* sh) {
+  static thread_local char buf[200];
+  if (mlp == nullptr) return "no chain description";
+  if (mlp->n_nets != 1) {
+    snprintf(buf, sizeof buf, "%d nets: one chain is expected", mlp->n_nets);
+    return buf;
+  }
+  const char* why = g64_why(mlp, mlp->n_layers, G64Chain{2, "layer", "chain", false, true}, buf, sizeof buf);
+  if (why != nullptr) return why;
+  const int L = mlp->n_layers;
+  if (K < 1 || K > CVF_MAX_NETS) {
+    snprintf(buf, sizeof buf, "K = %d regulariser heads: 1 to %d are supported", K, CVF_MAX_NETS);
+    return buf;
+  }
+  if (n_dec < 1 || n_reg < 1 || n_dec == n_reg) {
+    snprintf(buf, sizeof buf, "decoder and regulariser nets of %d and %d layers: two different depths >= 1 are expected (equal depths "
+             "take cvf_regae_general_*)", n_dec, n_reg);
+    return buf;
+  }
+  const int deep = n_dec > n_reg ? n_dec : n_reg, shallow = n_dec > n_reg ? n_reg : n_dec;
+  if (n_enc < 1 || n_enc + deep != L) {
+    snprintf(buf, sizeof buf, "n_enc_layers=%d + max(%d, %d) is not the chain's %d layers", n_enc, n_dec, n_reg, L);
+    return buf;
+  }
+  if (mlp->act[n_enc - 1] != CVF_ACT_NONE) return "the encoder's last layer must have no activation";
+  if (mlp->dims[n_enc] > CVF_MAX_NETS) {
+    snprintf(buf, sizeof buf, "latent width %d > %d", mlp->dims[n_enc], CVF_MAX_NETS);
+    return buf;
+  }
+  RagShape s;
+  s.L = L;
+  s.ne = n_enc;
+  s.ls = n_enc + shallow;
+  s.dec_deep = n_dec > n_reg;
+  s.fin = s.dec_deep ? K : mlp->dims[0];
+  const int last = s.dec_deep ? mlp->dims[0] : K;
+  if (mlp->dims[L] != last) {
+    snprintf(buf, sizeof buf, "the chain must end in the deeper group's %d outputs (it has %d)", last, mlp->dims[L]);
+    return buf;
+  }
+  if (mlp->dims[s.ls] <= s.fin) {
+    snprintf(buf, sizeof buf, "layer %d is %d wide: the shallower group's %d outputs leave no row for the deeper one", s.ls,
+             mlp->dims[s.ls], s.fin);
+    return buf;
+  }
+  int64_t n = 0;
+  for (int l = 0; l < L; ++l) n += (int64_t)mlp->dims[l + 1] * (s.in(mlp, l) + 1);
+  if (n != mlp->n_params) return "the flat buffer holds parameters outside the chain";
+  for (int l = 0; l < L; ++l)
+    if (mlp->w_off[0][l] < 0 || mlp->w_off[0][l] + (int64_t)mlp->dims[l + 1] * s.in(mlp, l) > n || mlp->b_off[0][l] < 0 ||
+        mlp->b_off[0][l] + (int64_t)mlp->dims[l + 1] > n)
+      return "a layer's parameters lie outside the flat buffer";
+  if (sh != nullptr) *sh = s;
+  return nullptr;
+}
+
+struct RagCall {
+  RegaegCall c;
+  RagShape sh;
+  int K;
+  int in(int l) const { return sh.in(c.mlp, l); }
+  // the finished rows of image ls (values in a_ls, adjoint in zbar_ls) and the chain's last layer (Z(L), in place)
+  RegaegView finished() const {
+    const int64_t off = (int64_t)in(sh.ls) * CVF_TILE;
+    return RegaegView{c.A(sh.ls) + off, c.Z(sh.ls) + off, c.ts(sh.ls), c.ts(sh.ls), CVF_ACT_NONE};
+  }
+  RegaegView last() const { return RegaegView{c.Z(sh.L), c.Z(sh.L), c.ts(sh.L), c.ts(sh.L), c.mlp->act[sh.L - 1]}; }
+  int out(RegaegOutArgs o, bool rec, bool head, int32_t* step_count) const {
+    o.d0 = c.mlp->dims[0];
+    o.K = K;
+    o.T = c.T;
+    if (rec) o.rec = sh.dec_deep ? last() : finished();
+    if (head) o.head = sh.dec_deep ? finished() : last();
+    hipLaunchKernelGGL(regaeg_out_kernel, dim3((unsigned)c.NT), dim3(256), 0, c.s, o, c.partial(), step_count);
+    return cvf_check_launch("regaeg_out_kernel");
+  }
+};
+
+int rag_begin(RagCall& r, const char* who, const cvf_mlp_desc* mlp, const float* theta, int64_t B, int64_t lag_target,
+              int64_t lag_input, int K, int n_enc, int n_dec, int n_reg, float* scratch, void* stream) {
+  const char* why = rag_why(mlp, K, n_enc, n_dec, n_reg, &r.sh);
+  CVF_REQUIRE(why == nullptr, "%s: %s", who, why);
+  CVF_REQUIRE(lag_target >= 0 && lag_input >= 0, "%s: negative lag", who);
+  RegaegCall& c = r.c;
+  c.T = cvf_ntiles(B);
+  CVF_REQUIRE(2 * c.T <= 0x7fffffff, "%s: %lld frames are more than one call takes", who, (long long)B);
+  c.NT = lag_input > 0 ? 2 * c.T : c.T;
+  c.mlp = mlp;
+  c.theta = theta;
+  c.scratch = scratch;
+  c.lay = regaeg_layout(mlp, c.T);
+  c.s = (hipStream_t)stream;
+  r.K = K;
+  return 0;
+}
+
+// gather + the chain forward: a_1..a_{L-1} (a_ls with the finished rows), the output in Z(L).  The layer that ends the shallower
+// group is two launches over its row ranges: the live rows take the layer's activation, the finished rows none.
+int rag_chain_forward(const RagCall& r, const float* feat_rows, const int64_t* idx, int64_t B, int64_t lag_input) {
+  const RegaegCall& c = r.c;
+  const cvf_mlp_desc* mlp = c.mlp;
+  const int L = mlp->n_layers;
+  hipLaunchKernelGGL(aeg_gather_kernel, dim3((unsigned)c.NT), dim3(256), 0, c.s, feat_rows, idx, B, mlp->dims[0], c.A(0), c.T, lag_input);
+  if (cvf_check_launch("aeg_gather_kernel")) return -1;
+  for (int l = 0; l < L; ++l) {
+    const int ki = r.in(l), mo = mlp->dims[l + 1];
+    const int live = l + 1 == r.sh.ls ? mo - r.sh.fin : mo;
+    for (int r0 = 0; r0 < mo; r0 = r0 == 0 ? live : mo) {   // rows [0, live), then [live, mo) when there are any
+      AegLayerArgs a = {};
+      a.w_off = mlp->w_off[0][l] + r0 * ki;
+      a.b_off = mlp->b_off[0][l] + r0;
+      a.ldw = ki;
+      a.M = r0 == 0 ? live : mo - live;
+      a.K = ki;
+      a.epi = EPI_ACT;
+      a.act = r0 == 0 ? mlp->act[l] : CVF_ACT_NONE;
+      a.x = c.A(l);
+      a.xs = c.ts(l);
+      a.out = (l + 1 < L ? c.A(l + 1) : c.Z(L)) + (int64_t)r0 * CVF_TILE;
+      a.os = c.ts(l + 1);
+      if (c.layer(a)) return -1;
+    }
+  }
+  return 0;
+}
+
+int rag_backward_impl(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                      int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag, double mse_scale,
+                      double head_scale, const float* y_tiled, const double* coef, int n_enc, int n_dec, int n_reg,
+                      const double* enc_coef, float* scratch, float* grad, const float* mask, int32_t* step_count,
+                      const cvf_adam_args* adam, void* stream, bool reuse) {
+  const char* who = "cvf_regae_ragged_backward";
+  RagCall r;
+  if (rag_begin(r, who, mlp, theta, B, lag_target, lag_input, K, n_enc, n_dec, n_reg, scratch, stream)) return -1;
+  const RegaegCall& c = r.c;
+  CVF_REQUIRE(theta && feat_rows && w && scratch && grad && B > 0, "%s: bad argument", who);
+  CVF_REQUIRE(coef == nullptr || (lag_input > 0 && w_lag && y_tiled), "%s: the regulariser needs lag_input > 0, w_lag and y_tiled", who);
+  CVF_REQUIRE(adam == nullptr || (adam->theta && adam->m && adam->v && adam->step_count), "%s: incomplete adam arguments", who);
+  const int L = mlp->n_layers;
+  if (!reuse && rag_chain_forward(r, feat_rows, idx, B, lag_input)) return -1;
+  RegaegOutArgs o = {};
+  o.with_grad = 1;
+  o.B = B;
+  o.lag_t = lag_target;
+  o.feat_rows = feat_rows;
+  o.idx = idx;
+  o.w = w;
+  o.w_lag = w_lag;
+  o.mse_scale = mse_scale;
+  o.head_scale = head_scale;
+  o.coef = coef;
+  o.y_in = y_tiled;
+  // zbar_L: the deeper group's seed (the step counter goes with the reconstruction's launch, whichever it is)
+  if (r.out(o, r.sh.dec_deep, !r.sh.dec_deep, r.sh.dec_deep ? step_count : nullptr)) return -1;
+
+  const int R = (int)g64_rows(mlp, c.NT);
+  float* slab = scratch + c.lay.slab;
+  for (int l = L - 1; l >= 0; --l) {
+    {  // layer l's gradient from zbar_{l+1} and the rows of a_l it reads
+      AegGradArgs g = {};
+      g.w_off = mlp->w_off[0][l];
+      g.b_off = mlp->b_off[0][l];
+      g.Mo = mlp->dims[l + 1];
+      g.Ki = r.in(l);
+      g.n_tiles = c.NT;
+      g.B = c.NT * CVF_TILE;   // every frame counts: the padded ones carry zero adjoints
+      g.rows = R;
+      g.n_params = mlp->n_params;
+      g.z = c.Z(l + 1);
+      g.zs = c.ts(l + 1);
+      g.h = c.A(l);
+      g.hs = c.ts(l);
+      const int nb = ((g.Mo + 63) / 64) * ((g.Ki + 1 + 63) / 64);
+      hipLaunchKernelGGL(aeg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb), dim3(256), 0, c.s, g, slab);
+      if (cvf_check_launch("aeg_wgrad_kernel")) return -1;
+    }
+    if (l == 0) break;
+    // rows [0, in(l)) of zbar_l = (W_l^T zbar_{l+1}) .* act'_{l-1}(a_l)
+    AegLayerArgs a = {};
+    a.w_off = mlp->w_off[0][l];
+    a.b_off = -1;
+    a.ldw = r.in(l);
+    a.trans = 1;
+    a.M = r.in(l);
+    a.K = mlp->dims[l + 1];
+    a.epi = EPI_BWD;
+    a.act = mlp->act[l - 1];
+    a.x = c.Z(l + 1);
+    a.xs = c.ts(l + 1);
+    a.out = c.Z(l);
+    a.os = c.ts(l);
+    a.eh = c.A(l);
+    a.es = c.ts(l);
+    if (c.layer(a)) return -1;
+    // the finished rows of zbar_ls: the shallower group's seed
+    if (l == r.sh.ls && r.out(o, !r.sh.dec_deep, r.sh.dec_deep, r.sh.dec_deep ? nullptr : step_count)) return -1;
+    if (enc_coef != nullptr && l == n_enc) {
+      hipLaunchKernelGGL(regaeg_enc_kernel, dim3((unsigned)c.T), dim3(256), 0, c.s, c.Z(l), c.A(l), mlp->dims[l], w, B, enc_coef);
+      if (cvf_check_launch("regaeg_enc_kernel")) return -1;
+    }
+  }
+  cvf_adam_args ad;
+  if (adam != nullptr) {
+    ad = *adam;
+    ad.mlp = nullptr;      // no MFMA fragment copy to refresh
+    ad.packed = nullptr;
+  }
+  return cvf_slab_reduce_impl(slab, R, mlp->n_params, grad, mask, adam != nullptr ? &ad : nullptr, stream);
+}
+
 }  // namespace
+
+extern "C" int cvf_regae_ragged_supported(const cvf_mlp_desc* mlp, int K, int n_enc_layers, int n_dec_layers, int n_reg_layers) {
+  const char* why = rag_why(mlp, K, n_enc_layers, n_dec_layers, n_reg_layers, nullptr);
+  if (why != nullptr) {
+    cvf_set_error("cvf_regae_ragged: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_regae_ragged_scratch_floats(const cvf_mlp_desc* mlp, int64_t B, int K, int n_enc_layers, int n_dec_layers,
+                                                   int n_reg_layers) {
+  if (B < 1 || rag_why(mlp, K, n_enc_layers, n_dec_layers, n_reg_layers, nullptr) != nullptr) return 0;
+  return regaeg_layout(mlp, cvf_ntiles(B)).total;
+}
+
+extern "C" int cvf_regae_ragged_forward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx,
+                                        int64_t B, int64_t lag_target, int64_t lag_input, int K, const float* w, float* scratch,
+                                        float* y_tiled, int n_enc_layers, int n_dec_layers, int n_reg_layers, float* enc_tiled,
+                                        double* out2, void* stream) {
+  const char* who = "cvf_regae_ragged_forward";
+  RagCall r;
+  if (rag_begin(r, who, mlp, theta, B, lag_target, lag_input, K, n_enc_layers, n_dec_layers, n_reg_layers, scratch, stream)) return -1;
+  CVF_REQUIRE(theta && feat_rows && w && scratch && out2 && B > 0 && y_tiled, "%s: bad argument", who);
+  if (rag_chain_forward(r, feat_rows, idx, B, lag_input)) return -1;
+  RegaegOutArgs o = {};
+  o.B = B;
+  o.lag_t = lag_target;
+  o.feat_rows = feat_rows;
+  o.idx = idx;
+  o.w = w;
+  o.y_out = y_tiled;
+  o.enc_out = enc_tiled;
+  o.enc_img = r.c.A(n_enc_layers);
+  o.k_enc = mlp->dims[n_enc_layers];
+  if (r.out(o, true, true, nullptr)) return -1;
+  hipLaunchKernelGGL(aeg_loss_sum_kernel, dim3(1), dim3(64), 0, r.c.s, r.c.partial(), r.c.T, out2);
+  return cvf_check_launch("aeg_loss_sum_kernel");
+}
+
+extern "C" int cvf_regae_ragged_backward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx,
+                                         int64_t B, int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag,
+                                         double mse_scale, double head_scale, const float* y_tiled, const double* coef,
+                                         int n_enc_layers, int n_dec_layers, int n_reg_layers, const double* enc_coef, float* scratch,
+                                         float* grad, const float* mask, int32_t* step_count, const cvf_adam_args* adam,
+                                         void* stream) {
+  return rag_backward_impl(mlp, theta, feat_rows, idx, B, lag_target, lag_input, K, w, w_lag, mse_scale, head_scale, y_tiled, coef,
+                           n_enc_layers, n_dec_layers, n_reg_layers, enc_coef, scratch, grad, mask, step_count, adam, stream, false);
+}
+
+extern "C" int cvf_regae_ragged_backward_reuse(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx,
+                                               int64_t B, int64_t lag_target, int64_t lag_input, int K, const float* w,
+                                               const float* w_lag, double mse_scale, double head_scale, const float* y_tiled,
+                                               const double* coef, int n_enc_layers, int n_dec_layers, int n_reg_layers,
+                                               const double* enc_coef, float* scratch, float* grad, const float* mask,
+                                               int32_t* step_count, const cvf_adam_args* adam, void* stream) {
+  return rag_backward_impl(mlp, theta, feat_rows, idx, B, lag_target, lag_input, K, w, w_lag, mse_scale, head_scale, y_tiled, coef,
+                           n_enc_layers, n_dec_layers, n_reg_layers, enc_coef, scratch, grad, mask, step_count, adam, stream, true);
+}
 
 extern "C" int cvf_regae_general_supported(const cvf_mlp_desc* mlp, int K, int n_enc_layers) {
   const char* why = regaeg_why(mlp, K, n_enc_layers);

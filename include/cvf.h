@@ -618,6 +618,31 @@ int cvf_regae_general_backward_reuse(const cvf_mlp_desc* mlp, const float* theta
                        double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, const double* enc_coef,
                        float* scratch, float* grad, const float* mask, int32_t* step_count, const cvf_adam_args* adam,
                        void* stream);
+/* --- RegAutoEncoderTask with decoder and regulariser nets of DIFFERENT depths (csrc/regae_general.hip; DESIGN.md section 4.11;
+ * core.py:884-897, 975-1034, 1066-1128): the calls above for a chain of n_enc_layers + max(n_dec_layers, n_reg_layers) layers,
+ * n_dec_layers != n_reg_layers, both >= 1, 1 <= K <= CVF_MAX_NETS.  Behind the encoder every merged layer holds the rows of the
+ * groups still alive, the deeper group's first.  With ls = n_enc_layers + min(n_dec_layers, n_reg_layers), the last `fin` of the
+ * dims[ls] outputs of layer ls - 1 are the shallower group's outputs (fin = K heads when the decoder is deeper, else dims[0]
+ * reconstruction rows): they take no activation, and layer ls reads the other dims[ls] - fin >= 1, so its matrix is dense
+ * [dims[ls + 1]][dims[ls] - fin]; every other W_l is [dims[l + 1]][dims[l]].  dims[n_layers] is dims[0] (decoder deeper) or K.
+ * The parameters fill the flat buffer; the other limits, the arguments, outputs, scratch formula (with this n_params) and
+ * hand-off are those of the cvf_regae_general_* twin, which takes the equal depths these calls refuse.  No atomics. */
+int cvf_regae_ragged_supported(const cvf_mlp_desc* mlp, int K, int n_enc_layers, int n_dec_layers, int n_reg_layers);
+int64_t cvf_regae_ragged_scratch_floats(const cvf_mlp_desc* mlp, int64_t B, int K, int n_enc_layers, int n_dec_layers,
+                                        int n_reg_layers);
+int cvf_regae_ragged_forward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                      int64_t lag_target, int64_t lag_input, int K, const float* w, float* scratch, float* y_tiled,
+                      int n_enc_layers, int n_dec_layers, int n_reg_layers, float* enc_tiled, double* out2, void* stream);
+int cvf_regae_ragged_backward(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                       int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag, double mse_scale,
+                       double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, int n_dec_layers,
+                       int n_reg_layers, const double* enc_coef, float* scratch, float* grad, const float* mask,
+                       int32_t* step_count, const cvf_adam_args* adam, void* stream);
+int cvf_regae_ragged_backward_reuse(const cvf_mlp_desc* mlp, const float* theta, const float* feat_rows, const int64_t* idx, int64_t B,
+                       int64_t lag_target, int64_t lag_input, int K, const float* w, const float* w_lag, double mse_scale,
+                       double head_scale, const float* y_tiled, const double* coef, int n_enc_layers, int n_dec_layers,
+                       int n_reg_layers, const double* enc_coef, float* scratch, float* grad, const float* mask,
+                       int32_t* step_count, const cvf_adam_args* adam, void* stream);
 /* latent penalties from the latent vector's batch sums (cvf_ef_stats layout [W, S1(k), S2(i<=j), ..]):
  * terms = {sum_j (var_j - 1)^2, sum_{i<j} cov_ij^2} (core.py:934, 966); enc_coef [k + k*k] for cvf_regae_backward */
 int cvf_regae_enc_loss(const double* stats, int k, double eta1, double eta2, double* terms, double* enc_coef, void* stream);

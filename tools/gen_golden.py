@@ -353,6 +353,21 @@ def run_regae_cases(core, rnn, id2, mol10):
     torch.set_default_dtype(torch.float32)
 
 
+def run_regae_depth_cases(core, rnn, id2, mol10):
+    """Decoder and regulariser nets of different depths (nn.py:137-154 builds the three chains independently)."""
+    for dtype in (torch.float32, torch.float64):
+        # the decoder one layer deeper than the two regulariser nets, both lags, the latent penalties on
+        run_regae_train(core, rnn, "train_regae_depth_id2_k2", id2, [2, 12, 12, 2], [2, 12, 12, 2], [2, 12, 1], 2, dtype, 1.0,
+                        [1.0, 8.0], [1.0, 0.3], 1, 2, 0.5, 5e-3, 100, 3, 721, eta=(0.0, 0.5, 0.7))
+        # the regulariser nets one layer deeper than the decoder, main.ipynb's encoder through the alignment layer, lag_tau_ae = 0
+        run_regae_train(core, rnn, "train_regae_depth_mol10_k2", mol10, [30, 20, 20, 20, 2], [2, 10, 30], [2, 10, 10, 1], 2, dtype, 1.0,
+                        [1.0, 10.0], [1.0, 0.5], 0, 1, 0.5, 2e-3, 64, 3, 722)
+        # train_regae_id2_k1_gen with a decoder of one hidden layer: generator mode, the chain regulariser o encoder unchanged
+        run_regae_train(core, rnn, "train_regae_depth_id2_k1_gen", id2, [2, 20, 20, 20, 1], [1, 20, 2], [1, 20, 20, 1], 1, dtype, 1.0,
+                        [1.0, 20.0], [1.0], 2, 0, 0.5, 5e-3, 100, 3, 723, beta=1.5)
+    torch.set_default_dtype(torch.float32)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Fixtures at the sizes bench.py times (VERDICT r3 item 1a): BASELINE configs 2 and 3 - 22 atoms x 100 000 frames, batches of
 # 20 000 (examples/dipeptide/main.ipynb:266) - run by the imported reference.  The trajectory is NOT stored: the fixture keeps
@@ -550,6 +565,10 @@ def main():
         t2, w2 = make_2d_traj(600, seed=11)
         run_regae_eta_cases(core, rnn, dict(pp="identity", traj=t2, w=w2), molecule_case(10, 300, seed=21))
         return
+    if "--regae-depth-only" in sys.argv:
+        t2, w2 = make_2d_traj(600, seed=11)
+        run_regae_depth_cases(core, rnn, dict(pp="identity", traj=t2, w=w2), molecule_case(10, 300, seed=21))
+        return
     if "--regae-only" in sys.argv:   # add the G7 cases without rewriting the other fixtures
         t2, w2 = make_2d_traj(600, seed=11)
         run_regae_cases(core, rnn, dict(pp="identity", traj=t2, w=w2), molecule_case(10, 300, seed=21))
@@ -587,6 +606,7 @@ def main():
     run_regae_eta_cases(core, rnn, id2, mol10)
     run_regae_grad_cases(core, rnn, id2, mol10)
     run_regae_generator_cases(core, rnn, id2, mol10)
+    run_regae_depth_cases(core, rnn, id2, mol10)
     run_big_cases(core, rnn)
 
 
