@@ -31,6 +31,8 @@ PP_ALIGN_CONTIG, PP_PURE_POSITION, PP_SLOT_BATCHED = 1, 2, 4
 # cvf_align_feature_route (include/cvf.h): slice / pipe codes are the base + NI
 K1_ROUTE_SMALL, K1_ROUTE_GATHER_CONTIG, K1_ROUTE_GATHER, K1_ROUTE_CAPTURE_VEC4, K1_ROUTE_CAPTURE = 0, 1, 2, 3, 4
 K1_ROUTE_SLICE, K1_ROUTE_PIPE = 10, 20
+# cvf_metric_route (include/cvf.h): kernel families of cvf_metric_apply[_stats]
+METRIC_IDENTITY, METRIC_FACTORED, METRIC_FEATURES, METRIC_ALIGN, METRIC_PURE, METRIC_ROWS = range(6)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcvf_hip.so")
@@ -43,6 +45,12 @@ class PPDesc(C.Structure):
                 ("atom_align", C.c_void_p), ("atom_slot", C.c_void_p), ("rec_slot", C.c_void_p), ("slot_atom", C.c_void_p), ("n_slot", C.c_int32),
                 ("n_rec_slot", C.c_int32), ("align_w", C.c_void_p), ("mrec", C.c_void_p), ("slot_row", C.c_void_p),
                 ("n_mrec", C.c_int32), ("n_ref", C.c_int32)]
+
+
+class MetricPlan(C.Structure):
+    _fields_ = [("family", C.c_int32), ("F", C.c_int32), ("waves", C.c_int32), ("geo_pre", C.c_int32), ("multi", C.c_int32),
+                ("npb", C.c_int32), ("nets_per_wg", C.c_int32), ("fused", C.c_int32), ("fused_rows", C.c_int32),
+                ("reserved", C.c_int32), ("lds_bytes", C.c_int64), ("grid", C.c_int64)]
 
 
 class MLPDesc(C.Structure):
@@ -81,6 +89,7 @@ _SIGNATURES = {
     "cvf_metric_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvf_metric_apply": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvf_metric_route": (C.c_int, [C.POINTER(PPDesc), C.c_int64, C.c_int, C.c_int, C.POINTER(MetricPlan)]),
     "cvf_metric_stats_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int]),
     "cvf_metric_apply_stats": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EFCfg), C.c_void_p,

@@ -659,9 +659,10 @@ size_t cvf_k1_large_scratch_bytes(const cvf_pp_desc* pp, int64_t B);
 size_t cvf_metric_large_lds(const cvf_pp_desc* pp);
 int cvf_ef_stats_finish(const cvf_ef_cfg* cfg, int n_rows, const double* partial, double* stats, double* loss_vec, double* coef,
                         hipStream_t s);
-int cvf_metric_large_launch(const cvf_pp_desc* pp, int64_t B, const float* aux_tiled, const float* a, int k,
-                            const float* slot_xyz, const double* dense, const float* g_tiled, float* q_tiled, float* e_tiled,
-                            const MetricFuse* fuse, int* fused_rows, hipStream_t s);
+int cvf_metric_rows_plan(const cvf_pp_desc* pp, int64_t B, int k, int with_stats, cvf_metric_plan* P);
+int cvf_metric_rows_launch(const cvf_metric_plan& P, const cvf_pp_desc* pp, int64_t B, const float* aux_tiled, const float* a, int k,
+                           const float* slot_xyz, const double* dense, const float* g_tiled, float* q_tiled, float* e_tiled,
+                           const MetricFuse* fuse, int* fused_rows, hipStream_t s);
 int cvf_ef_stats_finish_impl(const cvf_ef_cfg* cfg, int n_rows, int stat_major, const double* partial, double* stats,
                              double* loss_vec, double* coef, hipStream_t s);
 
@@ -773,40 +774,28 @@ extern "C" int cvf_align_feature_fwd(const cvf_pp_desc* pp, const float* x, int6
   return cvf_check_launch("k1_align_kernel");
 }
 
-static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, const float* a,
-                             int k, const float* g_tiled, float* q_tiled, float* e_tiled, const float* slot_xyz,
-                             const double* dense, const MetricFuse& fuse, bool* fused, void* stream, int* major_rows = nullptr) {
-  if (fused) *fused = false;
-  if (major_rows) *major_rows = 0;   // > 0: the launch left that many rows of [statistic][row] partial sums (large molecules)
-  CVF_REQUIRE(pp && (a || pp->mode == CVF_PP_FACTORED) && g_tiled && q_tiled && e_tiled && B > 0 && k >= 1 && k <= CVF_MAX_NETS,
-              "cvf_metric_apply: bad argument (B=%lld k=%d)", (long long)B, k);
+// Which kernel a metric call launches, with its grid and LDS (cvf_metric_route answers with it, metric_apply_impl launches by it): host
+// arithmetic on the descriptor's counts and flags - no pointer of the descriptor is read but align_w, for NULL.
+static int metric_plan(const cvf_pp_desc* pp, int64_t B, int k, bool with_stats, cvf_metric_plan* P) {
+  *P = cvf_metric_plan{};
+  CVF_REQUIRE(pp && B > 0 && k >= 1 && k <= CVF_MAX_NETS, "cvf_metric_apply: bad argument (B=%lld k=%d)", (long long)B, k);
   const int64_t T = cvf_ntiles(B);
-  hipStream_t s = (hipStream_t)stream;
-  if (pp->mode == CVF_PP_IDENTITY) {
-    hipLaunchKernelGGL(metric_identity_kernel, dim3((unsigned)T, k), dim3(64), 0, s, pp->n_coord, a, k, g_tiled, q_tiled,
-                       e_tiled);
-    return cvf_check_launch("metric_identity_kernel");
-  }
-  if (pp->mode == CVF_PP_FACTORED)   // t = L^T g, q = L t, E = |t|^2 from the records (csrc/metric_factor.hip); stats: two-stage path
-    return cvf_metric_factor_launch(pp, x, B, k, g_tiled, q_tiled, e_tiled, s);
-  if (pp->mode == CVF_PP_FEATURES)   // features of the raw coordinates (csrc/k1_features.hip); stats: two-stage path
-    return cvf_features_metric_launch(pp, x, B, a, k, g_tiled, q_tiled, e_tiled, s);
+  P->waves = P->nets_per_wg = 1;
+  P->grid = T * k;
+  if (pp->mode == CVF_PP_IDENTITY) return P->family = CVF_METRIC_ROUTE_IDENTITY, 0;
+  if (pp->mode == CVF_PP_FACTORED) return P->family = CVF_METRIC_ROUTE_FACTORED, P->waves = P->nets_per_wg = 0, P->grid = 0, 0;   // (csrc/metric_factor.hip decides its own launch)
+  if (pp->mode == CVF_PP_FEATURES) return P->family = CVF_METRIC_ROUTE_FEATURES, P->waves = P->nets_per_wg = 0, P->grid = 0, 0;   // (csrc/k1_features.hip)
   CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
-  CVF_REQUIRE(aux_tiled, "cvf_metric_apply: align mode needs aux");
   CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
               "cvf_metric_apply: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
               kLanePerFrameMaxCoord);
   if (pp->n_coord > kLanePerFrameMaxCoord) {
-    CVF_REQUIRE(slot_xyz && dense && pp->rec_slot && pp->slot_atom && pp->atom_align && pp->n_slot > 0,
-                "cvf_metric_apply: large molecules need the slot tables, slot_xyz (cvf_align_feature_fwd scratch) and "
+    CVF_REQUIRE(pp->n_slot > 0, "cvf_metric_apply: large molecules need the slot tables, slot_xyz (cvf_align_feature_fwd scratch) and "
                 "dense (cvf_metric_dense_tensors)");
-    return cvf_metric_large_launch(pp, B, aux_tiled, a, k, slot_xyz, dense, g_tiled, q_tiled, e_tiled, &fuse, major_rows, s);
+    return cvf_metric_rows_plan(pp, B, k, with_stats, P);
   }
-  CVF_REQUIRE(x, "cvf_metric_apply: align mode needs x");
   const size_t lds = ((size_t)CVF_TILE * (x_tile_stride(pp->n_coord) + pp->n_coord) + tables_dwords(*pp) + pp->n_coord) * sizeof(float);
   CVF_REQUIRE(lds <= 160 * 1024, "frames of %d coordinates do not fit the lane-per-frame metric kernel's LDS", pp->n_coord);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)metric_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   // the three-pass kernel additionally wants every align atom to be a feature atom (atoms 0..n_align-1)
   const bool fast = (pp->flags & (CVF_PP_ALIGN_CONTIG | CVF_PP_PURE_POSITION)) == (CVF_PP_ALIGN_CONTIG | CVF_PP_PURE_POSITION) &&
                     pp->n_align <= pp->n_rec;
@@ -820,16 +809,66 @@ static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, c
     const int wpb = lds_for(k) <= 80 * 1024 ? k : 1;
     const size_t lds_p = lds_for(wpb);
     CVF_REQUIRE(lds_p <= 160 * 1024, "frames of %d coordinates do not fit the lane-per-frame metric kernel's LDS", pp->n_coord);
-    if (lds_p > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)metric_pure_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
+    P->family = CVF_METRIC_ROUTE_PURE;
+    P->waves = P->nets_per_wg = wpb;
+    P->grid = T * (k / wpb);
+    P->lds_bytes = (int64_t)lds_p;
+    P->fused = with_stats && T <= kFuseMaxTiles;
+    P->fused_rows = P->fused ? (int)T : 0;
+    return 0;
+  }
+  P->family = CVF_METRIC_ROUTE_ALIGN;
+  P->lds_bytes = (int64_t)lds;
+  return 0;
+}
+
+extern "C" int cvf_metric_route(const cvf_pp_desc* pp, int64_t B, int k, int with_stats, cvf_metric_plan* plan) {
+  CVF_REQUIRE(plan, "cvf_metric_route: null plan");
+  return metric_plan(pp, B, k, with_stats != 0, plan);
+}
+
+static int metric_apply_impl(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, const float* a,
+                             int k, const float* g_tiled, float* q_tiled, float* e_tiled, const float* slot_xyz,
+                             const double* dense, const MetricFuse& fuse, bool* fused, void* stream, int* major_rows = nullptr) {
+  if (fused) *fused = false;
+  if (major_rows) *major_rows = 0;   // > 0: the launch left that many rows of [statistic][row] partial sums (large molecules)
+  CVF_REQUIRE(pp && (a || pp->mode == CVF_PP_FACTORED) && g_tiled && q_tiled && e_tiled && B > 0 && k >= 1 && k <= CVF_MAX_NETS,
+              "cvf_metric_apply: bad argument (B=%lld k=%d)", (long long)B, k);
+  cvf_metric_plan P;
+  if (const int rc = metric_plan(pp, B, k, fuse.on != 0, &P)) return rc;
+  const int64_t T = cvf_ntiles(B);
+  hipStream_t s = (hipStream_t)stream;
+  switch (P.family) {
+    case CVF_METRIC_ROUTE_IDENTITY:
+      hipLaunchKernelGGL(metric_identity_kernel, dim3((unsigned)T, k), dim3(64), 0, s, pp->n_coord, a, k, g_tiled, q_tiled, e_tiled);
+      return cvf_check_launch("metric_identity_kernel");
+    case CVF_METRIC_ROUTE_FACTORED:   // t = L^T g, q = L t, E = |t|^2 from the records (csrc/metric_factor.hip); stats: two-stage path
+      return cvf_metric_factor_launch(pp, x, B, k, g_tiled, q_tiled, e_tiled, s);
+    case CVF_METRIC_ROUTE_FEATURES:   // features of the raw coordinates (csrc/k1_features.hip); stats: two-stage path
+      return cvf_features_metric_launch(pp, x, B, a, k, g_tiled, q_tiled, e_tiled, s);
+    default: break;
+  }
+  CVF_REQUIRE(aux_tiled, "cvf_metric_apply: align mode needs aux");
+  if (P.family == CVF_METRIC_ROUTE_ROWS) {
+    CVF_REQUIRE(slot_xyz && dense && pp->rec_slot && pp->slot_atom && pp->atom_align && pp->n_slot > 0,
+                "cvf_metric_apply: large molecules need the slot tables, slot_xyz (cvf_align_feature_fwd scratch) and "
+                "dense (cvf_metric_dense_tensors)");
+    return cvf_metric_rows_launch(P, pp, B, aux_tiled, a, k, slot_xyz, dense, g_tiled, q_tiled, e_tiled, &fuse, major_rows, s);
+  }
+  CVF_REQUIRE(x, "cvf_metric_apply: align mode needs x");
+  if (P.family == CVF_METRIC_ROUTE_PURE) {
+    if (P.lds_bytes > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)metric_pure_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes);
     MetricFuse f = fuse;
-    if (T > kFuseMaxTiles) f.on = 0;
-    hipLaunchKernelGGL(metric_pure_kernel, dim3((unsigned)T, k / wpb), dim3(64 * wpb), lds_p, s, *pp, x, B, aux_tiled, a, k,
-                       g_tiled, q_tiled, e_tiled, f);
+    if (!P.fused) f.on = 0;
+    hipLaunchKernelGGL(metric_pure_kernel, dim3((unsigned)T, k / P.nets_per_wg), dim3(64 * P.nets_per_wg), (size_t)P.lds_bytes, s, *pp, x,
+                       B, aux_tiled, a, k, g_tiled, q_tiled, e_tiled, f);
     if (fused) *fused = f.on != 0;
     return cvf_check_launch("metric_pure_kernel");
   }
-  hipLaunchKernelGGL(metric_align_kernel, dim3((unsigned)T, k), dim3(64), lds, s, *pp, x, B, aux_tiled, a, k, g_tiled,
+  if (P.lds_bytes > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)metric_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes);
+  hipLaunchKernelGGL(metric_align_kernel, dim3((unsigned)T, k), dim3(64), (size_t)P.lds_bytes, s, *pp, x, B, aux_tiled, a, k, g_tiled,
                      q_tiled, e_tiled);
   return cvf_check_launch("metric_align_kernel");
 }

@@ -519,12 +519,11 @@ static size_t metric_rows_lds(const cvf_pp_desc* pp, int F, int waves) {
 }
 size_t cvf_metric_large_lds(const cvf_pp_desc* pp) { return metric_rows_lds(pp, 4, 8); }   // the smallest layout
 
-// fuse / fused_rows: see MetricFuse (cvf_metric.hpp); *fused_rows = rows of [statistic][row] partial sums written (0: none)
-int cvf_metric_large_launch(const cvf_pp_desc* pp, int64_t B, const float* aux_tiled, const float* a, int k,
-                            const float* slot_xyz, const double* dense, const float* g_tiled, float* q_tiled, float* e_tiled,
-                            const MetricFuse* fuse, int* fused_rows, hipStream_t s) {
-  if (fused_rows) *fused_rows = 0;
-  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->n_mrec > 0 && pp->n_ref >= pp->n_slot && pp->n_ref < 65536,
+// The rows kernel's half of the metric plan (cvf_metric_route, csrc/k1_align.hip): instance <F, waves, kGeoPre, kMulti>, nets per workgroup,
+// grid, LDS and whether the launch carries the first stage of the batch sums.  Host arithmetic on the descriptor's counts - no pointer of
+// the descriptor is read; the launch below runs by this plan and by nothing else.
+int cvf_metric_rows_plan(const cvf_pp_desc* pp, int64_t B, int k, int with_stats, cvf_metric_plan* P) {
+  CVF_REQUIRE(pp->n_mrec > 0 && pp->n_ref >= pp->n_slot && pp->n_ref < 65536,
               "cvf_metric_apply: large molecules need the record / row tables (mrec, slot_row, n_mrec, n_ref) of cvf_pp_desc");
   constexpr size_t kBudget = 158 * 1024;
   static const int waves = getenv("CVF_METRIC_WAVES") ? atoi(getenv("CVF_METRIC_WAVES")) : 8;   // developer switch: 8 | 16
@@ -554,33 +553,68 @@ int cvf_metric_large_launch(const cvf_pp_desc* pp, int64_t B, const float* aux_t
       }
     }
   }
-  if (getenv("CVF_METRIC_NPB") && k % atoi(getenv("CVF_METRIC_NPB")) == 0 && atoi(getenv("CVF_METRIC_NPB")) > 0) npb = atoi(getenv("CVF_METRIC_NPB"));   // developer switch
-  MetricFuse mf = {};
-  if (fuse != nullptr && fuse->on && groups / k <= 384) {   // one row per frame group, while the finishing launch reads them in one trip
-    mf = *fuse;
-    if (fused_rows) *fused_rows = (int)(groups / k);
+  if (const char* e = getenv("CVF_METRIC_NPB")) {   // developer switch, read on every call; only a divisor of k counts (0 or text: ignored)
+    const int v = atoi(e);
+    if (v > 0 && k % v == 0) npb = v;
   }
+  static const int pre_multi = getenv("CVF_METRIC_PRE") ? atoi(getenv("CVF_METRIC_PRE")) : 7;   // developer switch: 5 (no spills) | 7 (17 spilled registers, but 363 against 416 us at 16 000 frames x 6 nets)
+  P->family = CVF_METRIC_ROUTE_ROWS;
+  P->F = F;
+  P->waves = W;
+  P->multi = W == 16 || npb > 1;
+  P->geo_pre = W == 16 ? 2 : F == 16 ? (npb > 1 && pre_multi != 7 ? 5 : 7) : F == 8 ? 4 : 2;
+  P->npb = npb;
+  P->nets_per_wg = npb;
+  // one row of partial sums per frame group, while the finishing launch reads them in one trip
+  P->fused = with_stats && groups / k <= 384;
+  P->fused_rows = P->fused ? (int)(groups / k) : 0;
+  P->lds_bytes = (int64_t)lds;
+  P->grid = groups / npb;
+  return 0;
+}
+
+// fuse: see MetricFuse (cvf_metric.hpp), taken when the plan says so; *fused_rows = rows of [statistic][row] partial sums written (0: none)
+int cvf_metric_rows_launch(const cvf_metric_plan& P, const cvf_pp_desc* pp, int64_t B, const float* aux_tiled, const float* a, int k,
+                           const float* slot_xyz, const double* dense, const float* g_tiled, float* q_tiled, float* e_tiled,
+                           const MetricFuse* fuse, int* fused_rows, hipStream_t s) {
+  if (fused_rows) *fused_rows = 0;
+  CVF_REQUIRE(pp->mrec && pp->slot_row, "cvf_metric_apply: large molecules need the record / row tables (mrec, slot_row, n_mrec, n_ref) of cvf_pp_desc");
+  MetricFuse mf = {};
+  if (fuse != nullptr && fuse->on && P.fused) {
+    mf = *fuse;
+    if (fused_rows) *fused_rows = P.fused_rows;
+  }
+  const int npb = P.npb;
   auto go = [&](auto kernel) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(groups / npb)), dim3(64 * W), lds, s, *pp, B, aux_tiled, a, k, slot_xyz, dense,
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64 * P.waves), (size_t)P.lds_bytes, s, *pp, B, aux_tiled, a, k, slot_xyz, dense,
                        g_tiled, q_tiled, e_tiled, npb, mf);
   };
-  static const int pre_multi = getenv("CVF_METRIC_PRE") ? atoi(getenv("CVF_METRIC_PRE")) : 7;   // developer switch: 5 (no spills) | 7 (17 spilled registers, but 363 against 416 us at 16 000 frames x 6 nets)
-  if (W == 16) {
-    if (F == 16) go(metric_rows_kernel<16, 16, 2, true>);
-    else if (F == 8) go(metric_rows_kernel<8, 16, 2, true>);
-    else go(metric_rows_kernel<4, 16, 2, true>);
-  } else if (npb > 1) {
-    if (F == 16 && pre_multi == 7) go(metric_rows_kernel<16, 8, 7, true>);
-    else if (F == 16) go(metric_rows_kernel<16, 8, 5, true>);
-    else if (F == 8) go(metric_rows_kernel<8, 8, 4, true>);
-    else go(metric_rows_kernel<4, 8, 2, true>);
-  } else {
-    if (F == 16) go(metric_rows_kernel<16, 8, 7, false>);
-    else if (F == 8) go(metric_rows_kernel<8, 8, 4, false>);
-    else go(metric_rows_kernel<4, 8, 2, false>);
+  const int inst = P.F * 10000 + P.waves * 100 + P.geo_pre * 10 + P.multi;   // <F, waves, kGeoPre, kMulti>
+  switch (inst) {
+    case 161621: go(metric_rows_kernel<16, 16, 2, true>); break;
+    case 81621: go(metric_rows_kernel<8, 16, 2, true>); break;
+    case 41621: go(metric_rows_kernel<4, 16, 2, true>); break;
+    case 160871: go(metric_rows_kernel<16, 8, 7, true>); break;
+    case 160851: go(metric_rows_kernel<16, 8, 5, true>); break;
+    case 80841: go(metric_rows_kernel<8, 8, 4, true>); break;
+    case 40821: go(metric_rows_kernel<4, 8, 2, true>); break;
+    case 160870: go(metric_rows_kernel<16, 8, 7, false>); break;
+    case 80840: go(metric_rows_kernel<8, 8, 4, false>); break;
+    case 40820: go(metric_rows_kernel<4, 8, 2, false>); break;
+    default: CVF_REQUIRE(false, "cvf_metric_apply: no metric_rows_kernel<%d, %d, %d, %d>", P.F, P.waves, P.geo_pre, P.multi);
   }
   return cvf_check_launch("metric_rows_kernel");
+}
+
+// plan and launch in one call (tools/metric_large_probe.hip)
+int cvf_metric_large_launch(const cvf_pp_desc* pp, int64_t B, const float* aux_tiled, const float* a, int k,
+                            const float* slot_xyz, const double* dense, const float* g_tiled, float* q_tiled, float* e_tiled,
+                            const MetricFuse* fuse, int* fused_rows, hipStream_t s) {
+  if (fused_rows) *fused_rows = 0;
+  cvf_metric_plan P = {};
+  if (const int rc = cvf_metric_rows_plan(pp, B, k, fuse != nullptr && fuse->on, &P)) return rc;
+  return cvf_metric_rows_launch(P, pp, B, aux_tiled, a, k, slot_xyz, dense, g_tiled, q_tiled, e_tiled, fuse, fused_rows, s);
 }
 
 extern "C" int64_t cvf_metric_dense_doubles(const cvf_pp_desc* pp) {

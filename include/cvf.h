@@ -266,6 +266,33 @@ int cvf_align_feature_hvp(const cvf_pp_desc* pp, const float* x, int64_t B, cons
 int cvf_metric_apply(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, const float* a,
                      int k, const float* g_tiled, float* q_tiled, float* e_tiled, const float* slot_xyz,
                      const double* dense, void* stream);
+/* Which kernel a cvf_metric_apply (with_stats = 0) or cvf_metric_apply_stats (with_stats = 1) call on B frames and k nets launches,
+ * by the very function the two calls launch by (host arithmetic; no pointer of the descriptor is read, so a descriptor that carries only
+ * its counts and flags is enough).  Returns 0 and fills *plan, or a negative value (and cvf_last_error()) for a descriptor or a batch the
+ * calls refuse.  Fields that do not apply to the family are 0. */
+enum {
+  CVF_METRIC_ROUTE_IDENTITY = 0, /* metric_identity_kernel */
+  CVF_METRIC_ROUTE_FACTORED = 1, /* csrc/metric_factor.hip */
+  CVF_METRIC_ROUTE_FEATURES = 2, /* csrc/k1_features.hip */
+  CVF_METRIC_ROUTE_ALIGN = 3,    /* metric_align_kernel: n_coord <= 192, any feature list, weighted or not */
+  CVF_METRIC_ROUTE_PURE = 4,     /* metric_pure_kernel: n_coord <= 192, CVF_PP_ALIGN_CONTIG | CVF_PP_PURE_POSITION, n_align <= n_rec */
+  CVF_METRIC_ROUTE_ROWS = 5      /* metric_rows_kernel<F, waves, geo_pre, multi>: n_coord > 192 (csrc/metric_large.hip) */
+};
+typedef struct {
+  int32_t family;      /* CVF_METRIC_ROUTE_* */
+  int32_t F;           /* rows: frames per workgroup, 16 | 8 | 4 */
+  int32_t waves;       /* rows: 8 | 16;  pure: nets_per_wg;  align, identity: 1 */
+  int32_t geo_pre;     /* rows: records per lane group whose geometry stays in registers */
+  int32_t multi;       /* rows: the instance that walks npb nets per workgroup */
+  int32_t npb;         /* rows: nets per workgroup (a divisor of k; CVF_METRIC_NPB is read on every call) */
+  int32_t nets_per_wg; /* pure: k (all nets share one staged coordinate tile) or 1;  rows: npb;  else 1 */
+  int32_t fused;       /* with_stats: the launch also writes the first stage of the batch sums */
+  int32_t fused_rows;  /* rows of partial sums it writes: pure - tiles; rows - frame groups of F; 0 when not fused */
+  int32_t reserved;
+  int64_t lds_bytes;   /* dynamic LDS of the launch */
+  int64_t grid;        /* workgroups */
+} cvf_metric_plan;
+int cvf_metric_route(const cvf_pp_desc* pp, int64_t B, int k, int with_stats, cvf_metric_plan* plan);
 /* The same launch with the first stage of K5 (cvf_ef_stats in generator mode, below) folded in: every block reduces its
  * tile's share of the batch sums, one short launch adds the tiles in a fixed order and, when loss_vec != NULL,
  * evaluates cvf_ef_loss.  Shapes the fused stage does not cover run cvf_metric_apply and cvf_ef_stats back to back -
