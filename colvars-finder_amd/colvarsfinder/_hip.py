@@ -182,6 +182,14 @@ _SIGNATURES = {
     "cvf_ef_general_shared_backward": (C.c_int, [C.POINTER(EFCfg), C.POINTER(MLPDesc), C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]),
+    "cvf_ef_general_shared_transfer_supported": (C.c_int, [C.POINTER(MLPDesc), C.c_int]),
+    "cvf_ef_general_shared_transfer_slab_rows": (C.c_int64, [C.POINTER(MLPDesc), C.c_int64, C.c_int]),
+    "cvf_ef_general_shared_transfer_saved_floats": (C.c_int64, [C.POINTER(MLPDesc), C.c_int64, C.c_int]),
+    "cvf_ef_general_shared_transfer_fwd": (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    "cvf_ef_general_shared_transfer_backward": (C.c_int, [C.POINTER(EFCfg), C.POINTER(MLPDesc), C.c_int, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvf_ef_align_fwd": (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PPDesc), C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvf_slab_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(AdamArgs), C.c_void_p]),

@@ -41,7 +41,7 @@ import torch
 import ctypes
 
 from . import _dist, _hip
-from .nn import AutoEncoder, EigenFunctions, RegAutoEncoder, RegModel, mlp_layout  # noqa: F401
+from .nn import AutoEncoder, EigenFunctions, RegAutoEncoder, RegModel, SharedEigenFunctions, mlp_layout  # noqa: F401
 from .nn import _strict_chain_layers
 from .pp import AlignFeatureLayer, FactoredMetric, identity_desc, module_features
 
@@ -269,7 +269,7 @@ class _CVModel(torch.nn.Sequential):
         ``cat(params)`` (per chain and layer: weight, bias), form A for an ``EigenFunctions`` (its nets in their own order: the
         model's outputs), form B for a bare chain.  TypeError with the reason for every other module.  Built from the modules on
         every call - nothing is kept between calls, so parameters trained or replaced in between are the ones read."""
-        if type(nets) is EigenFunctions:
+        if type(nets) in (EigenFunctions, SharedEigenFunctions):   # (a shared trunk: its tensors once per chain in `params`)
             chains = [_strict_chain_layers(net) for net in nets.eigen_funcs]
         elif type(nets) is torch.nn.Sequential:
             chains = [_strict_chain_layers(nets)]
@@ -471,7 +471,9 @@ class _FlatParams:
         model.to(device=device, dtype=torch.float32)
         self.model = model
         self._views = None
-        if isinstance(model, EigenFunctions) and self._init_padded(model, device):
+        # (a shared trunk has one layout: mlp_layout() gives its layers the same offsets for every net, trunk - head 0 - head 1 ..)
+        shared = isinstance(model, SharedEigenFunctions)
+        if isinstance(model, EigenFunctions) and not shared and self._init_padded(model, device):
             return
         lay = mlp_layout(model)
         self.n = lay["n_params"]
@@ -497,7 +499,7 @@ class _FlatParams:
                 d.w_off[i][l], d.b_off[i][l] = wo, bo
         self.desc = d
         # second copy of the weights as MFMA fragments (EigenFunctions nets only; see csrc/cvf_pack.hpp)
-        n_pack = _hip.lib().cvf_ef_pack_floats(d) if isinstance(model, EigenFunctions) else 0
+        n_pack = _hip.lib().cvf_ef_pack_floats(d) if isinstance(model, EigenFunctions) and not shared else 0
         self.packed = torch.zeros(n_pack, device=device, dtype=torch.float32) if n_pack > 0 else None
         self.repack()
 
@@ -941,7 +943,9 @@ class _EFRoute(NamedTuple):
     align_inside: bool   # the forward launch can solve the alignment itself (used when the batch is not already aligned)
     unit_rows: bool      # ef16 transfer mode: the paired front launch that leaves the units' rows of the time-lagged sums
     backward: tuple      # (call name = C function, takes packed, takes w_lag, takes q) of the backward launch
-    shared: Optional[int] = None   # general route of an inner task whose nets share their first `shared` layers (cvf_ef_general_shared_*)
+    # general route of nets that share their first `shared` layers - a SharedEigenFunctions model, or RegAutoEncoderTask's inner task:
+    # cvf_ef_general_shared_* in generator mode, cvf_ef_general_shared_transfer_* in transfer mode
+    shared: Optional[int] = None
 
 
 class _EFWorkspace:
@@ -977,11 +981,13 @@ class _EFWorkspace:
         self._k1_scratch, self.k1_scratch_checked = [None, None], False   # large-molecule alignment scratch, sized on first use
         # hidden activations handed from the forward kernel to the backward kernel (0 floats: shape without hand-off)
         # (the general route, csrc/ef_general.hip: activations, the sweep of g, the tangent chain and the adjoints of every layer)
-        n_saved = (lib.cvf_ef_general_shared_saved_floats(mlp_desc, Tt, ns) if ns is not None else
+        n_saved = (lib.cvf_ef_general_shared_transfer_saved_floats(mlp_desc, Tt, ns) if ns is not None and lag > 0 else
+                   lib.cvf_ef_general_shared_saved_floats(mlp_desc, Tt, ns) if ns is not None else
                    lib.cvf_ef_general_saved_floats(mlp_desc, Tt, lag) if general else
                    lib.cvf_ef16_saved_floats(mlp_desc, Tt) if ef16 else lib.cvf_ef_saved_floats(mlp_desc, Tt))
         self.saved = torch.empty(n_saved, **f32) if n_saved > 0 else None
-        self.slab_rows = (lib.cvf_ef_general_shared_slab_rows(mlp_desc, Tt, ns) if ns is not None else
+        self.slab_rows = (lib.cvf_ef_general_shared_transfer_slab_rows(mlp_desc, Tt, ns) if ns is not None and lag > 0 else
+                          lib.cvf_ef_general_shared_slab_rows(mlp_desc, Tt, ns) if ns is not None else
                           lib.cvf_ef_general_slab_rows(mlp_desc, Tt) if general else lib.cvf_ef_backward_slab_rows(Tt))
         self.slab = torch.empty(self.slab_rows * n_params, **f32)
         # the 16-frame step at this batch size: > 0 - the front launch leaves the units' rows of the batch sums in `scratch` and
@@ -1056,12 +1062,27 @@ class EigenFunctionTask(TrainingTask):
         if _shared_trunk is not None:
             st = _shared_trunk
             if self.lag_idx != 0:
-                raise NotImplementedError("nets with a shared trunk: the transfer-mode shared step is not built (csrc/ef_general.hip)")
+                raise NotImplementedError("nets with a shared trunk: the private _shared_trunk option is generator-mode only; the "
+                                          "transfer-mode shared step takes a nn.SharedEigenFunctions model (csrc/ef_general.hip)")
             self._flat = _SharedTrunkFlat(st["dims"], st["acts"], k, st["n_shared"], self.device)
             self.optimizer = _FusedOptimizer(self._flat, self.optimizer_name, self.learning_rate)
             if not _hip.lib().cvf_ef_general_shared_supported(self._flat.desc, st["n_shared"]):
                 raise NotImplementedError(f"{_hip.lib().cvf_last_error().decode()} (csrc/ef_general.hip: cvf_ef_general_shared_supported)")
             self._n_shared = int(st["n_shared"])
+        elif isinstance(model, SharedEigenFunctions):
+            # a public model on a shared trunk: its parameters alias the flat buffer (trunk once, then head by head), and the step
+            # runs the shared launches of csrc/ef_general.hip - generator mode the existing ones, transfer mode
+            # cvf_ef_general_shared_transfer_* - whatever `general_nets` says: this model has no other route
+            if _dist.world() > 1:
+                raise NotImplementedError("EigenFunctionTask with a SharedEigenFunctions model runs in single-process jobs only: "
+                                          "its data-parallel step (world > 1) has not been verified")
+            self.init_model_and_optimizer()
+            lib, ns = _hip.lib(), int(model.n_shared)
+            ok = (lib.cvf_ef_general_shared_supported if self.lag_idx == 0 else lib.cvf_ef_general_shared_transfer_supported)(self._flat.desc, ns)
+            if not ok:
+                raise NotImplementedError(f"EigenFunctionTask with a SharedEigenFunctions model on MI355X: {lib.cvf_last_error().decode()} "
+                                          "(csrc/ef_general.hip: efg_why_shared)")
+            self._n_shared = ns
         else:
             self.init_model_and_optimizer()
         # general_nets: shapes without a kernel instance run the per-layer launches of csrc/ef_general.hip (shapes WITH an
@@ -1173,6 +1194,9 @@ class EigenFunctionTask(TrainingTask):
     def get_reordered_eigenfunctions(self, model, cvec):
         """core.py:356-370: deep copy whose module list is re-ordered by ``cvec``."""
         new = copy.deepcopy(model)
+        if isinstance(model, SharedEigenFunctions):   # the copy's own chains re-ordered: they keep sharing the copy's trunk
+            new.eigen_funcs = torch.nn.ModuleList([new.eigen_funcs[int(i)] for i in cvec])
+            return new
         new.eigen_funcs = torch.nn.ModuleList([copy.deepcopy(model.eigen_funcs[int(i)]) for i in cvec])
         return new
 
@@ -1421,6 +1445,9 @@ class EigenFunctionTask(TrainingTask):
         if inside:
             self._call("cvf_ef_align_fwd", lib.cvf_ef_align_fwd, fl.desc, P(fl.theta), P(fl.packed), P(ws.feat), self._pp, P(X),
                        P(X_lag), ws.B, P(ws.y), P(ws.saved), s)
+        elif self._route.shared is not None and not gen:
+            self._call("cvf_ef_general_shared_transfer_fwd", lib.cvf_ef_general_shared_transfer_fwd, fl.desc, self._route.shared,
+                       P(fl.theta), P(ws.feat), ws.Tt, P(ws.y), P(ws.saved), s)
         elif self._route.shared is not None:
             self._call("cvf_ef_general_shared_fwd", lib.cvf_ef_general_shared_fwd, fl.desc, self._route.shared, P(fl.theta), P(ws.feat),
                        ws.Tt, P(ws.y), P(ws.g), P(ws.saved), s)
@@ -1442,7 +1469,11 @@ class EigenFunctionTask(TrainingTask):
         that sums the per-block partial gradients applies the Adam update in the same launch."""
         lib, fl, P = _hip.lib(), self._flat, _hip.ptr
         name, packed, lagged, q = self._route.backward
-        if self._route.shared is not None:   # (generator mode: no w_lag; n_shared follows the description)
+        if self._route.shared is not None and self.lag_idx != 0:   # (transfer mode: no q)
+            self._call("cvf_ef_general_shared_transfer_backward", lib.cvf_ef_general_shared_transfer_backward, self._cfg, fl.desc,
+                       self._route.shared, P(fl.theta), ws.B, P(w), P(w_lag), P(ws.feat_in), P(ws.y), P(ws.coef), P(ws.slab),
+                       P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())
+        elif self._route.shared is not None:   # (generator mode: no w_lag; n_shared follows the description)
             self._call("cvf_ef_general_shared_backward", lib.cvf_ef_general_shared_backward, self._cfg, fl.desc, self._route.shared,
                        P(fl.theta), ws.B, P(w), P(ws.feat_in), P(ws.y), P(ws.q), P(ws.coef), P(ws.slab),
                        P(self.optimizer.step_count) if advance else None, P(ws.saved), _hip.stream())

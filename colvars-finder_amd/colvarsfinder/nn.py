@@ -128,6 +128,42 @@ class EigenFunctions(torch.nn.Module):
         return torch.cat([net(inp) for net in self.eigen_funcs], dim=1)
 
 
+class SharedEigenFunctions(EigenFunctions):
+    """``k`` scalar eigenfunctions on ONE trunk (the VAMPnets / SRV form ``[d_r, H, .., H, k]``; not in the reference).
+
+    ``trunk_dims = [d_r, h_1, .., h_m]``, ``m >= 1``: Linear layers shared by all ``k`` eigenfunctions, each followed by
+    ``activation``.  ``head_dims = [h_m, .., 1]``, at least one Linear layer: ``k`` independent copies, ``activation`` between
+    their layers and none after the last.  ``head_dims = [h_m, 1]`` is the classic multi-output net.
+
+    ``eigen_funcs[i]`` is the chain trunk -> head ``i`` as a ``create_sequential_nn``-shaped ``Sequential`` whose first ``m``
+    Linear layers are the SAME module objects for every ``i``: ``parameters()`` yields every trunk tensor once (trunk, head 0,
+    head 1, ..), ``state_dict()`` names it under every ``eigen_funcs.i`` (the keys of an ``EigenFunctions`` of the full chain),
+    a deep copy keeps the sharing, and ``get_params_of_cv(i)`` returns the trunk's and head ``i``'s parameters.
+    ``n_shared = m`` is what the kernels are told (csrc/ef_general.hip: cvf_ef_general_shared_*)."""
+
+    def __init__(self, trunk_dims, head_dims, k, activation=torch.nn.Tanh()):
+        torch.nn.Module.__init__(self)
+        trunk_dims, head_dims = list(trunk_dims), list(head_dims)
+        assert len(trunk_dims) >= 2, "the trunk needs at least one Linear layer"
+        assert len(head_dims) >= 2, "a head needs at least one Linear layer"
+        assert head_dims[0] == trunk_dims[-1], "output dimension of the trunk and input dimension of the heads do not match!"
+        assert head_dims[-1] == 1, "each eigenfunction must be scalar-valued"
+        assert k >= 1, "at least one eigenfunction is needed"
+        self.n_shared = m = len(trunk_dims) - 1
+        trunk = [torch.nn.Linear(a, b) for a, b in zip(trunk_dims[:-1], trunk_dims[1:])]
+        n = m + len(head_dims) - 1
+        nets = []
+        for _ in range(k):
+            net = torch.nn.Sequential()
+            head = [torch.nn.Linear(a, b) for a, b in zip(head_dims[:-1], head_dims[1:])]
+            for pos, lin in enumerate(trunk + head, start=1):
+                net.add_module(str(pos), lin)
+                if pos < n:
+                    net.add_module(f"activation {pos}", activation)
+            nets.append(net)
+        self.eigen_funcs = torch.nn.ModuleList(nets)
+
+
 # ----------------------------------------------------------------------------------------------
 # Flat-buffer description of a model for the HIP kernels (not part of the reference API)
 # ----------------------------------------------------------------------------------------------

@@ -33,7 +33,22 @@
 //   dW_l, l < n_shared = sum over the nets of the per-net products: one launch with one net in grid z, whose block walks, per
 //                      tile, the nets 0..k-1 in order into one accumulator and writes the slab entry once, at the shared offset.
 // n_shared = 0 is the launch list of the plain entries.
+//
+// THE SAME IN TRANSFER MODE (cvf_ef_general_shared_transfer_*; n_tiles = 2T: the frames, then their lagged partners).  There is no
+// tangent chain and no gamma term, so the only per-net quantity of a shared layer is its adjoint, and the adjoint that enters the
+// trunk is a sum over the nets - the trunk back-propagates ONCE:
+//   heads            zbar_l, l >= n_shared, per net (EPI_BWD_TR, grid z = k), as on the plain route;
+//   the boundary     zbar_{ns-1} = sigma'(h_{ns-1}) .* sum_i W_{ns,i}^T zbar_{ns,i}: ONE launch (eftr_trunk_sum_kernel, csrc/ef_general_sum.hip) whose block
+//                    walks the nets 0..k-1 in that order into one accumulator and writes one image;
+//                    n_shared = NH (the heads are output rows only): the sum belongs to the top step,
+//                    zbar_{NH-1} = sigma'(h_{NH-1}) .* sum_i alpha_i W_{NH,i}^T (eftr_top_sum_kernel);
+//   below it         one chain, grid z = 1 (efg_layer_kernel, EPI_BWD_TR, the shared weights in place);
+//   dW_l, l < ns     ONE product from the summed zbar_l (nets = 1, grid z = 1), written once at the shared offset of the slab row.
+// `saved` = 64 n_tiles (sum_{l<ns} d_l + k (sum_{l>=ns} d_l + 2 max_l d_l + 1)) floats over the hidden widths d_l: the trunk's h_l
+// once, the heads' h_l per net, two ping-pong images of zbar (a shared layer's single image lies in the same two), alpha.
+// (The two summing kernels carry their own prefix: the four efg_ kernels above are unchanged, in code and in resources.)
 #include "cvf_gemm64.hpp"
+#include "ef_general_sum.hpp"
 
 namespace {
 
@@ -196,9 +211,34 @@ __global__ __launch_bounds__(256) void efg_top_kernel(const cvf_mlp_desc mlp, co
   }
 }
 
+// ---- transfer mode with a shared trunk: the two launches that sum over the nets.  The boundary launch lives in
+// csrc/ef_general_sum.hip (eftr_launch_trunk_sum): compiled into this code object it changes the register allocation of
+// efg_layer_kernel (53 -> 60 VGPRs), in a code object of its own it leaves the four kernels above as they were.
+// n_shared = NH: zbar_{NH-1}[j] = sigma'(h_{NH-1}[j]) (sum_net alpha_net W_{NH,net}[j]), the nets in the order 0..nets-1
+struct EftrTopArgs {
+  int H, act, nets;
+  EfgView h, z, alpha;   // h, z: one image each; alpha per net
+};
+
+__global__ __launch_bounds__(256) void eftr_top_sum_kernel(const cvf_mlp_desc mlp, const float* __restrict__ theta, EftrTopArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  float al[CVF_MAX_NETS];
+#pragma unroll
+  for (int i = 0; i < CVF_MAX_NETS; ++i) al[i] = i < a.nets ? at(a.alpha, i, tile, 0)[lane] : 0.0f;
+  for (int j = wave; j < a.H; j += 4) {
+    float s = al[0] * theta[mlp.w_off[0][mlp.n_layers - 1] + j];
+#pragma unroll
+    for (int i = 1; i < CVF_MAX_NETS; ++i)
+      if (i < a.nets) s += al[i] * theta[mlp.w_off[i][mlp.n_layers - 1] + j];
+    at(a.z, 0, tile, j)[lane] = cvf_act_d1(a.act, at(a.h, 0, tile, j)[lane]) * s;
+  }
+}
+
 // ---- the `saved` buffer.  Generator mode (n_tiles = T): per hidden layer h_l, u_l (-> d_l), zdot_l (-> zbar_l), then alpha,
 // gamma.  Transfer mode (n_tiles = 2T): h_l per hidden layer, two ping-pong images of zbar (widest layer), alpha.
-// Every image is [net][tile][width][64]; with a shared trunk the h_l of the shared layers are [tile][width][64], once.
+// Every image is [net][tile][width][64]; with a shared trunk the h_l of the shared layers are [tile][width][64], once (and so is,
+// in transfer mode, a shared layer's summed zbar, inside the ping-pong image of its parity).
 struct EfgLayout {
   int64_t h[CVF_MAX_LAYERS], u[CVF_MAX_LAYERS], z[CVF_MAX_LAYERS], zb[2], alpha, gamma, total;
 };
@@ -394,7 +434,8 @@ int efg_fwd(const cvf_mlp_desc* mlp, int ns, const float* theta, const float* fe
   return 0;
 }
 
-// the launches of cvf_ef_general_backward; ns as efg_fwd (ns > 0: generator mode)
+// the launches of cvf_ef_general_backward; ns as efg_fwd (transfer mode with ns > 0: the adjoints of the shared layers are summed
+// over the nets - one image, one chain, one weight-gradient product per layer)
 int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const float* theta, int64_t B, const float* w,
                  const float* w_lag, const float* feat_tiled, const float* y_tiled, const float* q_tiled, const double* coef,
                  float* slab, int32_t* step_count, float* saved, hipStream_t s) {
@@ -407,7 +448,9 @@ int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const f
   const EfgView qv{(float*)q_tiled, (int64_t)k * D * CVF_TILE, (int64_t)D * CVF_TILE};
   auto H = [&](int l) { return img(saved, L.h[l], nt, mlp->dims[l + 1], l < ns); };
   auto U = [&](int l) { return img(saved, L.u[l], nt, mlp->dims[l + 1]); };
-  auto Z = [&](int l) { return gen ? img(saved, L.z[l], nt, mlp->dims[l + 1]) : img(saved, L.zb[l & 1], nt, mlp->dims[l + 1]); };
+  auto Z = [&](int l) {
+    return gen ? img(saved, L.z[l], nt, mlp->dims[l + 1]) : img(saved, L.zb[l & 1], nt, mlp->dims[l + 1], l < ns);
+  };
   const EfgView alpha = img(saved, L.alpha, nt, 1), gamma = img(saved, L.gamma, nt, 1);
 
   // the tangent chain along q: zdot_0 = W_0 q, zdot_l = W_l (sigma'(h_{l-1}) .* zdot_{l-1})
@@ -453,13 +496,17 @@ int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const f
         g.act_b2 = mlp->act[l - 1];
       }
     }
-    g.nets = l < ns ? k : 1;   // a shared layer: one block sums the nets' products
+    g.nets = l < ns && gen ? k : 1;   // a shared layer: one block sums the nets' products (transfer mode: zbar_l is the sum already)
     const int nb = ((g.Mo + 63) / 64) * ((g.Ki + 1 + 63) / 64);
     hipLaunchKernelGGL(efg_wgrad_kernel, dim3((unsigned)R, (unsigned)nb, l < ns ? 1 : k), dim3(256), 0, s, *mlp, g, slab);
     return cvf_check_launch("efg_wgrad_kernel");
   };
   if (wgrad(NH)) return -1;
-  {
+  if (!gen && ns == NH) {   // the heads are output rows: the sum over the nets in the top step
+    EftrTopArgs t = {mlp->dims[NH], mlp->act[NH - 1], k, H(NH - 1), Z(NH - 1), alpha};
+    hipLaunchKernelGGL(eftr_top_sum_kernel, dim3((unsigned)nt), dim3(256), 0, s, *mlp, theta, t);
+    if (cvf_check_launch("eftr_top_sum_kernel")) return -1;
+  } else {
     EfgTopArgs t = {mlp->dims[NH], mlp->act[NH - 1], gen ? 1 : 0, H(NH - 1), Z(NH - 1), gen ? U(NH - 1) : EfgView{}, alpha, gamma};
     hipLaunchKernelGGL(efg_top_kernel, dim3((unsigned)nt, k), dim3(256), 0, s, *mlp, theta, t);
     if (cvf_check_launch("efg_top_kernel")) return -1;
@@ -467,6 +514,11 @@ int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const f
   for (int l = NH - 1; l >= 0; --l) {
     if (wgrad(l)) return -1;
     if (l == 0) break;
+    if (!gen && l == ns) {   // the trunk boundary: zbar_{ns-1} = sigma'(h_{ns-1}) .* sum_i W_{ns,i}^T zbar_{ns,i}, one image
+      EftrSumArgs b = {l, mlp->dims[l], mlp->dims[l + 1], k, mlp->act[l - 1], Z(l).p, Z(l).ns, Z(l - 1).p, H(l - 1).p};
+      if (eftr_launch_trunk_sum(mlp, theta, b, nt, s)) return -1;
+      continue;
+    }
     // zbar_{l-1} = sigma'(h_{l-1}) .* (W_l^T zbar_l) [+ gamma sigma''(h_{l-1}) .* zdot_{l-1} .* u_{l-1};  d_{l-1}]
     EfgLayerArgs a = layer_args(l, 1, mlp->dims[l], mlp->dims[l + 1], 0, gen ? EPI_BWD_GEN : EPI_BWD_TR);
     a.x = Z(l);
@@ -477,7 +529,7 @@ int efg_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int ns, const f
       a.eu = U(l - 1);
       a.gam = gamma;
     }
-    if (launch_layer(mlp, theta, a, nt, s, k)) return -1;
+    if (launch_layer(mlp, theta, a, nt, s, !gen && l < ns ? 1 : k)) return -1;   // (below the boundary: one chain)
   }
   return 0;
 }
@@ -549,5 +601,50 @@ extern "C" int cvf_ef_general_shared_backward(const cvf_ef_cfg* cfg, const cvf_m
               "cvf_ef_general_shared_backward: bad argument");
   CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_shared_backward: cfg.k != number of nets");
   return efg_backward(cfg, mlp, n_shared, theta, B, w, nullptr, feat_tiled, y_tiled, q_tiled, coef, slab, step_count, saved,
+                      (hipStream_t)stream);
+}
+
+// ---- the same in transfer mode: the shared layers' adjoint summed over the nets, the trunk back-propagated once
+extern "C" int cvf_ef_general_shared_transfer_supported(const cvf_mlp_desc* mlp, int n_shared) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  if (why != nullptr) {
+    cvf_set_error("cvf_ef_general_shared_transfer: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_ef_general_shared_transfer_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared) {
+  if (efg_why_shared(mlp, n_shared) != nullptr) return 0;
+  return g64_rows(mlp, n_tiles);
+}
+
+extern "C" int64_t cvf_ef_general_shared_transfer_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared) {
+  if (efg_why_shared(mlp, n_shared) != nullptr || n_tiles < 1) return 0;
+  return efg_layout(mlp, n_tiles, false, n_shared).total;
+}
+
+extern "C" int cvf_ef_general_shared_transfer_fwd(const cvf_mlp_desc* mlp, int n_shared, const float* theta, const float* feat_tiled,
+                                                  int64_t n_tiles, float* y_tiled, float* saved, void* stream) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_shared_transfer_fwd: %s", why);
+  CVF_REQUIRE(theta && feat_tiled && y_tiled && saved && n_tiles > 0, "cvf_ef_general_shared_transfer_fwd: bad argument");
+  return efg_fwd(mlp, n_shared, theta, feat_tiled, n_tiles, y_tiled, nullptr, saved, (hipStream_t)stream);
+}
+
+extern "C" int cvf_ef_general_shared_transfer_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int n_shared, const float* theta,
+                                                       int64_t B, const float* w, const float* w_lag, const float* feat_tiled,
+                                                       const float* y_tiled, const double* coef, float* slab, int32_t* step_count,
+                                                       float* saved, void* stream) {
+  const char* why = efg_why_shared(mlp, n_shared);
+  CVF_REQUIRE(why == nullptr, "cvf_ef_general_shared_transfer_backward: %s", why);
+  CVF_REQUIRE(cfg, "cvf_ef_general_shared_transfer_backward: bad argument");
+  CVF_REQUIRE(cfg->lag_idx != 0, "cvf_ef_general_shared_transfer_backward: a generator-mode cfg (lag_idx = 0) belongs to "
+                                 "cvf_ef_general_shared_backward");
+  CVF_REQUIRE(w_lag, "cvf_ef_general_shared_transfer_backward: transfer mode needs w_lag");
+  CVF_REQUIRE(theta && w && feat_tiled && y_tiled && coef && slab && saved && B > 0,
+              "cvf_ef_general_shared_transfer_backward: bad argument");
+  CVF_REQUIRE(cfg->k == mlp->n_nets, "cvf_ef_general_shared_transfer_backward: cfg.k != number of nets");
+  return efg_backward(cfg, mlp, n_shared, theta, B, w, w_lag, feat_tiled, y_tiled, nullptr, coef, slab, step_count, saved,
                       (hipStream_t)stream);
 }

@@ -520,7 +520,7 @@ int cvf_ef_general_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, cons
  *                                      else per net.
  *  cvf_ef_general_shared_fwd         : replaces self.model(...) at core.py:996 and the autograd.grad of core.py:1009 (and
  *                                      core.py:899,903 of the penalty): y_tiled [n_tiles][k][64], g_tiled [n_tiles][k][d0][64]
- *                                      (required: without it the call would be the transfer-mode step, which is not built).
+ *                                      (required: without it the call would be the transfer-mode step, which has entries of its own, below).
  *  cvf_ef_general_shared_backward    : replaces loss.backward() at core.py:1102 for these terms: slab rows of the flat gradient
  *                                      [rows][n_params], each shared entry written once (follow with cvf_slab_reduce).  A cfg
  *                                      with lag_idx != 0 is refused by name.
@@ -533,6 +533,35 @@ int cvf_ef_general_shared_fwd(const cvf_mlp_desc* mlp, int n_shared, const float
 int cvf_ef_general_shared_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int n_shared, const float* theta, int64_t B,
                                    const float* w, const float* feat_tiled, const float* y_tiled, const float* q_tiled,
                                    const double* coef, float* slab, int32_t* step_count, float* saved, void* stream);
+
+/* --- The shared trunk in TRANSFER mode (csrc/ef_general.hip): colvarsfinder.nn.SharedEigenFunctions under
+ * EigenFunctionTask(lag_tau > 0) - the loss of core.py:403-457 on one trunk with k heads.  The description and its limits are those
+ * of cvf_ef_general_shared_supported; n_tiles = 2T (the frames' tiles, then their lagged partners'), as on the plain general route.
+ * Transfer mode has no tangent chain and no gamma term, so the adjoint that enters the trunk is the sum over the nets: the heads
+ * run per net down to layer n_shared, ONE launch sums sigma'(h_{ns-1}) .* sum_i W_{ns,i}^T zbar_{ns,i} (the nets walked in the order
+ * 0..k-1 into one accumulator; n_shared = n_layers - 1: sigma' .* sum_i alpha_i W_{NH,i}^T in the top step), the trunk
+ * back-propagates once, and every weight gradient of a shared layer is one product from the summed adjoint, written once at the
+ * shared offset of the slab row.  No atomics: the same inputs give the same bits.  n_shared = 0 is, launch for launch,
+ * cvf_ef_general_fwd (g_tiled = NULL) / cvf_ef_general_backward (lag_idx != 0).
+ *  cvf_ef_general_shared_transfer_supported   : 1, or 0 with the reason in cvf_last_error().
+ *  cvf_ef_general_shared_transfer_slab_rows   : as cvf_ef_general_slab_rows.
+ *  cvf_ef_general_shared_transfer_saved_floats: floats of `saved` = 64 n_tiles (sum_{l<ns} d_l + k (sum_{l>=ns} d_l + 2 max_l d_l + 1))
+ *                                               over the hidden widths d_l: the trunk's h_l once (not k times), the heads' h_l per
+ *                                               net, two ping-pong images of the adjoint, alpha.
+ *  cvf_ef_general_shared_transfer_fwd         : replaces self.model(...) at core.py:403,414: y_tiled [n_tiles][k][64].
+ *  cvf_ef_general_shared_transfer_backward    : replaces loss.backward() at core.py:517 (cvf_ef_stats between the two calls, follow
+ *                                               with cvf_slab_reduce); step_count as cvf_ef_backward.  Refused by name: a
+ *                                               generator-mode cfg (lag_idx == 0), a missing w_lag.
+ * The calls return a negative code (0 for the sizes), with the reason in cvf_last_error(), before any launch. */
+int cvf_ef_general_shared_transfer_supported(const cvf_mlp_desc* mlp, int n_shared);
+int64_t cvf_ef_general_shared_transfer_slab_rows(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared);
+int64_t cvf_ef_general_shared_transfer_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles, int n_shared);
+int cvf_ef_general_shared_transfer_fwd(const cvf_mlp_desc* mlp, int n_shared, const float* theta, const float* feat_tiled,
+                                       int64_t n_tiles, float* y_tiled, float* saved, void* stream);
+int cvf_ef_general_shared_transfer_backward(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, int n_shared, const float* theta,
+                                            int64_t B, const float* w, const float* w_lag, const float* feat_tiled,
+                                            const float* y_tiled, const double* coef, float* slab, int32_t* step_count,
+                                            float* saved, void* stream);
 
 /* --- AutoEncoder: weighted reconstruction loss and its parameter gradient in one pass
  * (core.py:664-666,708).  feat_rows [n][d0] row-major (the precomputed feature
