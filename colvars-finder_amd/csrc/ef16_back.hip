@@ -21,11 +21,25 @@ struct Back16Args {
   int64_t T;              // transfer-operator mode: tiles 0..T-1 hold the frames, T..2T-1 their lagged partners
   const float* w_lag;     // ... and the partners' weights
 };
+// What the kernel reads of cvf_mlp_desc (by value the descriptor is 1 KB of kernel arguments whose offset tables are loaded
+// piecemeal into a scalar file that is too small for them).  The host has checked that every net is laid out the regular way -
+// per layer the weight [out, in], then the bias, layer after layer - so that an offset inside a net is a constant of (H, NH)
+// plus H * D, and a block needs ONE scalar of the record's table: its own net's base.
+struct Back16Nets {
+  int D;                       // dims[0]
+  int n_params;
+  int base[CVF_MAX_NETS];      // w_off[net][0]
+};
+// offsets of layer l = 0..NH (NH: the 1 x H output layer) from the net's base; hd = H * D
+template <int H, int NH>
+__host__ __device__ constexpr int net_w_off(int l, int hd) { return l == 0 ? 0 : hd + H + (l - 1) * (H * H + H); }
+template <int H, int NH>
+__host__ __device__ constexpr int net_b_off(int l, int hd) { return net_w_off<H, NH>(l, hd) + (l == 0 ? hd : l == NH ? H : H * H); }
 
 // GEN: generator mode (tangent chain, second operands).  !GEN: transfer-operator mode - the plain backward pass of y and y'
 // with the coefficients of the time-lagged loss (as ef_bwd_mfma_kernel's lag_idx > 0 branch), no tangent chain.
 template <int H, int NH, bool MULTI, bool GEN>
-__global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_mlp_desc mlp, const float* __restrict__ theta,
+__global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back16Nets nets, const float* __restrict__ theta,
                                                             const float* __restrict__ packed, const float* __restrict__ w,
                                                             const float* __restrict__ feat, const float* __restrict__ y_tiled,
                                                             const float* __restrict__ q_tiled, const double* __restrict__ coef,
@@ -46,21 +60,36 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   float* SA2 = SA1 + H * kPitch;
   float* SB1 = SA2 + H * kPitch;
   float* SB2 = SB1 + (H + 1) * kPitch;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform values in SGPRs (see the front kernel)
-  const int col = lane & 15, q = lane >> 4, row16 = col, r0 = 4 * q;
-  const int fo = 16 * wave + col;   // this lane's frame of the tile
-  const int rowf = 4 * col + q;     // the row whose strip sum this lane keeps (strip_rows: hid_feature(col >> 2, col & 3, q))
-  const int net = blockIdx.y, k = args.k, D = mlp.dims[0];
-  const int CT1 = (D + 1 + 15) / 16;
-  // A last column tile of the first layer [f ; 1] with 1..4 useful columns (D = 66: features 64, 65 and the bias) does not go to
-  // the matrix cores: its columns are `ncol` strips of H sums over the frames (strip_rows).  CTM column tiles stay matrix tiles.
-  const int c0 = 16 * (CT1 - 1), nfeat = D - c0, ncol = nfeat + 1;   // the last tile's first column, its features, its columns
-  const bool strip = ncol <= 4;
-  const int CTM = strip ? CT1 - 1 : CT1;
-  const int gbase = mlp.w_off[net][0];
-  const int gspan = mlp.b_off[net][NH] + 1 - gbase;
-  float* out = slab + (int64_t)blockIdx.x * mlp.n_params + gbase;   // this block's slab row, this net's span
+  int lane = tid & 63, col, q, row16, r0, fo, rowf;
+  auto derive_lane = [&]() {
+    col = lane & 15, q = lane >> 4, row16 = col, r0 = 4 * q;
+    fo = 16 * wave + col;   // this lane's frame of the tile
+    rowf = 4 * col + q;     // the row whose strip sum this lane keeps (strip_rows: hid_feature(col >> 2, col & 3, q))
+  };
+  derive_lane();
+  static_assert(H % 4 == 0, "a lane's four rows of a gradient tile are inside the layer together (emit_tile)");
+  const int net = blockIdx.y;
+  int k = args.k;
+  // What follows from D.  A last column tile of the first layer [f ; 1] with 1..4 useful columns (D = 66: features 64, 65 and the
+  // bias) does not go to the matrix cores: its columns are `ncol` strips of H sums over the frames (strip_rows).  CTM column tiles
+  // stay matrix tiles.  (Not const: the multi-tile form derives them again for every tile, see the tile loop.)
+  int D = nets.D, HD, c0, nfeat, ncol, CTM;   // c0, nfeat, ncol: the last tile's first column, its features, its columns
+  bool strip;
+  PackLayout L;
+  auto derive = [&]() {
+    const int CT1 = (D + 1 + 15) / 16;
+    HD = H * D;
+    c0 = 16 * (CT1 - 1), nfeat = D - c0, ncol = nfeat + 1;
+    strip = ncol <= 4;
+    CTM = strip ? CT1 - 1 : CT1;
+    L = pack_layout(H, NH, D);
+  };
+  derive();
+  const int gbase = nets.base[net];
+  const int gspan = net_b_off<H, NH>(NH, HD) + 1;
+  float* out = slab + (int64_t)blockIdx.x * nets.n_params + gbase;   // this block's slab row, this net's span
 
   {   // (16-byte LDS writes: kRows * kPitch is a multiple of 4)
     static_assert((kRows * kPitch) % 4 == 0, "IMG is zeroed in 16-byte pieces");
@@ -69,17 +98,14 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   }
   if (MULTI)
     for (int i = tid; i < gspan; i += NT) GI[i] = 0.0f;
-  // (LDS only: __syncthreads() would also wait for the coefficient / last-layer loads requested above - a whole global round trip
-  //  at the head of every block before the tile's own requests go out; stamped prologue 4.4 k cycles)
+  // (LDS only: __syncthreads() would also wait for every global load requested so far - a whole global round trip at the head of
+  //  every block before the tile's own requests go out; stamped prologue 4.4 k cycles)
   lds_barrier();
   if (tid < 64) SB1[H * kPitch + tid] = 1.0f;  // bias column of [h ; 1]  (row H of SB2 stays 0)
 
-  const PackLayout L = pack_layout(H, NH, D);
   const URows pk = urows(packed + (int64_t)net * L.per_net, L.per_net, lane);   // this net's fragments (see URows)
   float wl[RT][4];
-  load_hid_const_u<H>(urows(theta + mlp.w_off[net][NH], H, q), wl);
-  const double gS1n = coef[net], gEtn = coef[k + k * k + net];
-  const double gS1ln = GEN ? 0.0 : coef[2 * k + k * k + net], gS2ln = GEN ? 0.0 : coef[3 * k + k * k + net];
+  load_hid_const_u<H>(urows(theta + gbase + net_w_off<H, NH>(NH, HD), H, q), wl);
   const float one[1] = {1.0f};
 
   // a finished 16x16 tile of layer `l` (rows = outputs, columns = inputs + bias).  Every tile of the gradient is produced
@@ -91,21 +117,24 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
   //  the four offsets of every call site are hoisted out of the layer loops, spilled, and reloaded behind a wait for ALL
   //  outstanding memory operations - i.e. for the previous store's completion, eight times per tile)
   const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, gspan * 4, 0x00020000);
-  auto emit_tile = [&](int l, int n_out, int n_in, int rt, int ct, const f32x4& acc) {
-    const int wo = mlp.w_off[net][l] - gbase, bo = mlp.b_off[net][l] - gbase;
+  // A lane's four entries of a tile are rows ob .. ob + 3 of ONE column: they are inside the layer together (H % 4 == 0) and a constant
+  // stride apart - a row of the weights, or one float in the bias column.  So a tile costs one offset and one stride, not four of each.
+  constexpr int kDead = 0x7fff0000;   // (+ 3 strides stays positive)
+  auto emit_tile = [&](int l, int n_in, int rt, int ct, const f32x4& acc) {
+    const int wo = net_w_off<H, NH>(l, HD), bo = net_b_off<H, NH>(l, HD);
     const int i = 16 * ct + row16;
     int ob = 16 * rt + r0;
     asm volatile("" : "+v"(ob));
+    const bool isb = i == n_in, live = ob < H && i <= n_in;
+    const int idx0 = isb ? bo + ob : wo + ob * n_in + i, stride = isb ? 1 : n_in;
+    const int off0 = live ? idx0 * 4 : kDead;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int o = ob + r;
-      const bool isw = o < n_out && i < n_in, isb = o < n_out && i == n_in;
-      const int idx = isw ? wo + o * n_in + i : bo + (o < n_out ? o : 0);
       const float av = acc[r];   // (by value: __builtin_bit_cast applied to the vector-element lvalue acc[r] read element 0 four times)
       if (MULTI) {
-        if (isw || isb) GI[idx] += av;
+        if (live) GI[idx0 + r * stride] += av;
       } else {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, av), out_rs, (isw || isb) ? idx * 4 : 0x7ffffff0, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, av), out_rs, off0 + r * stride * 4, 0, 0);
       }
     }
   };
@@ -122,7 +151,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
     if (MULTI) {
       if (live) GI[idx] += v;
     } else {
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), out_rs, live ? idx * 4 : 0x7ffffff0, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), out_rs, live ? idx * 4 : kDead, 0, 0);
     }
   };
   // the last layer's H weights and bias from the four waves' partials in PART (one wave; behind a block barrier)
@@ -132,7 +161,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
       asm volatile("" : "+v"(i));
       const bool live = i <= H;
       const float v = strip_total(PART + (live ? i : H), H + 1);
-      emit_entry(live, i < H ? mlp.w_off[net][NH] - gbase + i : mlp.b_off[net][NH] - gbase, v);
+      emit_entry(live, i < H ? net_w_off<H, NH>(NH, HD) + i : net_b_off<H, NH>(NH, HD), v);
     }
   };
   // the first layer's strip columns from the partials in SB1 ([wave][row][4 columns]; behind a block barrier)
@@ -143,13 +172,34 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
       const int o = e >> 2, c = e & 3;
       const bool live = o < H && c < ncol;
       const float v = strip_total(SB1 + (o < H ? e : 0), 4 * H);
-      emit_entry(live, c < nfeat ? mlp.w_off[net][0] - gbase + o * D + c0 + c : mlp.b_off[net][0] - gbase + o, v);
+      emit_entry(live, c < nfeat ? o * D + c0 + c : HD + o, v);
     }
   };
 
-  for (int64_t tile = blockIdx.x; tile < args.n_tiles; tile += gridDim.x) {
+  // (a block of the one-tile form runs this ONCE, and as straight-line code: around a loop the compiler computes every uniform value
+  //  of the body - some eighty fragment and hand-off row offsets among them - in front of it, and with a hundred scalar registers
+  //  that means a lane write into a spill register there and a lane read back at the use, for values that are one scalar add.
+  //  gridDim.x <= n_tiles, so a block's first tile always exists.)
+  // The multi-tile form keeps the loop, with D, k and the lane opaque inside it: what the body derives from them then depends on the
+  // iteration and stays in the body (uniform values in scalar registers, per-lane offsets in vector registers that are free again).
+  int64_t tile = blockIdx.x;
+  do {
+    if constexpr (MULTI) {
+      asm volatile("" : "+s"(D), "+s"(k));
+      derive();
+      asm volatile("" : "+v"(lane));
+      derive_lane();
+    }
     CVF_STAMP(8);
     // ---- everything the chains need from memory is requested here
+    // the block's coefficients in one go: its row of the k x k block (entries past k repeat the last one and are not used) and its
+    // entries of the k-vectors, one wait for all of them in front of `alpha` instead of a load and a wait per j
+    double crow[CVF_MAX_NETS];
+#pragma unroll
+    for (int j = 0; j < CVF_MAX_NETS; ++j) crow[j] = coef[k + net * k + (j < k ? j : k - 1)];
+    double gS1n = coef[net], gEtn = coef[k + k * k + net];
+    double gS1ln = GEN ? 0.0 : coef[2 * k + k * k + net], gS2ln = GEN ? 0.0 : coef[3 * k + k * k + net];
+    __builtin_amdgcn_sched_barrier(0);   // (requested HERE, ahead of the vector requests below: the scheduler otherwise sinks them to the pins)
     const bool lagged = !GEN && tile >= args.T;              // (uniform) a tile of lagged partners
     const int64_t t0 = lagged ? tile - args.T : tile;        // the tile of the frames themselves
     const int64_t frame = t0 * CVF_TILE + fo;
@@ -201,11 +251,16 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
 #pragma unroll
     for (int j = 0; j < CVF_MAX_NETS; ++j)
       if (j == net) ynet = yb[j];
+    // (pinned: all of them are in scalar registers here, or each load sinks to its use behind the branch on j < k)
+#pragma unroll
+    for (int j = 0; j < CVF_MAX_NETS; ++j) asm volatile("" : "+s"(crow[j]));
+    asm volatile("" : "+s"(gS1n), "+s"(gEtn));
+    if constexpr (!GEN) asm volatile("" : "+s"(gS1ln), "+s"(gS2ln));
     if (GEN || !lagged) {
       double a = gS1n;
 #pragma unroll
       for (int j = 0; j < CVF_MAX_NETS; ++j)
-        if (j < k) a += (j == net ? 2.0 : 1.0) * coef[k + net * k + j] * (double)yb[j];
+        if (j < k) a += (j == net ? 2.0 : 1.0) * crow[j] * (double)yb[j];
       alpha = (float)((double)wb * a);
       if constexpr (GEN) gamma = (float)(2.0 * (double)wb * gEtn);
       else alpha = (float)((double)wb * a - 2.0 * (double)wb * gEtn * ((double)ylag - (double)ynet));   // ... and d/dy of gT sum w (y' - y)^2
@@ -328,10 +383,10 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
           // SIMD, if wave w of every resident block sits on the same one) has the full tile twice.
           const int role = (wave + 2 * (l & 1)) & 3;   // wave-uniform
           if (role == 0) {
-            emit_tile(l, H, H, 0, 0, outer2(SA1, SB1, SA2, SB2, 0, 0));
+            emit_tile(l, H, 0, 0, outer2(SA1, SB1, SA2, SB2, 0, 0));
           } else {
             const int g = col >> 2, m = lane & 3;
-            const int wo = mlp.w_off[net][l] - gbase, bo = mlp.b_off[net][l] - gbase;
+            const int wo = net_w_off<H, NH>(l, HD), bo = net_b_off<H, NH>(l, HD);
             // one job: the lane's rows of the A and B images -> entry (o, i) in the lanes of DPP row q (rows_sum_scatter)
             auto job = [&](int arow, int brow, int o, int i, bool live) {
               f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -350,7 +405,7 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
         } else {
           for (int pr = wave; pr < RTO * CTH; pr += WPB) {
             const int rt = pr / CTH, ct = pr - rt * CTH;
-            emit_tile(l, H, H, rt, ct, outer2(SA1, SB1, SA2, SB2, rt, ct));
+            emit_tile(l, H, rt, ct, outer2(SA1, SB1, SA2, SB2, rt, ct));
           }
         }
         if (l == NH - 1) emit_last();
@@ -431,14 +486,14 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
             if constexpr (TAIL4) tail0(tacc, SA2, bB, wave, false);
           }
 #pragma unroll
-          for (int rt = 0; rt < (TAIL4 ? 1 : RTO); ++rt) emit_tile(0, H, D, rt, wave, acc[rt]);
+          for (int rt = 0; rt < (TAIL4 ? 1 : RTO); ++rt) emit_tile(0, D, rt, wave, acc[rt]);
           if constexpr (TAIL4) {   // DPP row q holds row 16 + q of the lane's column
             const float v = rows_sum_scatter(tacc);
             int o = 16 + q;
             asm volatile("" : "+v"(o));
             const int i = 16 * wave + row16;
             const bool isw = o < H && i < D, isb = o < H && i == D;
-            emit_entry(isw || isb, isw ? mlp.w_off[net][0] - gbase + o * D + i : mlp.b_off[net][0] - gbase + (o < H ? o : 0), v);
+            emit_entry(isw || isb, isw ? o * D + i : HD + (o < H ? o : 0), v);
           }
         }
         for (int pr = wave; pr < extra; pr += WPB) {
@@ -451,14 +506,15 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, cvf_
           if constexpr (GEN) half0(acc, SA2, bB, ct, rt, RTO, false);
 #pragma unroll
           for (int r_ = 0; r_ < RTO; ++r_)
-            if (r_ == rt) emit_tile(0, H, D, r_, ct, acc[r_]);
+            if (r_ == rt) emit_tile(0, D, r_, ct, acc[r_]);
         }
         emit_strip();
         if (NH == 1) emit_last();
         __syncthreads();
       }
     }
-  }
+    tile += gridDim.x;
+  } while (MULTI && tile < args.n_tiles);
   CVF_STAMP(17);
   if (MULTI) {   // flush this block's partial gradient of `net` into its slab row
     __syncthreads();
@@ -495,6 +551,19 @@ static int ef16_backward_impl(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, co
     covered += span;
   }
   CVF_REQUIRE(covered == mlp->n_params, "cvf_ef16_backward: flat buffer holds parameters outside the nets");
+  // ... and the kernel derives a layer's offsets from its net's base: per layer the weight, then the bias, layer after layer (the order
+  // of model.parameters(), which is what every caller passes)
+  for (int n = 0; n < mlp->n_nets; ++n)
+    for (int l = 0; l <= NH; ++l) {
+      CVF_REQUIRE(mlp->b_off[n][l] == mlp->w_off[n][l] + mlp->dims[l] * mlp->dims[l + 1],
+                  "cvf_ef16_backward: net %d, layer %d: the bias does not follow the weight", n, l);
+      CVF_REQUIRE(l == NH || mlp->w_off[n][l + 1] == mlp->b_off[n][l] + mlp->dims[l + 1],
+                  "cvf_ef16_backward: net %d: layer %d does not follow layer %d", n, l + 1, l);
+    }
+  Back16Nets nets;
+  nets.D = mlp->dims[0];
+  nets.n_params = mlp->n_params;
+  for (int n = 0; n < CVF_MAX_NETS; ++n) nets.base[n] = n < mlp->n_nets ? mlp->w_off[n][0] : 0;
   Back16Args a;
   a.k = cfg->k;
   a.B = B;
@@ -505,7 +574,7 @@ static int ef16_backward_impl(const cvf_ef_cfg* cfg, const cvf_mlp_desc* mlp, co
   const bool launched = ef16_dispatch(H, NH, [&](auto h_, auto nh_) {
     constexpr int kH = decltype(h_)::value, kNH = decltype(nh_)::value;
     auto go = [&](auto kernel, size_t lds) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)G, cfg->k), dim3(256), lds, (hipStream_t)stream, a, *mlp, theta, packed, w, feat_tiled,
+      hipLaunchKernelGGL(kernel, dim3((unsigned)G, cfg->k), dim3(256), lds, (hipStream_t)stream, a, nets, theta, packed, w, feat_tiled,
                          y_tiled, q_tiled, coef, slab, step_count, saved);
     };
     const size_t gi = (size_t)span * sizeof(float);

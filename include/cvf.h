@@ -378,7 +378,10 @@ int cvf_ef_align_fwd_metric_stats(const cvf_mlp_desc* mlp, const float* theta, c
  *                     hand-off of the hidden activations), q_tiled [T][k][d_r][64], e_tiled [T][k][64], stats (+ loss_vec, coef
  *                     when non-NULL: cvf_ef_loss in the same call).  Replaces pp_layer(X), model(...), the k autograd.grad calls
  *                     and the batch sums of core.py:403-452.  scratch: cvf_ef16_scratch_doubles(B, k) doubles.
- *  cvf_ef16_backward: flat parameter gradient as slab rows, as cvf_ef_backward (core.py:517); follow with cvf_slab_reduce. */
+ *  cvf_ef16_backward: flat parameter gradient as slab rows, as cvf_ef_backward (core.py:517); follow with cvf_slab_reduce.
+ *                     Every net must be one run of the flat buffer in the order of model.parameters() - per layer the weight, then
+ *                     the bias, layer after layer: the kernel derives a layer's offsets from w_off[net][0].  Any other order
+ *                     inside a net is refused (cvf_ef16_backward_transfer alike). */
 int cvf_ef16_supported(const cvf_mlp_desc* mlp, const cvf_pp_desc* pp);
 int64_t cvf_ef16_scratch_doubles(int64_t B, int k);
 int64_t cvf_ef16_saved_floats(const cvf_mlp_desc* mlp, int64_t n_tiles);
