@@ -252,6 +252,19 @@ _SIGNATURES["cvf_regae_ragged_backward_reuse"] = _with_depths(_SIGNATURES["cvf_r
 # the isotropic-metric forms of the two front calls take the arguments of their general twins
 _SIGNATURES["cvf_ef16_front_iso"] = _SIGNATURES["cvf_ef16_front"]
 _SIGNATURES["cvf_ef16_front_rows_iso"] = _SIGNATURES["cvf_ef16_front_rows"]
+
+
+class CVModel(C.Structure):
+    """``cvf_cv_model`` (include/cvf.h): what ``cvf_cv_file_bind`` fills - both descriptors and theta over one device buffer."""
+    _fields_ = [("mlp", MLPDesc), ("pp", PPDesc), ("theta", C.c_void_p), ("upto_layer", C.c_int32), ("k", C.c_int32)]
+
+
+# xi and d xi / d x per frame in one launch (csrc/cv_frame.hip), and the self-contained model file (csrc/cv_file.hip)
+_SIGNATURES["cvf_cv_frame_supported"] = (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.POINTER(PPDesc)])
+_SIGNATURES["cvf_cv_frame_eval"] = (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_int, C.POINTER(PPDesc), C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_SIGNATURES["cvf_cv_file_device_bytes"] = (C.c_int64, [C.c_char_p, C.c_int64])
+_SIGNATURES["cvf_cv_file_bind"] = (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(CVModel), C.c_void_p])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

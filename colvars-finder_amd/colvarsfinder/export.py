@@ -102,3 +102,171 @@ def scriptable_cv(cv: torch.nn.Sequential) -> torch.nn.Sequential:
         else:
             mods.append(copy.deepcopy(m).to("cpu"))
     return torch.nn.Sequential(*mods)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The self-contained model file of a trained CV (include/cvf.h: cvf_cv_file_*) and its evaluator.
+# TorchScript (save_model) serves programs that link libtorch; this file serves a C caller of libcvf_hip.so - an MD engine that
+# needs xi(x) and grad_x xi(x) for one frame per step: cvf_cv_file_bind once, cvf_cv_frame_eval per step.
+# ------------------------------------------------------------------------------------------------------------------------
+CV_FILE_MAGIC, CV_FILE_VERSION, CV_FILE_DIR_OFFSET = b"CVF1", 1, 960
+# table ids of the directory (include/cvf.h: CVF_FILE_*), element type 0 = int32, 1 = float32
+CV_FILE_TABLES = (("align_idx", 1, 0), ("ref_c", 2, 1), ("rec", 3, 0), ("align_w", 4, 1), ("atom_align", 5, 0), ("atom_slot", 6, 0),
+                  ("rec_slot", 7, 0), ("slot_atom", 8, 0), ("mrec", 9, 0), ("slot_row", 10, 0), ("theta", 11, 1))
+
+
+def _cv_parts(cv):
+    """``(pp scalars dict, tables dict of CPU numpy arrays, MLPDesc, upto_layer, k)`` of a ``colvar_model()``."""
+    import numpy as np
+    from .core import _CVModel
+    from .pp import AlignFeatureLayer
+    if not hasattr(cv, "_pp_and_nets"):
+        raise NotImplementedError(f"save_cv_file takes what colvar_model() returns, got a {type(cv).__name__}")
+    pp, nets = cv._pp_and_nets()
+    if not isinstance(pp, (torch.nn.Identity, AlignFeatureLayer)):
+        raise NotImplementedError(f"the preprocessing layer is a {type(pp).__name__}: a CV file holds an Identity or an "
+                                  "AlignFeatureLayer (a foreign pp_layer has no tables to write)")
+    try:
+        desc, upto, k, params = _CVModel._nets_plan(nets)
+    except TypeError as e:
+        raise NotImplementedError(str(e)) from e
+    theta = torch.cat([p.detach().to(device="cpu", dtype=torch.float32).reshape(-1) for p in params]).numpy()
+    i32, f32 = (lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.int32).reshape(-1)), \
+               (lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32).reshape(-1))
+    empty_i, empty_f = np.zeros(0, np.int32), np.zeros(0, np.float32)
+    if isinstance(pp, torch.nn.Identity):
+        n = int(desc.dims[0])
+        sc = dict(mode=_hip.PP_IDENTITY, n_coord=n, n_align=0, n_rec=0, d_r=n, use_angle_value=0, has_position=0, flags=0,
+                  n_slot=0, n_rec_slot=0, n_mrec=0, n_ref=0)
+        tabs = {name: (empty_f if ty else empty_i) for name, _, ty in CV_FILE_TABLES}
+    else:
+        with_rows = pp._n_ref < 65536 and pp._n_slot < 65536 and getattr(pp, "_row_off_max", 0) < 256   # as pp_desc()
+        sc = dict(mode=_hip.PP_ALIGN if pp.aligned else _hip.PP_FEATURES, n_coord=3 * pp.n_atoms, n_align=int(pp.align_idx.numel()),
+                  n_rec=int(pp.rec.shape[0]), d_r=int(pp.d_r), use_angle_value=int(pp.use_angle_value),
+                  has_position=int(bool((pp.rec[:, 0] == _hip.FEAT_POSITION).any().item())), flags=int(pp._flags),
+                  n_slot=int(pp._n_slot), n_rec_slot=int(pp._n_rec_slot), n_mrec=int(pp.mrec.shape[0]) if with_rows else 0,
+                  n_ref=int(pp._n_ref) if with_rows else 0)
+        tabs = dict(align_idx=i32(pp.align_idx), ref_c=f32(pp.ref_c) if pp.aligned else empty_f, rec=i32(pp.rec),
+                    align_w=f32(pp.align_w) if pp.align_w is not None else empty_f, atom_align=i32(pp.atom_align),
+                    atom_slot=i32(pp.atom_slot), rec_slot=i32(pp.rec_slot), slot_atom=i32(pp.slot_atom),
+                    mrec=i32(pp.mrec) if with_rows else empty_i, slot_row=i32(pp.slot_row) if with_rows else empty_i)
+    tabs["theta"] = theta
+    return sc, tabs, desc, int(upto), int(k)
+
+
+def cv_file_bytes(cv) -> bytes:
+    """The bytes :func:`save_cv_file` writes (layout: include/cvf.h, ``cvf_cv_file_*``)."""
+    import struct
+    sc, tabs, desc, upto, k = _cv_parts(cv)
+    head = CV_FILE_MAGIC + struct.pack("<3i", CV_FILE_VERSION, _hip.MAX_NETS, _hip.MAX_LAYERS) + bytes(desc)
+    head += struct.pack("<12i", *(sc[f] for f in ("mode", "n_coord", "n_align", "n_rec", "d_r", "use_angle_value", "has_position",
+                                                  "flags", "n_slot", "n_rec_slot", "n_mrec", "n_ref")))
+    head += struct.pack("<4i", upto, k, len(CV_FILE_TABLES), 0)
+    assert len(head) == CV_FILE_DIR_OFFSET
+    pos = (CV_FILE_DIR_OFFSET + 24 * len(CV_FILE_TABLES) + 15) // 16 * 16
+    directory, body = b"", b""
+    data_off = pos
+    for name, tid, ty in CV_FILE_TABLES:
+        a = tabs[name]
+        directory += struct.pack("<2i2q", tid, ty, a.size, pos if a.size else 0)
+        if a.size:
+            raw = a.astype("<f4" if ty else "<i4", copy=False).tobytes()
+            body += raw + b"\0" * (-len(raw) % 16)
+            pos += len(raw) + (-len(raw) % 16)
+    blob = head + directory
+    return blob + b"\0" * (data_off - len(blob)) + body
+
+
+def save_cv_file(cv, path):
+    """Write ``colvar_model()`` as ONE self-contained little-endian file a C caller binds with ``cvf_cv_file_bind`` and evaluates
+    with ``cvf_cv_frame_eval`` - the nets' flat parameters and description and ALL tables of the preprocessing layer, so that the
+    bound model also feeds the three-call recipe.  ``NotImplementedError`` (with the reason) for models the HIP nets' kernels do
+    not describe: a ``RegModel``, foreign modules, a foreign ``pp_layer``.  ``save_model`` and its TorchScript files are a
+    different artefact and are not touched."""
+    blob = cv_file_bytes(cv)
+    with open(path, "wb") as f:
+        f.write(blob)
+    return path
+
+
+class FrameCV:
+    """``xi(x)`` and ``d xi / d x`` of a saved (path) or live (``colvar_model()``) CV on the kernels a C caller of the file gets.
+
+    Both forms go through the file's bytes and ``cvf_cv_file_bind`` into one torch-owned device buffer.  ``fc(X, coef=None)``
+    returns ``(xi [B, k], J [B, k, *frame])`` or, with ``coef [B, k]``, ``(xi, F [B, *frame])`` with
+    ``F = sum_i coef_i d xi_i / d x`` (the bias force up to sign), on ``X``'s device and in its floating-point type, like
+    ``jacobian()``.  ``fc.supported`` is ``(bool, reason)`` of ``cvf_cv_frame_supported``; ``fc.route`` is ``"frame"`` (one
+    launch, one wave per frame: ``cvf_cv_frame_eval``) or ``"three-call"`` (``cvf_align_feature_fwd`` -> ``cvf_cv_nets_eval`` ->
+    ``cvf_align_feature_vjp_rows`` on the same bound model: large molecules, wide nets).  The one launch is built for one frame
+    or a few replicas per call; DESIGN.md section 4.15 gives the batch size above which the three-call recipe is the faster of
+    the two (``jacobian()`` is that recipe for whole trajectories)."""
+
+    def __init__(self, path_or_cv, device="cuda"):
+        import ctypes as C
+        if isinstance(path_or_cv, (str, bytes)) or hasattr(path_or_cv, "__fspath__"):
+            with open(path_or_cv, "rb") as f:
+                blob = f.read()
+        else:
+            blob = cv_file_bytes(path_or_cv)
+        self.device = _hip.require_gpu(torch.device(device))
+        lib = _hip.lib()
+        need = lib.cvf_cv_file_device_bytes(blob, len(blob))
+        if need <= 0:
+            raise ValueError(f"not a CV file ({need}): {lib.cvf_last_error().decode()}")
+        with torch.cuda.device(self.device):
+            self._buf = torch.empty(need, device=self.device, dtype=torch.uint8)
+            self.model = _hip.CVModel()
+            _hip.check(lib.cvf_cv_file_bind(blob, len(blob), C.c_void_p(self._buf.data_ptr()), need, C.byref(self.model),
+                                            _hip.stream()), "cvf_cv_file_bind")
+        self.k, self.n_coord, self.d_r = int(self.model.k), int(self.model.pp.n_coord), int(self.model.pp.d_r)
+        ok = lib.cvf_cv_frame_supported(C.byref(self.model.mlp), self.model.upto_layer, C.byref(self.model.pp)) == 1
+        self.supported = (ok, None if ok else lib.cvf_last_error().decode())
+        self.route = "frame" if ok else "three-call"
+
+    def __call__(self, X, coef=None):
+        import ctypes as C
+        import numpy as np
+        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
+        src_dev, src_dt = X.device, (X.dtype if X.dtype.is_floating_point else torch.float32)
+        B, frame_shape = int(X.shape[0]), tuple(X.shape[1:])
+        assert int(np.prod(frame_shape)) == self.n_coord, f"frames have {int(np.prod(frame_shape))} coordinates, the model takes {self.n_coord}"
+        dev, k, n = self.device, self.k, self.n_coord
+        lib, P, m = _hip.lib(), _hip.ptr, self.model
+        with torch.cuda.device(dev):
+            s = _hip.stream()
+            x = X.detach().to(device=dev, dtype=torch.float32).reshape(B, n).contiguous()
+            cf = None
+            if coef is not None:
+                cf = torch.as_tensor(coef).detach().to(device=dev, dtype=torch.float32).reshape(B, k).contiguous()
+            xi = torch.empty(B, k, device=dev, dtype=torch.float32)
+            D = torch.empty((B, n) if cf is not None else (B, k, n), device=dev, dtype=torch.float32)
+            if B > 0 and self.route == "frame":
+                _hip.check(lib.cvf_cv_frame_eval(C.byref(m.mlp), C.c_void_p(m.theta), m.upto_layer, C.byref(m.pp), P(x), B, P(cf),
+                                                 P(xi), P(D), s), "cvf_cv_frame_eval")
+            elif B > 0:
+                self._three_call(x, cf, xi, D, s)
+        D = D.reshape(((B,) if cf is not None else (B, k)) + frame_shape)
+        return xi.to(device=src_dev, dtype=src_dt), D.to(device=src_dev, dtype=src_dt)
+
+    def _three_call(self, x, cf, xi, D, s):
+        """cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp[_rows] on the bound model."""
+        import ctypes as C
+        lib, P, m, dev = _hip.lib(), _hip.ptr, self.model, self.device
+        B, k, d_r, T = int(x.shape[0]), self.k, self.d_r, _hip.ntiles(int(x.shape[0]))
+        pp, mlp, theta = C.byref(m.pp), C.byref(m.mlp), C.c_void_p(m.theta)
+        r = r_t = aux = None
+        if m.pp.mode == _hip.PP_IDENTITY:
+            r = x
+        else:
+            r_t = torch.empty(T, d_r, _hip.TILE, device=dev, dtype=torch.float32)
+            aux = torch.empty(T, _hip.AUX_ROWS, _hip.TILE, device=dev, dtype=torch.float32)
+            scratch = _hip.align_scratch(m.pp, B, dev)
+            _hip.check(lib.cvf_align_feature_fwd(pp, P(x), B, P(r_t), None, P(aux), P(scratch), s), "cvf_align_feature_fwd")
+        G = torch.empty(B, k, d_r, device=dev, dtype=torch.float32)
+        ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mlp, m.upto_layer, B, 1), device=dev, dtype=torch.float32)
+        _hip.check(lib.cvf_cv_nets_eval(mlp, theta, m.upto_layer, P(r), P(r_t), B, P(xi), P(G), None, P(ws), s), "cvf_cv_nets_eval")
+        if cf is None:
+            _hip.check(lib.cvf_align_feature_vjp_rows(pp, P(x), B, P(aux), k, P(G), P(D), s), "cvf_align_feature_vjp_rows")
+        else:   # the contraction at the feature level (k terms per feature), then one coordinate pass
+            g = torch.einsum("bk,bkr->br", cf, G).contiguous()
+            _hip.check(lib.cvf_align_feature_vjp(pp, P(x), B, P(aux), P(g), P(D), s), "cvf_align_feature_vjp")

@@ -745,6 +745,68 @@ int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer
                      const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled, float* scratch,
                      void* stream);
 
+/* --- xi(x) and d xi / d x per frame in ONE launch, one wave per frame (csrc/cv_frame.hip): the
+ * deployment form of the three calls cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp_rows for an MD engine
+ * that biases along a learned CV and evaluates one frame (or a handful of replicas) per step.  The alignment, the features, the
+ * nets' forward pass, their sweep and the coordinate part all stay in the LDS of the frame's workgroup (64 threads, grid B).
+ *   x [B][n_coord] -> xi_rows [B][k] and
+ *     coef == NULL : gx_rows [B][k][n_coord], row i = d xi_i / d x (the layout of cvf_align_feature_vjp_rows);
+ *     coef [B][k]  : gx_rows [B][n_coord] = sum_i coef[b][i] d xi_i / d x (the bias force up to sign); the sum is taken at the
+ *                    feature level, g = sum_i coef_i d xi_i / d r, so the coordinate part runs once, not k times.
+ * The model is described as for cvf_cv_nets_eval (form A: n_nets = k scalar chains, upto_layer = n_layers; form B: the first
+ * upto_layer layers of one chain, k = dims[upto_layer], the trunk forward once); any act code after any layer.
+ *  cvf_cv_frame_supported: 1, or 0 with the reason in cvf_last_error() - it names the three-call recipe, which takes every shape
+ *    this launch declines.  Accepted: CVF_PP_ALIGN and CVF_PP_FEATURES with n_coord <= 192 (align_w honoured, n_align <= 64;
+ *    flags are ignored: only rec, align_idx, ref_c and align_w are read), CVF_PP_IDENTITY with n_coord <= 512; dims[0] == d_r <= 512,
+ *    inner widths <= 256, 1 to CVF_MAX_LAYERS layers, k <= CVF_MAX_NETS; a workgroup LDS total (the frame, every layer's
+ *    activations, two sweep vectors, k rows of d xi / d r, of per-record contributions and of the gradient image) of at most
+ *    64 KiB.  CVF_PP_FACTORED is refused.
+ *  cvf_cv_frame_eval: no aux, no scratch, no allocation, no host synchronisation, no atomics.  Every refusal happens before any
+ *    launch (negative code, cvf_last_error()); B == 0 returns 0 and writes nothing.  xi_rows and gx_rows are fully written for
+ *    rows < B; the gradient is exactly 0 on atoms that are neither aligned nor read by a feature.  Every dot product of the nets
+ *    is a sequential sum in index order inside one lane, every sum over lanes a fixed tree: a frame's result depends on its own
+ *    coordinates and theta only - not on B, nor on its place in the batch - and two calls give the same bits.
+ * Large batches (the launch keeps one wave per frame busy with work a 64-frame tile shares), large molecules and wide nets
+ * belong to the three-call recipe. */
+int cvf_cv_frame_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int cvf_cv_frame_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp, const float* x,
+                      int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
+
+/* --- a trained CV as ONE self-contained file, and its binder (csrc/cv_file.hip; parser and validator: csrc/cvf_cv_file.hpp, host
+ * C++ without a HIP include).  colvarsfinder.export.save_cv_file writes it; a C caller reads the bytes, asks for the size of the
+ * device buffer, allocates it and binds:
+ *   cvf_cv_file_device_bytes(blob, nbytes)  -> bytes of dev_buf (> 0), or a negative code and a message naming the offending field;
+ *   cvf_cv_file_bind(blob, nbytes, dev_buf, dev_bytes, &model, stream) -> model.mlp / model.pp / model.theta point into dev_buf
+ *     (16-byte aligned, at least the size above), ready for cvf_cv_frame_eval - or, for shapes cvf_cv_frame_supported declines,
+ *     for the three-call recipe: the file holds ALL tables of the layer, not only those the one-launch kernel reads.
+ * `blob` is HOST memory (unlike the rest of this header).  cvf_cv_file_bind is a SET-UP call: it copies the table region in one
+ * host-to-device copy on `stream` and SYNCHRONISES the stream before it returns (the blob may be freed right away); it does not
+ * allocate.  cvf_cv_file_device_bytes touches no device.
+ * Layout, little-endian, int32 unless noted:
+ *   0    magic "CVF1", format version (1), CVF_MAX_NETS, CVF_MAX_LAYERS as written
+ *   16   the cvf_mlp_desc fields in struct order (n_nets, n_layers, dims, act, w_off, b_off, n_params)
+ *   896  mode, n_coord, n_align, n_rec, d_r, use_angle_value, has_position, flags, n_slot, n_rec_slot, n_mrec, n_ref
+ *   944  upto_layer, k, number of directory entries, 0
+ *   960  directory: per table { name id, element type (0 int32, 1 float32), int64 count, int64 byte offset in the file }, one
+ *        entry for EVERY id below (count 0 = the layer has no such table: the descriptor's pointer is NULL)
+ *   then the tables, each 16-byte aligned, in the order of their offsets.
+ * A file that is truncated, carries counts that disagree with the scalar fields, an atom index >= n_coord / 3, an output offset
+ * past d_r, a parameter offset past theta, an unknown act code, type id or table id is refused before any pointer is formed. */
+enum {
+  CVF_FILE_ALIGN_IDX = 1, CVF_FILE_REF_C = 2, CVF_FILE_REC = 3, CVF_FILE_ALIGN_W = 4, CVF_FILE_ATOM_ALIGN = 5,
+  CVF_FILE_ATOM_SLOT = 6, CVF_FILE_REC_SLOT = 7, CVF_FILE_SLOT_ATOM = 8, CVF_FILE_MREC = 9, CVF_FILE_SLOT_ROW = 10,
+  CVF_FILE_THETA = 11, CVF_FILE_N_TABLES = 11
+};
+#define CVF_FILE_VERSION 1
+typedef struct cvf_cv_model {
+  cvf_mlp_desc mlp;
+  cvf_pp_desc pp;
+  const float* theta;   /* device, cvf_mlp_desc.n_params floats */
+  int32_t upto_layer, k;
+} cvf_cv_model;
+int64_t cvf_cv_file_device_bytes(const void* blob_host, int64_t nbytes);
+int cvf_cv_file_bind(const void* blob_host, int64_t nbytes, void* dev_buf, int64_t dev_bytes, cvf_cv_model* out, void* stream);
+
 /* --- K6: Adam (torch.optim.Adam defaults as constructed at core.py:164: betas
  * (0.9,0.999), eps 1e-8, no weight decay, no amsgrad), one launch over the flat buffer.
  * step_count is a device int32 holding the number t of the CURRENT step (>= 1): it is advanced by the

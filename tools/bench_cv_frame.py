@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""xi(x) and d xi / d x for small batches: the one-launch entry cvf_cv_frame_eval (csrc/cv_frame.hip) against the
+three-call recipe cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp_rows, in one process.
+
+  shapes    c3         config 3: 22 atoms, all positions, d_r 66, nets [66,20,20,20,1] x 3
+            dipeptide  the dipeptide notebook: 10 atoms, all positions, d_r 30, nets [30,20,20,20,1] x 2
+  batches   B = 1, 8, 64, 1024
+  variants  three_eager   the three calls issued from the host each time
+            three_graph   the same launches replayed from one captured hipGraph (single stream) - the yardstick
+            frame_eager   cvf_cv_frame_eval issued from the host each time
+            frame_graph   the same launch replayed from a graph
+
+Method: HIP events around a window of --replays (200) back-to-back evaluations, time per evaluation = window / replays; per
+round and variant the median of --windows (3) windows; --rounds (3) rounds that alternate the variants; reported per variant: the
+median of the rounds' medians and their spread (min, max), in microseconds.  Before timing, the two routes' J are compared.
+Buffers are allocated once; nothing is allocated inside a window.  One JSON line; --summary PATH also writes a table."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "colvars-finder_amd")):
+    sys.path.insert(0, p)
+import torch  # noqa: E402
+
+from colvarsfinder import _hip, core, nn, pp  # noqa: E402
+from tests.synth import make_molecule_traj  # noqa: E402
+
+SHAPES = {"c3": (22, [66, 20, 20, 20, 1], 3), "dipeptide": (10, [30, 20, 20, 20, 1], 2)}
+BATCHES = (1, 8, 64, 1024)
+VARIANTS = ("three_eager", "three_graph", "frame_eager", "frame_graph")
+
+
+def build(shape, B, dev):
+    """The two routes as closures over preallocated buffers: (three(), frame(), J of each)."""
+    lib, P = _hip.lib(), _hip.ptr
+    n, dims, k = SHAPES[shape]
+    traj, _, ref = make_molecule_traj(n, B, seed=17)
+    layer = pp.AlignFeatureLayer(n, list(range(n)), ref, [("position", tuple(range(n)))]).to(dev)
+    torch.manual_seed(11)
+    nets = nn.EigenFunctions(dims, k).to(dev)
+    mdesc, upto, k, params = core._CVModel._nets_plan(nets)
+    theta = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+    pdesc = layer.pp_desc()
+    assert lib.cvf_cv_frame_supported(mdesc, upto, pdesc) == 1, lib.cvf_last_error().decode()
+    x = torch.tensor(traj, device=dev).reshape(B, -1).contiguous()
+    T, d_r, nc = _hip.ntiles(B), layer.d_r, 3 * n
+    r_t = torch.empty(T, d_r, _hip.TILE, device=dev)
+    aux = torch.empty(T, _hip.AUX_ROWS, _hip.TILE, device=dev)
+    G = torch.empty(B, k, d_r, device=dev)
+    ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mdesc, upto, B, 1), device=dev)
+    xi3, J3 = torch.empty(B, k, device=dev), torch.empty(B, k, nc, device=dev)
+    xi1, J1 = torch.empty(B, k, device=dev), torch.empty(B, k, nc, device=dev)
+    keep = (layer, nets, theta, x, r_t, aux, G, ws)
+
+    def three():
+        s = _hip.stream()
+        _hip.check(lib.cvf_align_feature_fwd(pdesc, P(x), B, P(r_t), None, P(aux), None, s), "cvf_align_feature_fwd")
+        _hip.check(lib.cvf_cv_nets_eval(mdesc, P(theta), upto, None, P(r_t), B, P(xi3), P(G), None, P(ws), s), "cvf_cv_nets_eval")
+        _hip.check(lib.cvf_align_feature_vjp_rows(pdesc, P(x), B, P(aux), k, P(G), P(J3), s), "cvf_align_feature_vjp_rows")
+
+    def frame():
+        _hip.check(lib.cvf_cv_frame_eval(mdesc, P(theta), upto, pdesc, P(x), B, None, P(xi1), P(J1), _hip.stream()), "cvf_cv_frame_eval")
+
+    return three, frame, J3, J1, keep
+
+
+def captured(fn):
+    """fn's launches as one graph on a single stream; returns the replay."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g.replay, g
+
+
+def window_us(fn, replays):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(replays):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / replays
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--replays", type=int, default=200)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--batches", default=",".join(map(str, BATCHES)), help="comma-separated batch sizes (larger ones locate the crossover)")
+    ap.add_argument("--summary", default=None)
+    a = ap.parse_args()
+    assert a.replays >= 200 and a.rounds >= 3, "at least 200 replays per window and three rounds"
+    assert torch.cuda.is_available(), "bench_cv_frame.py measures on the GPU"
+    dev = torch.device("cuda:0")
+    out = {"tool": "bench_cv_frame", "replays": a.replays, "windows": a.windows, "rounds": a.rounds, "unit": "us per evaluation",
+           "results": {}}
+    lines = [f"{'shape':10s} {'B':>5s} " + " ".join(f"{v:>24s}" for v in VARIANTS) + "   frame_graph / three_graph"]
+    for shape in SHAPES:
+        for B in [int(b) for b in a.batches.split(",")]:
+            three, frame, J3, J1, keep = build(shape, B, dev)
+            three()
+            frame()
+            torch.cuda.synchronize()
+            diff = float((J1 - J3).abs().max() / J3.abs().max())
+            three_g, g3 = captured(three)
+            frame_g, g1 = captured(frame)
+            fns = dict(zip(VARIANTS, (three, three_g, frame, frame_g)))
+            for fn in fns.values():          # warm every variant once more behind the captures
+                window_us(fn, 20)
+            rounds = {v: [] for v in VARIANTS}
+            for _ in range(a.rounds):
+                for v in VARIANTS:           # the variants alternate inside a round
+                    rounds[v].append(statistics.median(window_us(fns[v], a.replays) for _ in range(a.windows)))
+            res = {v: {"median": round(statistics.median(t), 3), "min": round(min(t), 3), "max": round(max(t), 3)} for v, t in rounds.items()}
+            res["rel_diff_J"] = diff
+            out["results"][f"{shape}/B{B}"] = res
+            ratio = res["frame_graph"]["median"] / res["three_graph"]["median"]
+            lines.append(f"{shape:10s} {B:5d} " + " ".join(
+                f"{res[v]['median']:9.2f} [{res[v]['min']:6.2f},{res[v]['max']:6.2f}]" for v in VARIANTS) + f"   {ratio:.3f}   (J rel diff {diff:.1e})")
+            del g3, g1, keep
+    print("\n".join(lines), file=sys.stderr)
+    if a.summary:
+        with open(a.summary, "w") as f:
+            f.write("bench_cv_frame: us per evaluation of (xi, J), median of the rounds' medians [min, max over rounds]; "
+                    f"{a.replays} replays per window, {a.windows} windows per round, {a.rounds} rounds, variants alternating\n")
+            f.write("\n".join(lines) + "\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
