@@ -265,6 +265,10 @@ _SIGNATURES["cvf_cv_frame_eval"] = (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _SIGNATURES["cvf_cv_file_device_bytes"] = (C.c_int64, [C.c_char_p, C.c_int64])
 _SIGNATURES["cvf_cv_file_bind"] = (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(CVModel), C.c_void_p])
+# the same in one launch for frames of any size, one workgroup per frame (csrc/cv_frame_large.hip)
+_SIGNATURES["cvf_cv_frame_large_supported"] = (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.POINTER(PPDesc)])
+_SIGNATURES["cvf_cv_frame_large_lds_bytes"] = (C.c_int64, [C.POINTER(MLPDesc), C.c_int, C.POINTER(PPDesc), C.POINTER(C.c_int32)])
+_SIGNATURES["cvf_cv_frame_large_eval"] = _SIGNATURES["cvf_cv_frame_eval"]
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

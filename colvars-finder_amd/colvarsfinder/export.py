@@ -199,9 +199,15 @@ class FrameCV:
     launch, one wave per frame: ``cvf_cv_frame_eval``) or ``"three-call"`` (``cvf_align_feature_fwd`` -> ``cvf_cv_nets_eval`` ->
     ``cvf_align_feature_vjp_rows`` on the same bound model: large molecules, wide nets).  The one launch is built for one frame
     or a few replicas per call; DESIGN.md section 4.15 gives the batch size above which the three-call recipe is the faster of
-    the two (``jacobian()`` is that recipe for whole trajectories)."""
+    the two (``jacobian()`` is that recipe for whole trajectories).
 
-    def __init__(self, path_or_cv, device="cuda"):
+    ``large_frames=True`` opts into the one launch for frames of any size (``cvf_cv_frame_large_eval``, one workgroup per frame;
+    DESIGN.md section 4.16): the route is ``"frame"`` where the wave kernel takes the model, else ``"frame-large"`` where
+    ``cvf_cv_frame_large_supported`` does, else ``"three-call"``.  ``fc.supported_large`` is ``(bool, reason)`` of that predicate
+    (asked with or without the option; ``fc.supported`` keeps its meaning).  Section 4.16 gives the measured times of both routes
+    and the batch size at which they meet; the default stays ``False``."""
+
+    def __init__(self, path_or_cv, device="cuda", large_frames=False):
         import ctypes as C
         if isinstance(path_or_cv, (str, bytes)) or hasattr(path_or_cv, "__fspath__"):
             with open(path_or_cv, "rb") as f:
@@ -221,7 +227,9 @@ class FrameCV:
         self.k, self.n_coord, self.d_r = int(self.model.k), int(self.model.pp.n_coord), int(self.model.pp.d_r)
         ok = lib.cvf_cv_frame_supported(C.byref(self.model.mlp), self.model.upto_layer, C.byref(self.model.pp)) == 1
         self.supported = (ok, None if ok else lib.cvf_last_error().decode())
-        self.route = "frame" if ok else "three-call"
+        ok_large = lib.cvf_cv_frame_large_supported(C.byref(self.model.mlp), self.model.upto_layer, C.byref(self.model.pp)) == 1
+        self.supported_large = (ok_large, None if ok_large else lib.cvf_last_error().decode())
+        self.route = "frame" if ok else ("frame-large" if large_frames and ok_large else "three-call")
 
     def __call__(self, X, coef=None):
         import ctypes as C
@@ -243,6 +251,9 @@ class FrameCV:
             if B > 0 and self.route == "frame":
                 _hip.check(lib.cvf_cv_frame_eval(C.byref(m.mlp), C.c_void_p(m.theta), m.upto_layer, C.byref(m.pp), P(x), B, P(cf),
                                                  P(xi), P(D), s), "cvf_cv_frame_eval")
+            elif B > 0 and self.route == "frame-large":
+                _hip.check(lib.cvf_cv_frame_large_eval(C.byref(m.mlp), C.c_void_p(m.theta), m.upto_layer, C.byref(m.pp), P(x), B, P(cf),
+                                                       P(xi), P(D), s), "cvf_cv_frame_large_eval")
             elif B > 0:
                 self._three_call(x, cf, xi, D, s)
         D = D.reshape(((B,) if cf is not None else (B, k)) + frame_shape)

@@ -772,6 +772,32 @@ int cvf_cv_frame_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp
 int cvf_cv_frame_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp, const float* x,
                       int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
 
+/* --- the same for frames of ANY size: one launch, one WORKGROUP of 256 threads per frame, grid B (csrc/cv_frame_large.hip;
+ * DESIGN.md section 4.16).  What a caller of colvar_model() (core.py:372-382) or of the scripted CV (save_model, core.py:205-226)
+ * gets from autograd through the alignment + feature layer and the nets (examples/dipeptide/main.ipynb:333-348), for molecules past
+ * the 64 atoms of cvf_cv_frame_eval.  Arguments, outputs and the meaning of coef are those of cvf_cv_frame_eval exactly; the two
+ * kernels are independent (shapes below 64 atoms are accepted here too).  The frame stays in global memory; the features, the
+ * nets' activations, d xi / d r and the table of contribution rows (n_ref * 12 bytes per cotangent row) live in the workgroup's
+ * dynamic LDS, and the coordinate part walks the cotangent rows in passes of rows_per_pass.
+ *  cvf_cv_frame_large_supported: 1, or 0 with the reason in cvf_last_error(), which names the limit and the three-call recipe.
+ *    Accepted: CVF_PP_ALIGN (any n_align >= 3, align_w honoured) and CVF_PP_FEATURES with n_coord any positive multiple of 3;
+ *    the nets' limits of cvf_cv_frame_eval (dims[0] == d_r <= 512, inner widths <= 256, 1 to CVF_MAX_LAYERS layers,
+ *    k <= CVF_MAX_NETS, both forms); n_slot <= CVF_FEATURES_MAX_SLOT, n_ref <= CVF_FEATURES_MAX_REF; the tables mrec (n_mrec > 0),
+ *    slot_row, slot_atom, atom_slot and, for CVF_PP_ALIGN, atom_align; an LDS total within 160 KiB with rows_per_pass >= 1.
+ *    CVF_PP_IDENTITY (cvf_cv_frame_eval takes it) and CVF_PP_FACTORED are refused.
+ *  cvf_cv_frame_large_lds_bytes: the dynamic LDS of one frame for coef == NULL, in bytes, and through rows_per_pass (may be NULL)
+ *    the cotangent rows per pass, min(k, what fits) - or a negative code for a model the predicate refuses.
+ *  cvf_cv_frame_large_eval: no aux, no scratch, no allocation, no host synchronisation, no atomics.  Every refusal happens before
+ *    any launch (negative code, cvf_last_error()) and leaves the outputs untouched; B == 0 returns 0 and writes nothing.  Every
+ *    element of xi_rows and gx_rows of rows < B is written exactly once; the gradient is exactly 0 on atoms that are neither
+ *    aligned nor read by a feature.  Every sum has a fixed order (a thread's own terms in index order, wave_sum inside a wave,
+ *    the four waves in index order), and a row's arithmetic does not depend on the pass it falls in: a frame's result depends on
+ *    its own coordinates and theta only - not on B, nor on its place in the batch - and two calls give the same bits. */
+int cvf_cv_frame_large_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int64_t cvf_cv_frame_large_lds_bytes(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp, int32_t* rows_per_pass);
+int cvf_cv_frame_large_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp, const float* x,
+                            int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
+
 /* --- a trained CV as ONE self-contained file, and its binder (csrc/cv_file.hip; parser and validator: csrc/cvf_cv_file.hpp, host
  * C++ without a HIP include).  colvarsfinder.export.save_cv_file writes it; a C caller reads the bytes, asks for the size of the
  * device buffer, allocates it and binds:

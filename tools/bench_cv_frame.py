@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""xi(x) and d xi / d x for small batches: the one-launch entry cvf_cv_frame_eval (csrc/cv_frame.hip) against the
-three-call recipe cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp_rows, in one process.
+"""xi(x) and d xi / d x for small batches: the one-launch entries cvf_cv_frame_eval (csrc/cv_frame.hip; one wave
+per frame, at most 64 atoms) and cvf_cv_frame_large_eval (csrc/cv_frame_large.hip; one workgroup per frame, any
+size) against the three-call recipe cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp_rows, in one process.
 
   shapes    c3         config 3: 22 atoms, all positions, d_r 66, nets [66,20,20,20,1] x 3
             dipeptide  the dipeptide notebook: 10 atoms, all positions, d_r 30, nets [30,20,20,20,1] x 2
+            mixed1000  1000 atoms, 600 of them aligned, 80 mixed features (d_r 132), nets [132,20,20,1] x 3
+            c5         the config-5 layer: 5000 atoms, d_r 384, nets [384,20,20,1] x 6
   batches   B = 1, 8, 64, 1024
   variants  three_eager   the three calls issued from the host each time
             three_graph   the same launches replayed from one captured hipGraph (single stream) - the yardstick
             frame_eager   cvf_cv_frame_eval issued from the host each time
             frame_graph   the same launch replayed from a graph
+            frame_large_eager, frame_large_graph   the same for cvf_cv_frame_large_eval
+            (a variant whose predicate declines the shape - the wave kernel past 64 atoms - is left out of that shape's row)
 
 Method: HIP events around a window of --replays (200) back-to-back evaluations, time per evaluation = window / replays; per
 round and variant the median of --windows (3) windows; --rounds (3) rounds that alternate the variants; reported per variant: the
@@ -28,23 +33,32 @@ import torch  # noqa: E402
 from colvarsfinder import _hip, core, nn, pp  # noqa: E402
 from tests.synth import make_molecule_traj  # noqa: E402
 
-SHAPES = {"c3": (22, [66, 20, 20, 20, 1], 3), "dipeptide": (10, [30, 20, 20, 20, 1], 2)}
+# (atoms, the nets' hidden dims behind d_r, k, named feature case of tests/test_align_vjp_gpu.case or None = all positions)
+SHAPES = {"c3": (22, [20, 20, 20, 1], 3, None), "dipeptide": (10, [20, 20, 20, 1], 2, None),
+          "mixed1000": (1000, [20, 20, 1], 3, "mixed1000"), "c5": (5000, [20, 20, 1], 6, "c5")}
 BATCHES = (1, 8, 64, 1024)
-VARIANTS = ("three_eager", "three_graph", "frame_eager", "frame_graph")
+VARIANTS = ("three_eager", "three_graph", "frame_eager", "frame_graph", "frame_large_eager", "frame_large_graph")
 
 
 def build(shape, B, dev):
-    """The two routes as closures over preallocated buffers: (three(), frame(), J of each)."""
+    """The routes as closures over preallocated buffers: (three(), frame() or None, large() or None, J of each, buffers)."""
     lib, P = _hip.lib(), _hip.ptr
-    n, dims, k = SHAPES[shape]
+    n, hidden, k, feature_case = SHAPES[shape]
     traj, _, ref = make_molecule_traj(n, B, seed=17)
-    layer = pp.AlignFeatureLayer(n, list(range(n)), ref, [("position", tuple(range(n)))]).to(dev)
+    if feature_case is None:
+        layer = pp.AlignFeatureLayer(n, list(range(n)), ref, [("position", tuple(range(n)))]).to(dev)
+    else:
+        from tests.test_align_vjp_gpu import case
+        _, align, feats, _ = case(feature_case)
+        layer = pp.AlignFeatureLayer(n, align, ref[align], feats).to(dev)
     torch.manual_seed(11)
-    nets = nn.EigenFunctions(dims, k).to(dev)
+    nets = nn.EigenFunctions([layer.d_r] + hidden, k).to(dev)
     mdesc, upto, k, params = core._CVModel._nets_plan(nets)
     theta = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
     pdesc = layer.pp_desc()
-    assert lib.cvf_cv_frame_supported(mdesc, upto, pdesc) == 1, lib.cvf_last_error().decode()
+    has_frame = lib.cvf_cv_frame_supported(mdesc, upto, pdesc) == 1
+    has_large = lib.cvf_cv_frame_large_supported(mdesc, upto, pdesc) == 1
+    assert has_frame or has_large, lib.cvf_last_error().decode()
     x = torch.tensor(traj, device=dev).reshape(B, -1).contiguous()
     T, d_r, nc = _hip.ntiles(B), layer.d_r, 3 * n
     r_t = torch.empty(T, d_r, _hip.TILE, device=dev)
@@ -53,18 +67,24 @@ def build(shape, B, dev):
     ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mdesc, upto, B, 1), device=dev)
     xi3, J3 = torch.empty(B, k, device=dev), torch.empty(B, k, nc, device=dev)
     xi1, J1 = torch.empty(B, k, device=dev), torch.empty(B, k, nc, device=dev)
-    keep = (layer, nets, theta, x, r_t, aux, G, ws)
+    xi2, J2 = torch.empty(B, k, device=dev), torch.empty(B, k, nc, device=dev)
+    scratch = _hip.align_scratch(pdesc, B, dev)   # (None for small molecules)
+    keep = (layer, nets, theta, x, r_t, aux, G, ws, scratch)
 
     def three():
         s = _hip.stream()
-        _hip.check(lib.cvf_align_feature_fwd(pdesc, P(x), B, P(r_t), None, P(aux), None, s), "cvf_align_feature_fwd")
+        _hip.check(lib.cvf_align_feature_fwd(pdesc, P(x), B, P(r_t), None, P(aux), P(scratch), s), "cvf_align_feature_fwd")
         _hip.check(lib.cvf_cv_nets_eval(mdesc, P(theta), upto, None, P(r_t), B, P(xi3), P(G), None, P(ws), s), "cvf_cv_nets_eval")
         _hip.check(lib.cvf_align_feature_vjp_rows(pdesc, P(x), B, P(aux), k, P(G), P(J3), s), "cvf_align_feature_vjp_rows")
 
     def frame():
         _hip.check(lib.cvf_cv_frame_eval(mdesc, P(theta), upto, pdesc, P(x), B, None, P(xi1), P(J1), _hip.stream()), "cvf_cv_frame_eval")
 
-    return three, frame, J3, J1, keep
+    def large():
+        _hip.check(lib.cvf_cv_frame_large_eval(mdesc, P(theta), upto, pdesc, P(x), B, None, P(xi2), P(J2), _hip.stream()),
+                   "cvf_cv_frame_large_eval")
+
+    return three, (frame if has_frame else None), (large if has_large else None), J3, J1, J2, keep
 
 
 def captured(fn):
@@ -98,6 +118,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batches", default=",".join(map(str, BATCHES)), help="comma-separated batch sizes (larger ones locate the crossover)")
+    ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated shapes of SHAPES")
     ap.add_argument("--summary", default=None)
     a = ap.parse_args()
     assert a.replays >= 200 and a.rounds >= 3, "at least 200 replays per window and three rounds"
@@ -105,30 +126,38 @@ def main():
     dev = torch.device("cuda:0")
     out = {"tool": "bench_cv_frame", "replays": a.replays, "windows": a.windows, "rounds": a.rounds, "unit": "us per evaluation",
            "results": {}}
-    lines = [f"{'shape':10s} {'B':>5s} " + " ".join(f"{v:>24s}" for v in VARIANTS) + "   frame_graph / three_graph"]
-    for shape in SHAPES:
+    lines = [f"{'shape':10s} {'B':>5s} " + " ".join(f"{v:>24s}" for v in VARIANTS) + "   frame_graph, frame_large_graph / three_graph"]
+    for shape in [s for s in a.shapes.split(",") if s]:
         for B in [int(b) for b in a.batches.split(",")]:
-            three, frame, J3, J1, keep = build(shape, B, dev)
+            three, frame, large, J3, J1, J2, keep = build(shape, B, dev)
             three()
-            frame()
-            torch.cuda.synchronize()
-            diff = float((J1 - J3).abs().max() / J3.abs().max())
-            three_g, g3 = captured(three)
-            frame_g, g1 = captured(frame)
-            fns = dict(zip(VARIANTS, (three, three_g, frame, frame_g)))
+            diffs = []
+            for fn, J in ((frame, J1), (large, J2)):   # one eager call of every route before any capture
+                if fn is not None:
+                    fn()
+                    torch.cuda.synchronize()
+                    diffs.append(float((J - J3).abs().max() / J3.abs().max()))
+            diff = max(diffs)
+            fns, graphs = {}, []
+            for name, fn in (("three", three), ("frame", frame), ("frame_large", large)):
+                if fn is not None:
+                    replay, g = captured(fn)
+                    graphs.append(g)
+                    fns[name + "_eager"], fns[name + "_graph"] = fn, replay
             for fn in fns.values():          # warm every variant once more behind the captures
                 window_us(fn, 20)
-            rounds = {v: [] for v in VARIANTS}
+            rounds = {v: [] for v in fns}
             for _ in range(a.rounds):
-                for v in VARIANTS:           # the variants alternate inside a round
+                for v in fns:                # the variants alternate inside a round
                     rounds[v].append(statistics.median(window_us(fns[v], a.replays) for _ in range(a.windows)))
             res = {v: {"median": round(statistics.median(t), 3), "min": round(min(t), 3), "max": round(max(t), 3)} for v, t in rounds.items()}
             res["rel_diff_J"] = diff
             out["results"][f"{shape}/B{B}"] = res
-            ratio = res["frame_graph"]["median"] / res["three_graph"]["median"]
+            ratios = " ".join(f"{res[v]['median'] / res['three_graph']['median']:.3f}" if v in res else "    -" for v in ("frame_graph", "frame_large_graph"))
             lines.append(f"{shape:10s} {B:5d} " + " ".join(
-                f"{res[v]['median']:9.2f} [{res[v]['min']:6.2f},{res[v]['max']:6.2f}]" for v in VARIANTS) + f"   {ratio:.3f}   (J rel diff {diff:.1e})")
-            del g3, g1, keep
+                (f"{res[v]['median']:9.2f} [{res[v]['min']:6.2f},{res[v]['max']:6.2f}]" if v in res else f"{'-':>24s}") for v in VARIANTS)
+                + f"   {ratios}   (J rel diff {diff:.1e})")
+            del graphs, fns, keep
     print("\n".join(lines), file=sys.stderr)
     if a.summary:
         with open(a.summary, "w") as f:
