@@ -269,6 +269,16 @@ _SIGNATURES["cvf_cv_file_bind"] = (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, 
 _SIGNATURES["cvf_cv_frame_large_supported"] = (C.c_int, [C.POINTER(MLPDesc), C.c_int, C.POINTER(PPDesc)])
 _SIGNATURES["cvf_cv_frame_large_lds_bytes"] = (C.c_int64, [C.POINTER(MLPDesc), C.c_int, C.POINTER(PPDesc), C.POINTER(C.c_int32)])
 _SIGNATURES["cvf_cv_frame_large_eval"] = _SIGNATURES["cvf_cv_frame_eval"]
+# form C, k scalar chains on one trunk: the argument lists of the namesakes, n_shared for upto_layer
+_SIGNATURES["cvf_cv_nets_shared_supported"] = _SIGNATURES["cvf_cv_nets_supported"]
+_SIGNATURES["cvf_cv_nets_shared_scratch_floats"] = _SIGNATURES["cvf_cv_nets_scratch_floats"]
+_SIGNATURES["cvf_cv_nets_shared_eval"] = _SIGNATURES["cvf_cv_nets_eval"]
+_SIGNATURES["cvf_cv_frame_shared_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+_SIGNATURES["cvf_cv_frame_shared_eval"] = _SIGNATURES["cvf_cv_frame_eval"]
+_SIGNATURES["cvf_cv_frame_large_shared_supported"] = _SIGNATURES["cvf_cv_frame_large_supported"]
+_SIGNATURES["cvf_cv_frame_large_shared_lds_bytes"] = _SIGNATURES["cvf_cv_frame_large_lds_bytes"]
+_SIGNATURES["cvf_cv_frame_large_shared_eval"] = _SIGNATURES["cvf_cv_frame_large_eval"]
+_SIGNATURES["cvf_cv_file_n_shared"] = (C.c_int, [C.c_char_p, C.c_int64])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

@@ -158,7 +158,16 @@ class _CVModel(torch.nn.Sequential):
     (core.py:372-382, 640-647, 855-877), evaluated on the task's GPU whatever device the input lives on.  The reference's
     callers pass CPU tensors made from the trajectory and call ``.detach().numpy()`` on the result (2d.ipynb:437-446,
     main.ipynb:561-562, and ``plot_class.plot(self.colvar_model(), ...)`` at core.py:530-532): the input is moved to the
-    device, alignment kernel and nets run there, the result comes back on the input's device and floating-point type."""
+    device, alignment kernel and nets run there, the result comes back on the input's device and floating-point type.
+
+    ``shared_trunk`` (default ``False``; a settable attribute, ``cv.shared_trunk = True``) opts a model whose ``k`` chains share
+    their first layers - a ``SharedEigenFunctions``, or the ``RegModel`` of ``reg_model()`` - into form C of the evaluation
+    kernels (``cvf_cv_*_shared_*``): the trunk is described, stored and run once.  Then
+    :meth:`nets_route` answers ``("hip", None)`` for both, :meth:`jacobian` / :meth:`metric_tensor` take
+    ``cvf_cv_nets_shared_eval``, and ``export.save_cv_file`` / ``export.FrameCV`` write and evaluate the form-C file.  Models of
+    every other type behave as with ``False``."""
+
+    shared_trunk = False
 
     def __init__(self, *modules, device=None):
         super().__init__(*modules)
@@ -258,10 +267,78 @@ class _CVModel(torch.nn.Sequential):
         if isinstance(pp, AlignFeatureLayer) and pp.derivative_table_limits() is not None:
             return "torch", f"the feature list has {pp.derivative_table_limits()}: the slow route"
         try:
-            self._nets_plan(nets)
+            self._plan(nets)
         except TypeError as e:
             return "torch", str(e)
         return "hip", None
+
+    _SHARED_HINT = ("; shared_trunk = True on the model (cv.shared_trunk = True) takes its trunk-and-heads form on HIP "
+                    "(cvf_cv_nets_shared_eval)")
+
+    def _plan(self, nets):
+        """``(desc, upto_layer, k, params, n_shared)``: :meth:`_nets_plan_shared` for a trunk-and-heads model under
+        ``shared_trunk = True``, else :meth:`_nets_plan` with ``n_shared = 0``.  TypeError with the reason."""
+        if self.shared_trunk and type(nets) in (SharedEigenFunctions, RegModel):
+            desc, L, k, params, ns = self._nets_plan_shared(nets)
+            return desc, L, k, params, ns
+        try:
+            return self._nets_plan(nets) + (0,)
+        except TypeError as e:
+            if type(nets) is RegModel:
+                raise TypeError(str(e) + self._SHARED_HINT) from None
+            raise
+
+    @staticmethod
+    def _nets_plan_shared(nets):
+        """``(desc, n_layers, k, params, n_shared)`` of form C (include/cvf.h: ``cvf_cv_nets_shared_eval``): ``k`` scalar chains
+        whose first ``n_shared`` layers are one set of tensors, every tensor once in ``params`` (the trunk, then head 0, head
+        1, ..) and the trunk's offsets the same for every net.  A ``SharedEigenFunctions`` gives ``n_shared = nets.n_shared``; a
+        ``RegModel`` gives the chains ``encoder + reg[cvec[i]]`` in ``cvec`` order, ``n_shared`` = the encoder's Linear layers.
+        TypeError with the reason for everything else.  Built from the modules on every call, like :meth:`_nets_plan`."""
+        if type(nets) is SharedEigenFunctions:
+            chains, ns = [_strict_chain_layers(net) for net in nets.eigen_funcs], int(nets.n_shared)
+            if any(a[0] is not b[0] for c in chains for a, b in zip(c[:ns], chains[0][:ns])):
+                raise TypeError(f"the first {ns} Linear layers of the eigenfunctions are not the same modules")
+        elif type(nets) is RegModel:
+            if nets.reg is None or len(nets.cvec) < 1:
+                raise TypeError("the RegModel has no regulariser nets")
+            trunk = _strict_chain_layers(nets.encoder)
+            heads = [_strict_chain_layers(nets.reg[int(i)]) for i in nets.cvec]
+            chains, ns = [trunk + h for h in heads], len(trunk)
+            if trunk[-1][0].out_features != heads[0][0][0].in_features:
+                raise TypeError(f"the encoder has {trunk[-1][0].out_features} outputs, the regulariser nets take {heads[0][0][0].in_features}")
+        else:
+            raise TypeError(f"the nets are a {type(nets).__name__}: cvf_cv_nets_shared_eval takes a SharedEigenFunctions or a RegModel")
+        shape = lambda c: [(lin.in_features, lin.out_features, act) for lin, act in c]
+        if any(shape(c) != shape(chains[0]) for c in chains):
+            raise TypeError("the nets behind the trunk differ in architecture")
+        L, k = len(chains[0]), len(chains)
+        if not 1 <= k <= _hip.MAX_NETS:
+            raise TypeError(f"k = {k} nets: the kernels take 1 to {_hip.MAX_NETS}")
+        if L > _hip.MAX_LAYERS:
+            raise TypeError(f"{L} layers: the kernels take 1 to {_hip.MAX_LAYERS}")
+        if chains[0][-1][0].out_features != 1:
+            raise TypeError(f"the nets behind the trunk must be scalar (they have {chains[0][-1][0].out_features} outputs each)")
+        d, params, pos = _hip.MLPDesc(), [], 0
+        d.n_nets, d.n_layers = k, L
+        for l, (fin, fout, act) in enumerate(shape(chains[0])):
+            d.dims[l], d.dims[l + 1], d.act[l] = fin, fout, act
+        for l, (lin, _) in enumerate(chains[0][:ns]):   # the trunk once, under the same offsets for every net
+            for i in range(k):
+                d.w_off[i][l], d.b_off[i][l] = pos, pos + lin.weight.numel()
+            pos += lin.weight.numel() + lin.bias.numel()
+            params += [lin.weight, lin.bias]
+        for i, chain in enumerate(chains):
+            for l, (lin, _) in enumerate(chain[ns:], start=ns):
+                d.w_off[i][l], d.b_off[i][l] = pos, pos + lin.weight.numel()
+                pos += lin.weight.numel() + lin.bias.numel()
+                params += [lin.weight, lin.bias]
+        if pos >= 2 ** 31:
+            raise TypeError(f"{pos} parameters: cvf_mlp_desc holds 32-bit offsets")
+        d.n_params = pos
+        if _hip.lib().cvf_cv_nets_shared_supported(d, ns, 1) != 1:
+            raise TypeError(_hip.lib().cvf_last_error().decode())
+        return d, L, k, params, ns
 
     @staticmethod
     def _nets_plan(nets):
@@ -316,7 +393,7 @@ class _CVModel(torch.nn.Sequential):
         plan = None
         if hip_route:
             try:
-                plan = self._nets_plan(nets)
+                plan = self._plan(nets)
             except TypeError:
                 pass    # (nets_route() names the reason) the nets' part by torch.func
         with torch.cuda.device(dev):
@@ -371,7 +448,7 @@ class _CVModel(torch.nn.Sequential):
         if plan is not None:
             # fp32 per frame: x, features, aux, d xi / d r and q (one layout each), J rows or M, the nets' launch-to-launch images
             per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 2 * k * d_r + k * n + k * k) \
-                + 4 * _hip.lib().cvf_cv_nets_scratch_floats(plan[0], plan[1], _hip.TILE, 1) // _hip.TILE
+                + 4 * self._nets_scratch_floats(plan, _hip.TILE) // _hip.TILE
         else:
             # fp32 per frame: x, features, aux, d xi / d r (rows, padded tiles, q), J rows or M, and torch.func's temporaries
             per = 4 * (2 * n + d_r + _hip.AUX_ROWS + 6 * k * d_r + k * n + k * k) + 64 * k * d_r
@@ -379,9 +456,18 @@ class _CVModel(torch.nn.Sequential):
         c = int(self.JACOBIAN_MEMORY_FRACTION * free) // per // _hip.TILE * _hip.TILE
         return max(_hip.TILE, min(c, B))
 
+    @staticmethod
+    def _nets_scratch_floats(plan, B):
+        """Floats of the nets' scratch for ``B`` frames: the formula of the plan's form (``plan[4]``: n_shared, 0 = forms A and B)."""
+        lib = _hip.lib()
+        if plan[4] > 0:
+            return lib.cvf_cv_nets_shared_scratch_floats(plan[0], plan[4], B, 1)
+        return lib.cvf_cv_nets_scratch_floats(plan[0], plan[1], B, 1)
+
     def _hip_chunk(self, xs, pp, nets, k, want_m, a_dev, dense, dev, plan=None, theta=None):
         """One chunk on the HIP route: (xi [c, k], J rows [c, k, n] or M [c, k, k]), fp32 on the device.  With a ``plan``
-        (``_nets_plan``; ``theta``: the flat parameters) the nets' part comes from ``cvf_cv_nets_eval``, else from ``torch.func``."""
+        (``_plan``; ``theta``: the flat parameters) the nets' part comes from ``cvf_cv_nets_eval`` (``cvf_cv_nets_shared_eval`` for a
+        form-C plan), else from ``torch.func``."""
         lib, P, s = _hip.lib(), _hip.ptr, _hip.stream()
         c = int(xs.shape[0])
         x = xs.detach().to(device=dev, dtype=torch.float32).reshape(c, -1).contiguous()
@@ -406,8 +492,12 @@ class _CVModel(torch.nn.Sequential):
             xi = torch.empty(c, k, device=dev, dtype=torch.float32)
             G = None if want_m else torch.empty(c, k, d_r, device=dev, dtype=torch.float32)
             g_t = torch.empty(T, k, d_r, _hip.TILE, device=dev, dtype=torch.float32) if want_m else None
-            ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mdesc, upto, c, 1), device=dev, dtype=torch.float32)
-            _hip.check(lib.cvf_cv_nets_eval(mdesc, P(theta), upto, P(r), P(r_t), c, P(xi), P(G), P(g_t), P(ws), s), "cvf_cv_nets_eval")
+            ws = torch.empty(self._nets_scratch_floats(plan, c), device=dev, dtype=torch.float32)
+            if plan[4] > 0:   # form C: the trunk once
+                _hip.check(lib.cvf_cv_nets_shared_eval(mdesc, P(theta), plan[4], P(r), P(r_t), c, P(xi), P(G), P(g_t), P(ws), s),
+                           "cvf_cv_nets_shared_eval")
+            else:
+                _hip.check(lib.cvf_cv_nets_eval(mdesc, P(theta), upto, P(r), P(r_t), c, P(xi), P(G), P(g_t), P(ws), s), "cvf_cv_nets_eval")
             if not want_m:
                 J = torch.empty(c, k, n, device=dev, dtype=torch.float32)
                 _hip.check(lib.cvf_align_feature_vjp_rows(desc, P(x), c, P(aux), k, P(G), P(J), s), "cvf_align_feature_vjp_rows")

@@ -116,9 +116,9 @@ CV_FILE_TABLES = (("align_idx", 1, 0), ("ref_c", 2, 1), ("rec", 3, 0), ("align_w
 
 
 def _cv_parts(cv):
-    """``(pp scalars dict, tables dict of CPU numpy arrays, MLPDesc, upto_layer, k)`` of a ``colvar_model()``."""
+    """``(pp scalars dict, tables dict of CPU numpy arrays, MLPDesc, upto_layer, k, n_shared)`` of a ``colvar_model()`` /
+    ``reg_model()`` (``n_shared > 0``: form C, under ``cv.shared_trunk = True``)."""
     import numpy as np
-    from .core import _CVModel
     from .pp import AlignFeatureLayer
     if not hasattr(cv, "_pp_and_nets"):
         raise NotImplementedError(f"save_cv_file takes what colvar_model() returns, got a {type(cv).__name__}")
@@ -127,7 +127,7 @@ def _cv_parts(cv):
         raise NotImplementedError(f"the preprocessing layer is a {type(pp).__name__}: a CV file holds an Identity or an "
                                   "AlignFeatureLayer (a foreign pp_layer has no tables to write)")
     try:
-        desc, upto, k, params = _CVModel._nets_plan(nets)
+        desc, upto, k, params, n_shared = cv._plan(nets)
     except TypeError as e:
         raise NotImplementedError(str(e)) from e
     theta = torch.cat([p.detach().to(device="cpu", dtype=torch.float32).reshape(-1) for p in params]).numpy()
@@ -151,17 +151,17 @@ def _cv_parts(cv):
                     atom_slot=i32(pp.atom_slot), rec_slot=i32(pp.rec_slot), slot_atom=i32(pp.slot_atom),
                     mrec=i32(pp.mrec) if with_rows else empty_i, slot_row=i32(pp.slot_row) if with_rows else empty_i)
     tabs["theta"] = theta
-    return sc, tabs, desc, int(upto), int(k)
+    return sc, tabs, desc, int(upto), int(k), int(n_shared)
 
 
 def cv_file_bytes(cv) -> bytes:
     """The bytes :func:`save_cv_file` writes (layout: include/cvf.h, ``cvf_cv_file_*``)."""
     import struct
-    sc, tabs, desc, upto, k = _cv_parts(cv)
+    sc, tabs, desc, upto, k, n_shared = _cv_parts(cv)
     head = CV_FILE_MAGIC + struct.pack("<3i", CV_FILE_VERSION, _hip.MAX_NETS, _hip.MAX_LAYERS) + bytes(desc)
     head += struct.pack("<12i", *(sc[f] for f in ("mode", "n_coord", "n_align", "n_rec", "d_r", "use_angle_value", "has_position",
                                                   "flags", "n_slot", "n_rec_slot", "n_mrec", "n_ref")))
-    head += struct.pack("<4i", upto, k, len(CV_FILE_TABLES), 0)
+    head += struct.pack("<4i", upto, k, len(CV_FILE_TABLES), n_shared)
     assert len(head) == CV_FILE_DIR_OFFSET
     pos = (CV_FILE_DIR_OFFSET + 24 * len(CV_FILE_TABLES) + 15) // 16 * 16
     directory, body = b"", b""
@@ -181,8 +181,10 @@ def save_cv_file(cv, path):
     """Write ``colvar_model()`` as ONE self-contained little-endian file a C caller binds with ``cvf_cv_file_bind`` and evaluates
     with ``cvf_cv_frame_eval`` - the nets' flat parameters and description and ALL tables of the preprocessing layer, so that the
     bound model also feeds the three-call recipe.  ``NotImplementedError`` (with the reason) for models the HIP nets' kernels do
-    not describe: a ``RegModel``, foreign modules, a foreign ``pp_layer``.  ``save_model`` and its TorchScript files are a
-    different artefact and are not touched."""
+    not describe: a ``RegModel`` without ``shared_trunk``, foreign modules, a foreign ``pp_layer``.  With ``cv.shared_trunk = True``
+    a ``SharedEigenFunctions`` model and the ``RegModel`` of ``reg_model()`` are written in form C (``n_shared > 0`` at byte 956,
+    ``theta`` with the trunk once; a C caller asks ``cvf_cv_file_n_shared`` and evaluates with ``cvf_cv_frame_shared_eval``).
+    ``save_model`` and its TorchScript files are a different artefact and are not touched."""
     blob = cv_file_bytes(cv)
     with open(path, "wb") as f:
         f.write(blob)
@@ -205,7 +207,11 @@ class FrameCV:
     DESIGN.md section 4.16): the route is ``"frame"`` where the wave kernel takes the model, else ``"frame-large"`` where
     ``cvf_cv_frame_large_supported`` does, else ``"three-call"``.  ``fc.supported_large`` is ``(bool, reason)`` of that predicate
     (asked with or without the option; ``fc.supported`` keeps its meaning).  Section 4.16 gives the measured times of both routes
-    and the batch size at which they meet; the default stays ``False``."""
+    and the batch size at which they meet; the default stays ``False``.
+
+    ``fc.n_shared`` is the file's ``n_shared`` (``cvf_cv_file_n_shared``).  With ``n_shared > 0`` (form C, DESIGN.md section
+    4.17) the predicates and launches are the ``_shared`` ones and the three-call recipe runs ``cvf_cv_nets_shared_eval``;
+    ``route``, ``supported`` and ``supported_large`` keep their meaning."""
 
     def __init__(self, path_or_cv, device="cuda", large_frames=False):
         import ctypes as C
@@ -225,9 +231,19 @@ class FrameCV:
             _hip.check(lib.cvf_cv_file_bind(blob, len(blob), C.c_void_p(self._buf.data_ptr()), need, C.byref(self.model),
                                             _hip.stream()), "cvf_cv_file_bind")
         self.k, self.n_coord, self.d_r = int(self.model.k), int(self.model.pp.n_coord), int(self.model.pp.d_r)
-        ok = lib.cvf_cv_frame_supported(C.byref(self.model.mlp), self.model.upto_layer, C.byref(self.model.pp)) == 1
+        self.n_shared = int(lib.cvf_cv_file_n_shared(blob, len(blob)))
+        # form C: the _shared entry points take n_shared where their namesakes take upto_layer
+        sh = self.n_shared > 0
+        self._cut = self.n_shared if sh else int(self.model.upto_layer)
+        self._frame_eval = lib.cvf_cv_frame_shared_eval if sh else lib.cvf_cv_frame_eval
+        self._large_eval = lib.cvf_cv_frame_large_shared_eval if sh else lib.cvf_cv_frame_large_eval
+        self._nets_scratch = lib.cvf_cv_nets_shared_scratch_floats if sh else lib.cvf_cv_nets_scratch_floats
+        self._nets_eval = lib.cvf_cv_nets_shared_eval if sh else lib.cvf_cv_nets_eval
+        frame_ok = lib.cvf_cv_frame_shared_supported if sh else lib.cvf_cv_frame_supported
+        large_ok = lib.cvf_cv_frame_large_shared_supported if sh else lib.cvf_cv_frame_large_supported
+        ok = frame_ok(C.byref(self.model.mlp), self._cut, C.byref(self.model.pp)) == 1
         self.supported = (ok, None if ok else lib.cvf_last_error().decode())
-        ok_large = lib.cvf_cv_frame_large_supported(C.byref(self.model.mlp), self.model.upto_layer, C.byref(self.model.pp)) == 1
+        ok_large = large_ok(C.byref(self.model.mlp), self._cut, C.byref(self.model.pp)) == 1
         self.supported_large = (ok_large, None if ok_large else lib.cvf_last_error().decode())
         self.route = "frame" if ok else ("frame-large" if large_frames and ok_large else "three-call")
 
@@ -249,18 +265,18 @@ class FrameCV:
             xi = torch.empty(B, k, device=dev, dtype=torch.float32)
             D = torch.empty((B, n) if cf is not None else (B, k, n), device=dev, dtype=torch.float32)
             if B > 0 and self.route == "frame":
-                _hip.check(lib.cvf_cv_frame_eval(C.byref(m.mlp), C.c_void_p(m.theta), m.upto_layer, C.byref(m.pp), P(x), B, P(cf),
-                                                 P(xi), P(D), s), "cvf_cv_frame_eval")
+                _hip.check(self._frame_eval(C.byref(m.mlp), C.c_void_p(m.theta), self._cut, C.byref(m.pp), P(x), B, P(cf),
+                                            P(xi), P(D), s), self._frame_eval.__name__)
             elif B > 0 and self.route == "frame-large":
-                _hip.check(lib.cvf_cv_frame_large_eval(C.byref(m.mlp), C.c_void_p(m.theta), m.upto_layer, C.byref(m.pp), P(x), B, P(cf),
-                                                       P(xi), P(D), s), "cvf_cv_frame_large_eval")
+                _hip.check(self._large_eval(C.byref(m.mlp), C.c_void_p(m.theta), self._cut, C.byref(m.pp), P(x), B, P(cf),
+                                            P(xi), P(D), s), self._large_eval.__name__)
             elif B > 0:
                 self._three_call(x, cf, xi, D, s)
         D = D.reshape(((B,) if cf is not None else (B, k)) + frame_shape)
         return xi.to(device=src_dev, dtype=src_dt), D.to(device=src_dev, dtype=src_dt)
 
     def _three_call(self, x, cf, xi, D, s):
-        """cvf_align_feature_fwd -> cvf_cv_nets_eval -> cvf_align_feature_vjp[_rows] on the bound model."""
+        """cvf_align_feature_fwd -> cvf_cv_nets_eval (form C: cvf_cv_nets_shared_eval) -> cvf_align_feature_vjp[_rows] on the bound model."""
         import ctypes as C
         lib, P, m, dev = _hip.lib(), _hip.ptr, self.model, self.device
         B, k, d_r, T = int(x.shape[0]), self.k, self.d_r, _hip.ntiles(int(x.shape[0]))
@@ -274,8 +290,8 @@ class FrameCV:
             scratch = _hip.align_scratch(m.pp, B, dev)
             _hip.check(lib.cvf_align_feature_fwd(pp, P(x), B, P(r_t), None, P(aux), P(scratch), s), "cvf_align_feature_fwd")
         G = torch.empty(B, k, d_r, device=dev, dtype=torch.float32)
-        ws = torch.empty(lib.cvf_cv_nets_scratch_floats(mlp, m.upto_layer, B, 1), device=dev, dtype=torch.float32)
-        _hip.check(lib.cvf_cv_nets_eval(mlp, theta, m.upto_layer, P(r), P(r_t), B, P(xi), P(G), None, P(ws), s), "cvf_cv_nets_eval")
+        ws = torch.empty(self._nets_scratch(mlp, self._cut, B, 1), device=dev, dtype=torch.float32)
+        _hip.check(self._nets_eval(mlp, theta, self._cut, P(r), P(r_t), B, P(xi), P(G), None, P(ws), s), self._nets_eval.__name__)
         if cf is None:
             _hip.check(lib.cvf_align_feature_vjp_rows(pp, P(x), B, P(aux), k, P(G), P(D), s), "cvf_align_feature_vjp_rows")
         else:   # the contraction at the feature level (k terms per feature), then one coordinate pass

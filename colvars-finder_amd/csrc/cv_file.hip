@@ -1,6 +1,6 @@
-// The binder of the CV model file (include/cvf.h: cvf_cv_file_device_bytes, cvf_cv_file_bind).  All the
-// reading and checking is cvf_cv_file.hpp's (host C++, shared with the stand-alone checker); this file adds the one
-// host-to-device copy of the table region and the descriptors over it.
+// The binder of the CV model file (include/cvf.h: cvf_cv_file_device_bytes, cvf_cv_file_bind, cvf_cv_file_n_shared; DESIGN.md
+// sections 4.15 and 4.17).  All the reading and checking is cvf_cv_file.hpp's (host C++, shared with the stand-alone checkers);
+// this file adds the one host-to-device copy of the table region and the descriptors over it.
 #include "cvf_common.hpp"
 #include "cvf_cv_file.hpp"
 
@@ -37,4 +37,15 @@ extern "C" int cvf_cv_file_bind(const void* blob_host, int64_t nbytes, void* dev
   CVF_REQUIRE(e == hipSuccess, "cvf_cv_file_bind: %s", hipGetErrorString(e));
   cvf_file::fill_model(v, static_cast<const unsigned char*>(dev_buf), out);
   return 0;
+}
+
+extern "C" int cvf_cv_file_n_shared(const void* blob_host, int64_t nbytes) {
+  cvf_file::View v;
+  char err[320];
+  const int rc = cvf_file::parse(blob_host, nbytes, &v, err, sizeof err);
+  if (rc != 0) {
+    cvf_set_error("cvf_cv_file_n_shared: %s", err);
+    return rc;
+  }
+  return v.n_shared;
 }

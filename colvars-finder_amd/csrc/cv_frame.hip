@@ -19,6 +19,13 @@
 // the batch, so its result depends on its coordinates and theta only, bit for bit.
 // The three-call recipe remains the route for large batches, large molecules and wide nets: a wave here does for ONE frame the
 // table reads, weight reads and solver instructions that a 64-frame tile shares there.
+//
+// Form C (cvf_cv_frame_shared_*): k scalar chains on one trunk of n_shared layers.  The trunk's
+// activations are held ONCE, its forward pass strides dims[l+1] units over the lanes (k * dims[l+1] above it), the k head sweeps
+// stop at layer n_shared, and below it the k vectors (or, with coef, their one sum taken at the boundary) are carried through
+// the shared weights together, unit (vector, input) over the lanes.  A row's arithmetic is that of form A.
+#include "cvf_cv_shared.hpp"
+#include "cvf_cv_shared_sweep.hpp"
 #include "cvf_features.hpp"
 #include "cvf_metric.hpp"
 
@@ -35,8 +42,11 @@ struct FrLayout {
   int a[CVF_MAX_LAYERS + 1];   // layer l's activations, [chain][dims[l]] (a[0]: the features, shared by the chains)
   int xs, v0, v1, g, ctab, gimg, zs, total;
   int L, k, nn, form_a;
+  int ns, t0, t1;              // form C: the trunk's layers (a[1..ns] hold one chain), two images [vector][width] of its sweep
 };
 
+// SHARED: form C (an instance of its own: forms A and B keep their code)
+template <bool SHARED>
 __global__ __launch_bounds__(64) void cv_frame_kernel(cvf_mlp_desc mlp, cvf_pp_desc pp, FrLayout lay,
                                                        const float* __restrict__ theta, const float* __restrict__ x,
                                                        const float* __restrict__ coef, float* __restrict__ xi_rows,
@@ -110,10 +120,11 @@ __global__ __launch_bounds__(64) void cv_frame_kernel(cvf_mlp_desc mlp, cvf_pp_d
     const int din = mlp.dims[l], dout = mlp.dims[l + 1], act = mlp.act[l];
     const float* ain = lds + lay.a[l];
     float* aout = lds + lay.a[l + 1];
-    for (int u = lane; u < nn * dout; u += CVF_WAVE) {
+    const int nch = SHARED && l < lay.ns ? 1 : nn;   // (the trunk runs once)
+    for (int u = lane; u < nch * dout; u += CVF_WAVE) {
       const int ch = u / dout, j = u - ch * dout;
       const float* w = theta + mlp.w_off[ch][l] + (int64_t)j * din;
-      const float* ai = ain + (l == 0 ? 0 : ch * din);
+      const float* ai = ain + (l == 0 || (SHARED && l <= lay.ns) ? 0 : ch * din);
       float acc = 0.0f;
 #pragma unroll 4
       for (int i = 0; i < din; ++i) acc = fmaf(w[i], ai[i], acc);
@@ -128,7 +139,11 @@ __global__ __launch_bounds__(64) void cv_frame_kernel(cvf_mlp_desc mlp, cvf_pp_d
 
   // ---- sweep: one per CV, or one per chain with the coefficient as the seed
   float* g = lds + lay.g;
-  const int nsweep = lay.form_a ? k : kk;
+  if (SHARED) {   // form C: the heads down to the boundary, then the kk vectors through the trunk together
+    const CvfFormCLds fl = {lay.a, lay.v0, lay.v1, lay.t0, lay.t1, lay.g};
+    cvf_form_c_sweep<CVF_WAVE>(mlp, theta, coef != nullptr ? coef + frame * k : nullptr, lds, fl, L, k, lay.ns, lane);
+  }
+  const int nsweep = SHARED ? 0 : (lay.form_a ? k : kk);
   for (int s = 0; s < nsweep; ++s) {
     const int ch = lay.form_a ? s : 0;
     float* grow = g + (coef != nullptr ? 0 : s) * d0;
@@ -266,8 +281,9 @@ __global__ __launch_bounds__(64) void cv_frame_kernel(cvf_mlp_desc mlp, cvf_pp_d
   for (int e = lane; e < kk * nc; e += CVF_WAVE) out[e] = gimg[e];
 }
 
-// nullptr and *lay filled, or why the launch declines the model
-const char* cvfr_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, FrLayout* lay) {
+// nullptr and *lay filled, or why the launch declines the model (ns > 0: form C, which the caller has checked with
+// cvf_form_c_why - k = n_nets scalar chains, whole, the first ns layers one trunk)
+const char* cvfr_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, FrLayout* lay, int ns = 0) {
   static thread_local char buf[320];
 #define CVFR_NO(...)                                              \
   do {                                                            \
@@ -279,7 +295,7 @@ const char* cvfr_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, F
   if (mlp->n_nets < 1 || mlp->n_nets > CVF_MAX_NETS) CVFR_NO("%d nets: 1 to %d are supported", mlp->n_nets, CVF_MAX_NETS);
   if (mlp->n_layers < 1 || mlp->n_layers > CVF_MAX_LAYERS) CVFR_NO("%d layers: 1 to %d are supported", mlp->n_layers, CVF_MAX_LAYERS);
   if (upto < 1 || upto > mlp->n_layers) CVFR_NO("upto_layer=%d out of range (the model has %d layers)", upto, mlp->n_layers);
-  const bool form_a = mlp->n_nets > 1;
+  const bool form_a = mlp->n_nets > 1 || ns > 0;
   if (form_a && upto != mlp->n_layers) CVFR_NO("%d nets side by side are evaluated whole: upto_layer must be %d", mlp->n_nets, mlp->n_layers);
   if (form_a && mlp->dims[upto] != 1) CVFR_NO("%d nets side by side must be scalar (they have %d outputs each)", mlp->n_nets, mlp->dims[upto]);
   const int k = form_a ? mlp->n_nets : mlp->dims[upto];
@@ -310,21 +326,24 @@ const char* cvfr_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, F
   if (mlp->dims[0] != pp->d_r) CVFR_NO("the nets take %d features, the preprocessing layer gives %d", mlp->dims[0], pp->d_r);
   // the LDS of one frame
   FrLayout L = {};
-  L.L = upto; L.k = k; L.nn = nn; L.form_a = form_a ? 1 : 0;
+  L.L = upto; L.k = k; L.nn = nn; L.form_a = form_a ? 1 : 0; L.ns = ns;
   const bool identity = pp->mode == CVF_PP_IDENTITY;
   int64_t pos = 0;
   L.xs = 0;
   pos += nc;
   L.a[0] = identity ? 0 : (int)pos;
   if (!identity) pos += mlp->dims[0];
-  int vmax = 1;
+  int vmax = 1, tmax = 0;   // the widest image of a head's sweep (forms A and B: of the sweep), of the trunk's
   for (int l = 1; l <= upto; ++l) {
     L.a[l] = (int)pos;
-    pos += (int64_t)nn * mlp->dims[l];
-    vmax = mlp->dims[l] > vmax ? mlp->dims[l] : vmax;
+    pos += (int64_t)(l <= ns ? 1 : nn) * mlp->dims[l];
+    if (l > ns) vmax = mlp->dims[l] > vmax ? mlp->dims[l] : vmax;
+    else tmax = mlp->dims[l] > tmax ? mlp->dims[l] : tmax;
   }
   L.v0 = (int)pos; pos += vmax;
   L.v1 = (int)pos; pos += vmax;
+  L.t0 = (int)pos; pos += (int64_t)k * tmax;
+  L.t1 = (int)pos; pos += (int64_t)k * tmax;
   L.g = (int)pos; pos += (int64_t)k * mlp->dims[0];
   if (!identity) {
     L.ctab = (int)pos; pos += (int64_t)k * pp->n_rec * 12;
@@ -358,8 +377,40 @@ extern "C" int cvf_cv_frame_eval(const cvf_mlp_desc* mlp, const float* theta, in
   if (B == 0) return 0;
   CVF_REQUIRE(theta && x && xi_rows && gx_rows, "cvf_cv_frame_eval: null argument");
   const size_t lds = (size_t)lay.total * sizeof(float);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)cv_frame_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(cv_frame_kernel, dim3((unsigned)B), dim3(CVF_WAVE), lds, (hipStream_t)stream, *mlp, *pp, lay, theta, x, coef,
-                     xi_rows, gx_rows);
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)cv_frame_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(cv_frame_kernel<false>, dim3((unsigned)B), dim3(CVF_WAVE), lds, (hipStream_t)stream, *mlp, *pp, lay, theta, x,
+                     coef, xi_rows, gx_rows);
   return cvf_check_launch("cv_frame_kernel");
+}
+
+namespace {
+const char* cvfr_shared_why(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp, FrLayout* lay) {
+  static thread_local char buf[240];
+  const char* why = cvf_form_c_why(mlp, n_shared, "cvf_cv_frame_eval", buf, sizeof buf);
+  return why != nullptr ? why : cvfr_why(mlp, mlp->n_layers, pp, lay, n_shared);
+}
+}  // namespace
+
+extern "C" int cvf_cv_frame_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp) {
+  const char* why = cvfr_shared_why(mlp, n_shared, pp, nullptr);
+  if (why != nullptr) {
+    cvf_set_error("cvf_cv_frame_shared: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int cvf_cv_frame_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                        const float* x, int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream) {
+  FrLayout lay;
+  const char* why = cvfr_shared_why(mlp, n_shared, pp, &lay);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_frame_shared_eval: %s", why);
+  CVF_REQUIRE(B >= 0 && B <= 0x7fffffff, "cvf_cv_frame_shared_eval: B = %lld frames (one call takes 0 to 2^31 - 1)", (long long)B);
+  if (B == 0) return 0;
+  CVF_REQUIRE(theta && x && xi_rows && gx_rows, "cvf_cv_frame_shared_eval: null argument");
+  const size_t lds = (size_t)lay.total * sizeof(float);
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)cv_frame_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(cv_frame_kernel<true>, dim3((unsigned)B), dim3(CVF_WAVE), lds, (hipStream_t)stream, *mlp, *pp, lay, theta, x,
+                     coef, xi_rows, gx_rows);
+  return cvf_check_launch("cv_frame_kernel<shared>");
 }

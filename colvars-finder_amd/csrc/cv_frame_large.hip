@@ -22,6 +22,12 @@
 //
 // No atomics, no scratch, no aux.  A frame meets the same instructions in the same order whatever B is, wherever it sits in the
 // batch and whichever pass a row falls in, so its result depends on its coordinates and theta only, bit for bit.
+//
+// Form C (cvf_cv_frame_large_shared_*) as in csrc/cv_frame.hip: the trunk's activations once, its forward
+// pass dims[l+1] units over the threads, the k head sweeps down to layer n_shared, the k vectors (with coef: their one sum)
+// through the shared weights together.
+#include "cvf_cv_shared.hpp"
+#include "cvf_cv_shared_sweep.hpp"
 #include "cvf_features.hpp"
 #include "cvf_metric.hpp"
 
@@ -40,6 +46,7 @@ struct LgLayout {
   int v0, v1, g, redd, redf, zs, rows, total;
   int L, k, nn, form_a;
   int rpp;                     // cotangent rows per pass of the coordinate part (1 .. k)
+  int ns, t0, t1;              // form C: the trunk's layers (a[1..ns] hold one chain), two images [vector][width] of its sweep
 };
 
 struct MRec {
@@ -61,8 +68,8 @@ __device__ __forceinline__ MRec load_mrec(const int32_t* mrec, int r) {   // inc
 }
 
 // MODE: 0 CVF_PP_FEATURES, 1 CVF_PP_ALIGN with uniform weights, 2 CVF_PP_ALIGN with align_w (instances, not branches: the uniform
-// values of the other modes stay out of the scalar registers)
-template <bool VEC4, int MODE>
+// values of the other modes stay out of the scalar registers); SHARED: form C
+template <bool VEC4, int MODE, bool SHARED>
 __global__ __launch_bounds__(kThreads) void cv_frame_large_kernel(cvf_mlp_desc mlp, cvf_pp_desc pp, LgLayout lay,
                                                                   const float* __restrict__ theta, const float* __restrict__ x,
                                                                   const float* __restrict__ coef, float* __restrict__ xi_rows,
@@ -158,10 +165,11 @@ __global__ __launch_bounds__(kThreads) void cv_frame_large_kernel(cvf_mlp_desc m
     const int din = mlp.dims[l], dout = mlp.dims[l + 1], act = mlp.act[l];
     const float* ain = lds + lay.a[l];
     float* aout = lds + lay.a[l + 1];
-    for (int u = tid; u < nn * dout; u += kThreads) {
+    const int nch = SHARED && l < lay.ns ? 1 : nn;   // (the trunk runs once)
+    for (int u = tid; u < nch * dout; u += kThreads) {
       const int ch = u / dout, j = u - ch * dout;
       const float* w = theta + mlp.w_off[ch][l] + (int64_t)j * din;
-      const float* ai = ain + (l == 0 ? 0 : ch * din);
+      const float* ai = ain + (l == 0 || (SHARED && l <= lay.ns) ? 0 : ch * din);
       float acc = 0.0f;
 #pragma unroll 8
       for (int i = 0; i < din; ++i) acc = fmaf(w[i], ai[i], acc);
@@ -176,7 +184,11 @@ __global__ __launch_bounds__(kThreads) void cv_frame_large_kernel(cvf_mlp_desc m
 
   // ---- sweep: one per CV, or one per chain with the coefficient as the seed
   float* g = lds + lay.g;
-  const int nsweep = lay.form_a ? k : kk;
+  if (SHARED) {   // form C: the heads down to the boundary, then the kk vectors through the trunk together
+    const CvfFormCLds fl = {lay.a, lay.v0, lay.v1, lay.t0, lay.t1, lay.g};
+    cvf_form_c_sweep<kThreads>(mlp, theta, coef != nullptr ? coef + frame * k : nullptr, lds, fl, L, k, lay.ns, tid);
+  }
+  const int nsweep = SHARED ? 0 : (lay.form_a ? k : kk);
   for (int s = 0; s < nsweep; ++s) {
     const int ch = lay.form_a ? s : 0;
     float* grow = g + (coef != nullptr ? 0 : s) * d0;
@@ -348,8 +360,9 @@ __global__ __launch_bounds__(kThreads) void cv_frame_large_kernel(cvf_mlp_desc m
   }
 }
 
-// nullptr and *lay filled, or why the launch declines the model
-const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, LgLayout* lay) {
+// nullptr and *lay filled, or why the launch declines the model (ns > 0: form C, which the caller has checked with
+// cvf_form_c_why)
+const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, LgLayout* lay, int ns = 0) {
   static thread_local char buf[360];
 #define CVFL_NO(...)                                              \
   do {                                                            \
@@ -362,7 +375,7 @@ const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, L
   if (mlp->n_nets < 1 || mlp->n_nets > CVF_MAX_NETS) CVFL_NO("%d nets: 1 to %d are supported", mlp->n_nets, CVF_MAX_NETS);
   if (mlp->n_layers < 1 || mlp->n_layers > CVF_MAX_LAYERS) CVFL_NO("%d layers: 1 to %d are supported", mlp->n_layers, CVF_MAX_LAYERS);
   if (upto < 1 || upto > mlp->n_layers) CVFL_NO("upto_layer=%d out of range (the model has %d layers)", upto, mlp->n_layers);
-  const bool form_a = mlp->n_nets > 1;
+  const bool form_a = mlp->n_nets > 1 || ns > 0;
   if (form_a && upto != mlp->n_layers) CVFL_NO("%d nets side by side are evaluated whole: upto_layer must be %d", mlp->n_nets, mlp->n_layers);
   if (form_a && mlp->dims[upto] != 1) CVFL_NO("%d nets side by side must be scalar (they have %d outputs each)", mlp->n_nets, mlp->dims[upto]);
   const int k = form_a ? mlp->n_nets : mlp->dims[upto];
@@ -396,18 +409,21 @@ const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, L
   if (mlp->dims[0] != pp->d_r) CVFL_NO("the nets take %d features, the preprocessing layer gives %d", mlp->dims[0], pp->d_r);
   // the LDS of one frame
   LgLayout Y = {};
-  Y.L = upto; Y.k = k; Y.nn = nn; Y.form_a = form_a ? 1 : 0;
+  Y.L = upto; Y.k = k; Y.nn = nn; Y.form_a = form_a ? 1 : 0; Y.ns = ns;
   int64_t pos = 0;
   Y.a[0] = 0;
   pos += mlp->dims[0];
-  int vmax = 1;
+  int vmax = 1, tmax = 0;   // the widest image of a head's sweep (forms A and B: of the sweep), of the trunk's
   for (int l = 1; l <= upto; ++l) {
     Y.a[l] = (int)pos;
-    pos += (int64_t)nn * mlp->dims[l];
-    vmax = mlp->dims[l] > vmax ? mlp->dims[l] : vmax;
+    pos += (int64_t)(l <= ns ? 1 : nn) * mlp->dims[l];
+    if (l > ns) vmax = mlp->dims[l] > vmax ? mlp->dims[l] : vmax;
+    else tmax = mlp->dims[l] > tmax ? mlp->dims[l] : tmax;
   }
   Y.v0 = (int)pos; pos += vmax;
   Y.v1 = (int)pos; pos += vmax;
+  Y.t0 = (int)pos; pos += (int64_t)k * tmax;
+  Y.t1 = (int)pos; pos += (int64_t)k * tmax;
   Y.g = (int)pos; pos += (int64_t)k * mlp->dims[0];
   pos = (pos + 1) & ~(int64_t)1;   // (doubles)
   Y.redd = (int)pos; pos += kRedD;
@@ -446,25 +462,66 @@ extern "C" int64_t cvf_cv_frame_large_lds_bytes(const cvf_mlp_desc* mlp, int upt
   return (int64_t)lay.total * (int64_t)sizeof(float);
 }
 
-extern "C" int cvf_cv_frame_large_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
-                                       const float* x, int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream) {
-  LgLayout lay;
-  const char* why = cvfl_why(mlp, upto_layer, pp, &lay);
-  CVF_REQUIRE(why == nullptr, "cvf_cv_frame_large_eval: %s", why);
-  CVF_REQUIRE(B >= 0 && B <= 0x7fffffff, "cvf_cv_frame_large_eval: B = %lld frames (one call takes 0 to 2^31 - 1)", (long long)B);
+namespace {
+
+template <bool SHARED>
+int cvfl_launch(const char* name, const cvf_mlp_desc* mlp, const LgLayout& lay, const float* theta, const cvf_pp_desc* pp, const float* x,
+                int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream) {
+  CVF_REQUIRE(B >= 0 && B <= 0x7fffffff, "%s: B = %lld frames (one call takes 0 to 2^31 - 1)", name, (long long)B);
   if (B == 0) return 0;
-  CVF_REQUIRE(theta && x && xi_rows && gx_rows, "cvf_cv_frame_large_eval: null argument");
+  CVF_REQUIRE(theta && x && xi_rows && gx_rows, "%s: null argument", name);
   // with coef the coordinate part has one row: the launch takes the LDS of that one row
   const int rows_now = coef != nullptr ? 1 : lay.rpp;
   const size_t lds = ((size_t)lay.rows + (size_t)rows_now * 3 * (size_t)pp->n_ref) * sizeof(float);
   const bool vec4 = pp->n_coord % 4 == 0 && ((uintptr_t)gx_rows & 15) == 0;   // 16-byte stores of the dense rows
   const int mode = pp->mode != CVF_PP_ALIGN ? 0 : (pp->align_w == nullptr ? 1 : 2);
-  const auto kernel = vec4 ? (mode == 0 ? cv_frame_large_kernel<true, 0> : mode == 1 ? cv_frame_large_kernel<true, 1> : cv_frame_large_kernel<true, 2>)
-                           : (mode == 0 ? cv_frame_large_kernel<false, 0> : mode == 1 ? cv_frame_large_kernel<false, 1> : cv_frame_large_kernel<false, 2>);
+  const auto kernel = vec4 ? (mode == 0 ? cv_frame_large_kernel<true, 0, SHARED> : mode == 1 ? cv_frame_large_kernel<true, 1, SHARED> : cv_frame_large_kernel<true, 2, SHARED>)
+                           : (mode == 0 ? cv_frame_large_kernel<false, 0, SHARED> : mode == 1 ? cv_frame_large_kernel<false, 1, SHARED> : cv_frame_large_kernel<false, 2, SHARED>);
   if (lds > 48 * 1024) {
     const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    CVF_REQUIRE(e == hipSuccess, "cvf_cv_frame_large_eval: %zu bytes of dynamic LDS: %s", lds, hipGetErrorString(e));
+    CVF_REQUIRE(e == hipSuccess, "%s: %zu bytes of dynamic LDS: %s", name, lds, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kThreads), lds, (hipStream_t)stream, *mlp, *pp, lay, theta, x, coef, xi_rows, gx_rows);
   return cvf_check_launch("cv_frame_large_kernel");
+}
+
+const char* cvfl_shared_why(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp, LgLayout* lay) {
+  static thread_local char buf[240];
+  const char* why = cvf_form_c_why(mlp, n_shared, "cvf_cv_frame_large_eval", buf, sizeof buf);
+  return why != nullptr ? why : cvfl_why(mlp, mlp->n_layers, pp, lay, n_shared);
+}
+
+}  // namespace
+
+extern "C" int cvf_cv_frame_large_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
+                                       const float* x, int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream) {
+  LgLayout lay;
+  const char* why = cvfl_why(mlp, upto_layer, pp, &lay);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_frame_large_eval: %s", why);
+  return cvfl_launch<false>("cvf_cv_frame_large_eval", mlp, lay, theta, pp, x, B, coef, xi_rows, gx_rows, stream);
+}
+
+extern "C" int cvf_cv_frame_large_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp) {
+  const char* why = cvfl_shared_why(mlp, n_shared, pp, nullptr);
+  if (why != nullptr) {
+    cvf_set_error("cvf_cv_frame_large_shared: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_cv_frame_large_shared_lds_bytes(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp, int32_t* rows_per_pass) {
+  LgLayout lay;
+  const char* why = cvfl_shared_why(mlp, n_shared, pp, &lay);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_frame_large_shared_lds_bytes: %s", why);
+  if (rows_per_pass != nullptr) *rows_per_pass = lay.rpp;
+  return (int64_t)lay.total * (int64_t)sizeof(float);
+}
+
+extern "C" int cvf_cv_frame_large_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                              const float* x, int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream) {
+  LgLayout lay;
+  const char* why = cvfl_shared_why(mlp, n_shared, pp, &lay);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_frame_large_shared_eval: %s", why);
+  return cvfl_launch<true>("cvf_cv_frame_large_shared_eval", mlp, lay, theta, pp, x, B, coef, xi_rows, gx_rows, stream);
 }

@@ -16,12 +16,21 @@
 // v_{L-1} = act_{L-1}'(xi_i) W_{L-1}[i][:] is a row of the weights times one factor per frame: it is never stored, the first
 // sweep launch (l = L-2) forms it while staging.  Form A (n_nets = k scalar chains, EigenFunctions) reads net i's own weights
 // and activations; form B (one chain cut after `upto_layer` layers, e.g. an encoder) runs the trunk ONCE and sweeps the k rows
-// of its last weight matrix through the shared weights and the shared act'(a_l).
+// of its last weight matrix through the shared weights and the shared act'(a_l).  Form C (cvf_cv_nets_shared_*; DESIGN.md section
+// 4.17) is form A whose first n_shared layers are one set of tensors: those layers are launched with ONE z and zero z strides,
+// layer n_shared reads the one image a_{n_shared}, and the sweeps of the k CVs read the shared act'(a_l) images below it.
+// The L2 is per XCD and not coherent across the eight of them, and workgroups go to the XCDs round-robin in dispatch order (x
+// fastest).  In form A block (tile, z) has the same place in every launch, so it reads what its own XCD wrote.  In form C a trunk
+// launch has T blocks and a head launch k T: unless T is a multiple of 8, block (tile, z > 0) lands on another XCD than the trunk
+// block of its tile and pays for reading an image just written elsewhere (measured at B = 1: 11.6 us against 8.4 us for the launch
+// of layer n_shared; nothing at T = 8 or 16).  So a form-C call rounds grid.x up to a multiple of 8 (CvnArgs.nt: blocks past the
+// tiles exit at once): tile t is on XCD t % 8 in EVERY launch of the call, whatever y and z.
 //
 // All products run on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation.  No atomics; a column of the B operand (a frame)
 // meets the same instructions in the same order whichever tile and lane it sits in, so a frame's xi and g depend on its
 // features and theta only.  Nothing is read from scratch or the outputs that the same call did not write.
 #include "aeg_kernels.hpp"
+#include "cvf_cv_shared.hpp"
 
 namespace {
 
@@ -45,8 +54,10 @@ struct CvnArgs {
   float* g_tiled;     // CVN_G: [tile][k][M][64]
   int64_t B;
   int k;
+  int nt;             // > 0: grid.x is rounded up past the nt tiles and blocks with blockIdx.x >= nt exit (0: every block works)
 };
 
+constexpr int kXcds = 8;   // gfx950
 constexpr int kXP = 65;   // pitch of the [frame][m] image of the g_rows transpose
 static_assert(CVF_TILE * kXP <= 2 * kKC * kPitch, "the transpose reuses the operand stages");
 
@@ -55,6 +66,7 @@ __global__ __launch_bounds__(256) void cvn_layer_kernel(const float* __restrict_
   __shared__ __attribute__((aligned(16))) float smem[2 * kKC * kPitch];   // As [k][m], then Bs [k][frame]
   const G64Thread t = g64_thread();
   const int lane = t.lane, wave = t.wave;
+  if (a.nt > 0 && blockIdx.x >= (unsigned)a.nt) return;   // (the whole block: no barrier has been met)
   const int64_t tile = blockIdx.x;
   const int m0 = blockIdx.y * 64, z = blockIdx.z;
   const float* xp = a.seed ? nullptr : a.x + z * a.xz + tile * a.xs;
@@ -139,6 +151,7 @@ constexpr int kMaxValuesK = 4096;   // widest output of a values-only call
 struct CvnShape {
   int L, k, nn;   // layers evaluated, CVs, forward chains (form A: k, form B: 1)
   bool form_a;
+  int ns;         // form C: the chains' first ns layers are one trunk (0: forms A and B)
 };
 
 const char* cvn_why(const cvf_mlp_desc* mlp, int upto, int want_g, CvnShape* sh) {
@@ -180,12 +193,22 @@ const char* cvn_why(const cvf_mlp_desc* mlp, int upto, int want_g, CvnShape* sh)
   for (int i = 0; i < (form_a ? mlp->n_nets : 1); ++i)
     for (int l = 0; l < upto; ++l)
       if (mlp->w_off[i][l] < 0 || mlp->b_off[i][l] < 0) return "a negative parameter offset";
-  if (sh != nullptr) *sh = CvnShape{upto, k, form_a ? mlp->n_nets : 1, form_a};
+  if (sh != nullptr) *sh = CvnShape{upto, k, form_a ? mlp->n_nets : 1, form_a, 0};
   return nullptr;
 }
 
+// form C: the aliasing first, then the checks of form A on the whole chains (one head, n_nets = 1, is form B's arithmetic)
+const char* cvn_shared_why(const cvf_mlp_desc* mlp, int n_shared, int want_g, CvnShape* sh) {
+  static thread_local char buf[240];
+  const char* why = cvf_form_c_why(mlp, n_shared, "cvf_cv_nets_eval", buf, sizeof buf);
+  if (why == nullptr) why = cvn_why(mlp, mlp->n_layers, want_g, sh);
+  if (why == nullptr && sh != nullptr) sh->ns = n_shared;
+  return why;
+}
+
 // ---- scratch: a_0 (the gathered features; unused when the caller has tiles), a_1..a_L ([chain][tile][width][64] each) and, for
-// g on chains of three layers or more, two ping-pong images of v_l, l = 1..L-2 ([CV][tile][widest of dims[1..L-2]][64])
+// g on chains of three layers or more, two ping-pong images of v_l, l = 1..L-2 ([CV][tile][widest of dims[1..L-2]][64]).
+// Form C holds the trunk's images a_1..a_ns once: 64 T (dims[0] + sum dims[1..ns] + k sum dims[ns+1..L]) + 128 T k vmax with g.
 struct CvnLayout {
   int64_t a[CVF_MAX_LAYERS + 1], v[2], total;
   int vmax;
@@ -199,7 +222,7 @@ CvnLayout cvn_layout(const cvf_mlp_desc* mlp, const CvnShape& sh, int64_t n_tile
   pos += per * mlp->dims[0];
   for (int l = 1; l <= sh.L; ++l) {
     L.a[l] = pos;
-    pos += per * mlp->dims[l] * sh.nn;
+    pos += per * mlp->dims[l] * (l <= sh.ns ? 1 : sh.nn);
   }
   for (int l = 1; l <= sh.L - 2; ++l) L.vmax = mlp->dims[l] > L.vmax ? mlp->dims[l] : L.vmax;
   if (want_g)
@@ -228,19 +251,18 @@ extern "C" int64_t cvf_cv_nets_scratch_floats(const cvf_mlp_desc* mlp, int upto_
   return cvn_layout(mlp, sh, cvf_ntiles(B), want_g != 0).total;
 }
 
-extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const float* feat_rows,
-                                const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled,
-                                float* scratch, void* stream) {
+namespace {
+
+// the launches of one call, for a shape the caller has checked (sh.ns > 0: form C)
+int cvn_eval(const char* name, const cvf_mlp_desc* mlp, const CvnShape& sh, const float* theta, const float* feat_rows,
+             const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled, float* scratch, void* stream) {
   const bool want_g = g_rows != nullptr || g_tiled != nullptr;
-  CvnShape sh;
-  const char* why = cvn_why(mlp, upto_layer, want_g, &sh);
-  CVF_REQUIRE(why == nullptr, "cvf_cv_nets_eval: %s", why);
-  CVF_REQUIRE(theta && scratch && xi_rows && B > 0, "cvf_cv_nets_eval: bad argument");
-  CVF_REQUIRE((feat_rows != nullptr) != (feat_tiled != nullptr), "cvf_cv_nets_eval: pass exactly one of feat_rows and feat_tiled");
+  CVF_REQUIRE(theta && scratch && xi_rows && B > 0, "%s: bad argument", name);
+  CVF_REQUIRE((feat_rows != nullptr) != (feat_tiled != nullptr), "%s: pass exactly one of feat_rows and feat_tiled", name);
   const int64_t T = cvf_ntiles(B);
-  CVF_REQUIRE(T <= 0x7fffffff, "cvf_cv_nets_eval: %lld frames are more than one call takes", (long long)B);
+  CVF_REQUIRE(T <= 0x7fffffff - kXcds, "%s: %lld frames are more than one call takes", name, (long long)B);
   hipStream_t s = (hipStream_t)stream;
-  const int L = sh.L, k = sh.k, nn = sh.nn, d0 = mlp->dims[0];
+  const int L = sh.L, k = sh.k, nn = sh.nn, ns = sh.ns, d0 = mlp->dims[0];
   const CvnLayout lay = cvn_layout(mlp, sh, T, want_g);
   auto ts = [&](int l) { return (int64_t)mlp->dims[l] * CVF_TILE; };   // tile stride of an image of layer l's width
   auto zs = [&](int l) { return T * ts(l); };                          // chain / CV stride of such an image
@@ -254,8 +276,11 @@ extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int
     a0 = A(0);
   }
 
-  auto launch = [&](const CvnArgs& a, int nz) {
-    hipLaunchKernelGGL(cvn_layer_kernel, dim3((unsigned)T, (unsigned)((a.M + 63) / 64), (unsigned)nz), dim3(256), 0, s, theta, a);
+  // form C: grid.x a multiple of the XCD count, so that a tile's blocks meet on one XCD in every launch (the header has the figures)
+  const int64_t gx = ns > 0 ? (T + kXcds - 1) / kXcds * kXcds : T;
+  auto launch = [&](CvnArgs a, int nz) {
+    a.nt = gx != T ? (int)T : 0;
+    hipLaunchKernelGGL(cvn_layer_kernel, dim3((unsigned)gx, (unsigned)((a.M + 63) / 64), (unsigned)nz), dim3(256), 0, s, theta, a);
     return cvf_check_launch("cvn_layer_kernel");
   };
   // forward: a_{l+1} = act_l(W_l a_l + b_l), every chain in one launch; the last layer also leaves xi_rows
@@ -272,14 +297,14 @@ extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int
     a.act = mlp->act[l];
     a.x = l == 0 ? a0 : A(l);
     a.xs = ts(l);
-    a.xz = l == 0 ? 0 : zs(l);   // the features are shared by the chains
+    a.xz = l == 0 || l <= ns ? 0 : zs(l);   // the features, and form C's trunk, are shared by the chains
     a.out = A(l + 1);
     a.os = ts(l + 1);
     a.oz = zs(l + 1);
     a.xi_rows = l + 1 == L ? xi_rows : nullptr;
     a.B = B;
     a.k = k;
-    if (launch(a, nn)) return -1;
+    if (launch(a, l < ns ? 1 : nn)) return -1;   // (a trunk layer of form C: one z)
   }
   if (!want_g) return 0;
 
@@ -316,7 +341,7 @@ extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int
     a.act = mlp->act[l];
     a.xh = A(l + 1);
     a.hs = ts(l + 1);
-    a.hz = sh.form_a ? zs(l + 1) : 0;   // form B: the trunk's activations are shared by the CVs
+    a.hz = sh.form_a && l + 1 > ns ? zs(l + 1) : 0;   // forms B and C: the trunk's activations are shared by the CVs
     if (l == L - 2) {
       a.seed = 1;
       a.act_top = mlp->act[L - 1];
@@ -343,4 +368,40 @@ extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int
     if (launch(a, k)) return -1;
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int cvf_cv_nets_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const float* feat_rows,
+                                const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled,
+                                float* scratch, void* stream) {
+  CvnShape sh;
+  const char* why = cvn_why(mlp, upto_layer, g_rows != nullptr || g_tiled != nullptr, &sh);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_nets_eval: %s", why);
+  return cvn_eval("cvf_cv_nets_eval", mlp, sh, theta, feat_rows, feat_tiled, B, xi_rows, g_rows, g_tiled, scratch, stream);
+}
+
+extern "C" int cvf_cv_nets_shared_supported(const cvf_mlp_desc* mlp, int n_shared, int want_g) {
+  const char* why = cvn_shared_why(mlp, n_shared, want_g, nullptr);
+  if (why != nullptr) {
+    cvf_set_error("cvf_cv_nets_shared: %s", why);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int64_t cvf_cv_nets_shared_scratch_floats(const cvf_mlp_desc* mlp, int n_shared, int64_t B, int want_g) {
+  CvnShape sh;
+  if (cvn_shared_why(mlp, n_shared, want_g, &sh) != nullptr || B < 1) return 0;
+  return cvn_layout(mlp, sh, cvf_ntiles(B), want_g != 0).total;
+}
+
+extern "C" int cvf_cv_nets_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const float* feat_rows,
+                                       const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled,
+                                       float* scratch, void* stream) {
+  CvnShape sh;
+  const char* why = cvn_shared_why(mlp, n_shared, g_rows != nullptr || g_tiled != nullptr, &sh);
+  CVF_REQUIRE(why == nullptr, "cvf_cv_nets_shared_eval: %s", why);
+  if (B == 0) return 0;
+  return cvn_eval("cvf_cv_nets_shared_eval", mlp, sh, theta, feat_rows, feat_tiled, B, xi_rows, g_rows, g_tiled, scratch, stream);
 }

@@ -17,7 +17,7 @@ namespace cvf_file {
 
 constexpr int64_t kMlpOff = 16, kMlpBytes = 4 * (2 + (CVF_MAX_LAYERS + 1) + CVF_MAX_LAYERS + 2 * CVF_MAX_NETS * CVF_MAX_LAYERS + 1);
 constexpr int64_t kPpOff = kMlpOff + kMlpBytes, kPpInts = 12;
-constexpr int64_t kTailOff = kPpOff + 4 * kPpInts;   // upto_layer, k, n_entries, 0
+constexpr int64_t kTailOff = kPpOff + 4 * kPpInts;   // upto_layer, k, n_entries, n_shared
 constexpr int64_t kDirOff = kTailOff + 16, kEntryBytes = 24;
 static_assert(kMlpBytes == (int64_t)sizeof(cvf_mlp_desc), "the file stores cvf_mlp_desc in struct order");
 static_assert(kDirOff == 960, "documented in include/cvf.h");
@@ -33,6 +33,7 @@ struct View {
   cvf_mlp_desc mlp;
   int32_t mode, n_coord, n_align, n_rec, d_r, use_angle_value, has_position, flags, n_slot, n_rec_slot, n_mrec, n_ref;
   int32_t upto_layer, k;
+  int32_t n_shared;                 // form C: the chains' first n_shared layers are one set of tensors (0: forms A and B)
   Table t[CVF_FILE_N_TABLES + 1];   // by name id
   int64_t data_off, data_end;       // the table region [data_off, data_end) of the blob, what the binder copies
 };
@@ -87,6 +88,7 @@ inline int parse(const void* blob, int64_t nbytes, View* v, char* err, size_t er
   v->upto_layer = rd32(b + kTailOff, 0);
   v->k = rd32(b + kTailOff, 1);
   const int32_t n_entries = rd32(b + kTailOff, 2);
+  v->n_shared = rd32(b + kTailOff, 3);
 
   // ---- the nets' description
   const cvf_mlp_desc& m = v->mlp;
@@ -101,6 +103,16 @@ inline int parse(const void* blob, int64_t nbytes, View* v, char* err, size_t er
   if (m.n_nets > 1 && (v->upto_layer != m.n_layers || m.dims[m.n_layers] != 1))
     CVF_FILE_FAIL(-5, "cv file: %d nets side by side must be scalar and whole (upto_layer = %d of %d, %d outputs)", m.n_nets, v->upto_layer, m.n_layers, m.dims[m.n_layers]);
   if (v->k != (m.n_nets > 1 ? m.n_nets : m.dims[v->upto_layer])) CVF_FILE_FAIL(-5, "cv file: k = %d disagrees with the nets' description", v->k);
+  if (v->n_shared < 0 || v->n_shared > m.n_layers - 1) CVF_FILE_FAIL(-5, "cv file: n_shared = %d outside 0..%d (n_layers - 1)", v->n_shared, m.n_layers - 1);
+  if (v->n_shared > 0) {   // form C: scalar chains, whole, the trunk's tensors once
+    if (v->upto_layer != m.n_layers || m.dims[m.n_layers] != 1)
+      CVF_FILE_FAIL(-5, "cv file: n_shared = %d needs scalar chains evaluated whole (upto_layer = %d of %d, %d outputs)", v->n_shared, v->upto_layer, m.n_layers, m.dims[m.n_layers]);
+    for (int i = 1; i < m.n_nets; ++i)
+      for (int l = 0; l < v->n_shared; ++l)
+        if (m.w_off[i][l] != m.w_off[0][l] || m.b_off[i][l] != m.b_off[0][l])
+          CVF_FILE_FAIL(-5, "cv file: n_shared = %d, but net %d does not share layer %d (w_off %d / %d, b_off %d / %d)", v->n_shared, i, l,
+                        m.w_off[i][l], m.w_off[0][l], m.b_off[i][l], m.b_off[0][l]);
+  }
 
   // ---- the layer's scalars
   if (v->mode != CVF_PP_IDENTITY && v->mode != CVF_PP_ALIGN && v->mode != CVF_PP_FEATURES)

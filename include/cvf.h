@@ -812,7 +812,8 @@ int cvf_cv_frame_large_eval(const cvf_mlp_desc* mlp, const float* theta, int upt
  *   0    magic "CVF1", format version (1), CVF_MAX_NETS, CVF_MAX_LAYERS as written
  *   16   the cvf_mlp_desc fields in struct order (n_nets, n_layers, dims, act, w_off, b_off, n_params)
  *   896  mode, n_coord, n_align, n_rec, d_r, use_angle_value, has_position, flags, n_slot, n_rec_slot, n_mrec, n_ref
- *   944  upto_layer, k, number of directory entries, 0
+ *   944  upto_layer, k, number of directory entries, n_shared (0: forms A and B, as every file written before form C has it;
+ *        > 0: form C below - theta holds the trunk once, and the offsets of its layers are the same for every net)
  *   960  directory: per table { name id, element type (0 int32, 1 float32), int64 count, int64 byte offset in the file }, one
  *        entry for EVERY id below (count 0 = the layer has no such table: the descriptor's pointer is NULL)
  *   then the tables, each 16-byte aligned, in the order of their offsets.
@@ -832,6 +833,41 @@ typedef struct cvf_cv_model {
 } cvf_cv_model;
 int64_t cvf_cv_file_device_bytes(const void* blob_host, int64_t nbytes);
 int cvf_cv_file_bind(const void* blob_host, int64_t nbytes, void* dev_buf, int64_t dev_bytes, cvf_cv_model* out, void* stream);
+
+/* --- form C: k scalar chains on ONE trunk (csrc/cvf_cv_shared.hpp).  What nn.SharedEigenFunctions is,
+ * and what RegAutoEncoderTask.reg_model() returns (reference nn.py:205-240: RegModel, the encoder followed by the K regulariser
+ * nets in the order cvec; core.py:870-877: reg_model()) - the eigenfunctions that task learns.  Form C is form A plus n_shared:
+ *   n_nets = k >= 1 scalar chains of one architecture, evaluated whole (k = 1 is legal);
+ *   1 <= n_shared <= n_layers - 1: the chains' first n_shared layers are one set of tensors,
+ *   w_off[i][l] == w_off[0][l] and b_off[i][l] == b_off[0][l] for every l < n_shared and every net i (the convention of
+ *   cvf_ef_general_shared_*); a description that breaks it is refused before any launch, with the net and the layer named.
+ * Any act code after any layer, CVF_ACT_NONE at the boundary included (a RegModel's encoder ends in a bare Linear layer).
+ * The trunk runs ONCE per frame, forward.  In the sweep the k head sweeps stop at layer n_shared; below it the Jacobian rows
+ * carry k vectors through the shared weights, and the coef form contracts at the boundary, v = sum_i coef_i v_i, and carries one.
+ * Every entry point mirrors its namesake without _shared - arguments, outputs, limits and guarantees - with n_shared where that
+ * one takes upto_layer; n_shared == 0 is refused with a message that names the namesake, B == 0 returns 0 and writes nothing.
+ * With coef == NULL a row's arithmetic is that of form A on the same (aliased) description: xi and every gradient row hold the
+ * same bits.  The coef form sums in another order (at the boundary, not at the features).
+ *  cvf_cv_nets_shared_scratch_floats: 64 T (dims[0] + sum of dims[1..n_shared] + k sum of dims[n_shared+1..n_layers]), + with
+ *    want_g 128 T k max(dims[1..n_layers-2]): the trunk's images once.
+ *  cvf_cv_frame_shared_supported / cvf_cv_frame_large_shared_supported: the limits of their namesakes with the LDS total of form
+ *    C - the trunk's activations once, plus two images of k max(dims[1..n_shared]) floats for the trunk's sweep.
+ *  cvf_cv_file_n_shared: the word at byte 956 of a file cvf_cv_file_device_bytes accepts (0: call the entry points without
+ *    _shared with model.upto_layer; > 0: call the _shared ones with it), or that call's negative code.  cvf_cv_model keeps its
+ *    size and fields. */
+int cvf_cv_nets_shared_supported(const cvf_mlp_desc* mlp, int n_shared, int want_g);
+int64_t cvf_cv_nets_shared_scratch_floats(const cvf_mlp_desc* mlp, int n_shared, int64_t B, int want_g);
+int cvf_cv_nets_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const float* feat_rows,
+                            const float* feat_tiled, int64_t B, float* xi_rows, float* g_rows, float* g_tiled, float* scratch,
+                            void* stream);
+int cvf_cv_frame_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int cvf_cv_frame_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp, const float* x,
+                             int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
+int cvf_cv_frame_large_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int64_t cvf_cv_frame_large_shared_lds_bytes(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp, int32_t* rows_per_pass);
+int cvf_cv_frame_large_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp, const float* x,
+                                   int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
+int cvf_cv_file_n_shared(const void* blob_host, int64_t nbytes);
 
 /* --- K6: Adam (torch.optim.Adam defaults as constructed at core.py:164: betas
  * (0.9,0.999), eps 1e-8, no weight decay, no amsgrad), one launch over the flat buffer.

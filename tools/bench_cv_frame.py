@@ -18,7 +18,16 @@ size) against the three-call recipe cvf_align_feature_fwd -> cvf_cv_nets_eval ->
 Method: HIP events around a window of --replays (200) back-to-back evaluations, time per evaluation = window / replays; per
 round and variant the median of --windows (3) windows; --rounds (3) rounds that alternate the variants; reported per variant: the
 median of the rounds' medians and their spread (min, max), in microseconds.  Before timing, the two routes' J are compared.
-Buffers are allocated once; nothing is allocated inside a window.  One JSON line; --summary PATH also writes a table."""
+Buffers are allocated once; nothing is allocated inside a window.  One JSON line; --summary PATH also writes a table.
+
+--shared measures form C (k scalar chains on one trunk: cvf_cv_frame_shared_eval, cvf_cv_frame_large_shared_eval,
+cvf_cv_nets_shared_eval) against form A - the entries above on the SAME aliased description and theta - on config
+3's layer, every route replayed from a captured graph, with and without coef:
+
+  models    narrow     trunk [66, 20, 20], head [20, 1], k = 3
+            wide       trunk [66, 64, 64], head [64, 1], k = 8
+  variants  per route (frame, frame_large, three): A, A2 (form A a second time: the tool's own run-to-run spread) and C, alternating
+            inside a round; with coef the three-call recipe contracts d xi / d r with coef (one bmm) before cvf_align_feature_vjp"""
 import argparse
 import json
 import os
@@ -112,6 +121,99 @@ def window_us(fn, replays):
     return e0.elapsed_time(e1) * 1e3 / replays
 
 
+SHARED_MODELS = {"narrow": ([20, 20], [20, 1], 3), "wide": ([64, 64], [64, 1], 8)}
+
+
+def build_shared(model, B, dev, with_coef):
+    """{(route, form): closure} over preallocated buffers for a SharedEigenFunctions on config 3's layer; form "A" is the existing
+    entry on the form-C description (aliased offsets, the same theta), form "C" the _shared one.  Also the outputs per closure."""
+    lib, P = _hip.lib(), _hip.ptr
+    n = 22
+    traj, _, ref = make_molecule_traj(n, B, seed=17)
+    layer = pp.AlignFeatureLayer(n, list(range(n)), ref, [("position", tuple(range(n)))]).to(dev)
+    trunk, head, k = SHARED_MODELS[model]
+    torch.manual_seed(11)
+    nets = nn.SharedEigenFunctions([layer.d_r] + trunk, head, k).to(dev)
+    mdesc, L, k, params, ns = core._CVModel._nets_plan_shared(nets)
+    theta = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+    pdesc = layer.pp_desc()
+    for ok in (lib.cvf_cv_frame_supported(mdesc, L, pdesc), lib.cvf_cv_frame_shared_supported(mdesc, ns, pdesc),
+               lib.cvf_cv_frame_large_supported(mdesc, L, pdesc), lib.cvf_cv_frame_large_shared_supported(mdesc, ns, pdesc)):
+        assert ok == 1, lib.cvf_last_error().decode()
+    x = torch.tensor(traj, device=dev).reshape(B, -1).contiguous()
+    T, d_r, nc = _hip.ntiles(B), layer.d_r, 3 * n
+    cf = torch.randn(B, k, generator=torch.Generator().manual_seed(3)).to(dev) if with_coef else None
+    r_t = torch.empty(T, d_r, _hip.TILE, device=dev)
+    aux = torch.empty(T, _hip.AUX_ROWS, _hip.TILE, device=dev)
+    G, g = torch.empty(B, k, d_r, device=dev), torch.empty(B, 1, d_r, device=dev)
+    ws = torch.empty(max(lib.cvf_cv_nets_scratch_floats(mdesc, L, B, 1), lib.cvf_cv_nets_shared_scratch_floats(mdesc, ns, B, 1)), device=dev)
+    keep = [layer, nets, theta, x, r_t, aux, G, g, ws, cf]
+    fns, outs = {}, {}
+    for route in ("frame", "frame_large", "three"):
+        for form in ("A", "A2", "C"):
+            xi, D = torch.empty(B, k, device=dev), torch.empty((B, nc) if with_coef else (B, k, nc), device=dev)
+            cut = ns if form == "C" else L
+            if route == "three":
+                nets_eval, label = (lib.cvf_cv_nets_shared_eval, "cvf_cv_nets_shared_eval") if form == "C" else (lib.cvf_cv_nets_eval, "cvf_cv_nets_eval")
+
+                def fn(xi=xi, D=D, cut=cut, nets_eval=nets_eval, label=label):
+                    s = _hip.stream()
+                    _hip.check(lib.cvf_align_feature_fwd(pdesc, P(x), B, P(r_t), None, P(aux), None, s), "cvf_align_feature_fwd")
+                    _hip.check(nets_eval(mdesc, P(theta), cut, None, P(r_t), B, P(xi), P(G), None, P(ws), s), label)
+                    if cf is None:
+                        _hip.check(lib.cvf_align_feature_vjp_rows(pdesc, P(x), B, P(aux), k, P(G), P(D), s), "cvf_align_feature_vjp_rows")
+                    else:
+                        torch.bmm(cf.unsqueeze(1), G, out=g)
+                        _hip.check(lib.cvf_align_feature_vjp(pdesc, P(x), B, P(aux), P(g), P(D), s), "cvf_align_feature_vjp")
+            else:
+                label = "cvf_cv_" + route + ("_shared" if form == "C" else "") + "_eval"
+                entry = getattr(lib, label)
+
+                def fn(xi=xi, D=D, cut=cut, entry=entry, label=label):
+                    _hip.check(entry(mdesc, P(theta), cut, pdesc, P(x), B, P(cf), P(xi), P(D), _hip.stream()), label)
+            fns[(route, form)], outs[(route, form)] = fn, (xi, D)
+    return fns, outs, keep
+
+
+def main_shared(a, dev):
+    out = {"tool": "bench_cv_frame --shared", "replays": a.replays, "windows": a.windows, "rounds": a.rounds, "unit": "us per evaluation",
+           "results": {}}
+    lines = [f"{'model':7s} {'B':>5s} {'coef':>4s} {'route':12s} {'form A':>24s} {'form A again':>24s} {'form C':>24s}   C/A   A2/A   max rel diff C vs A"]
+    for model in SHARED_MODELS:
+        for B in [int(b) for b in a.batches.split(",")]:
+            for with_coef in (False, True):
+                fns, outs, keep = build_shared(model, B, dev, with_coef)
+                for fn in fns.values():      # one eager call of every variant before any capture
+                    fn()
+                torch.cuda.synchronize()
+                diffs = {r: float((outs[(r, "C")][1] - outs[(r, "A")][1]).abs().max() / outs[(r, "A")][1].abs().max()) for r in ("frame", "frame_large", "three")}
+                replays, graphs = {}, []
+                for key, fn in fns.items():
+                    replays[key], g = captured(fn)
+                    graphs.append(g)
+                for fn in replays.values():
+                    window_us(fn, 20)
+                rounds = {v: [] for v in replays}
+                for _ in range(a.rounds):
+                    for v in replays:        # the variants alternate inside a round
+                        rounds[v].append(statistics.median(window_us(replays[v], a.replays) for _ in range(a.windows)))
+                res = {v: {"median": round(statistics.median(t), 3), "min": round(min(t), 3), "max": round(max(t), 3)} for v, t in rounds.items()}
+                cell = lambda r: f"{r['median']:9.2f} [{r['min']:6.2f},{r['max']:6.2f}]"
+                for route in ("frame", "frame_large", "three"):
+                    A, A2, Cc = res[(route, "A")], res[(route, "A2")], res[(route, "C")]
+                    out["results"][f"{model}/B{B}/{'coef' if with_coef else 'rows'}/{route}"] = {"A": A, "A2": A2, "C": Cc, "rel_diff": diffs[route]}
+                    lines.append(f"{model:7s} {B:5d} {'yes' if with_coef else 'no':>4s} {route:12s} {cell(A):>24s} {cell(A2):>24s} {cell(Cc):>24s}"
+                                 f"   {Cc['median'] / A['median']:.3f}  {A2['median'] / A['median']:.3f}   {diffs[route]:.1e}")
+                del graphs, replays, fns, keep
+    print("\n".join(lines), file=sys.stderr)
+    if a.summary:
+        with open(a.summary, "w") as f:
+            f.write("bench_cv_frame --shared: us per evaluation of (xi, J) or (xi, F), graph replays, median of the rounds' medians [min, max over "
+                    f"rounds]; {a.replays} replays per window, {a.windows} windows per round, {a.rounds} rounds, variants alternating\n")
+            f.write("\n".join(lines) + "\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=200)
@@ -120,10 +222,13 @@ def main():
     ap.add_argument("--batches", default=",".join(map(str, BATCHES)), help="comma-separated batch sizes (larger ones locate the crossover)")
     ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated shapes of SHAPES")
     ap.add_argument("--summary", default=None)
+    ap.add_argument("--shared", action="store_true", help="form C against form A on config 3's layer (DESIGN.md 4.17)")
     a = ap.parse_args()
     assert a.replays >= 200 and a.rounds >= 3, "at least 200 replays per window and three rounds"
     assert torch.cuda.is_available(), "bench_cv_frame.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.shared:
+        return main_shared(a, dev)
     out = {"tool": "bench_cv_frame", "replays": a.replays, "windows": a.windows, "rounds": a.rounds, "unit": "us per evaluation",
            "results": {}}
     lines = [f"{'shape':10s} {'B':>5s} " + " ".join(f"{v:>24s}" for v in VARIANTS) + "   frame_graph, frame_large_graph / three_graph"]
