@@ -33,6 +33,9 @@ K1_ROUTE_SMALL, K1_ROUTE_GATHER_CONTIG, K1_ROUTE_GATHER, K1_ROUTE_CAPTURE_VEC4, 
 K1_ROUTE_SLICE, K1_ROUTE_PIPE = 10, 20
 # cvf_metric_route (include/cvf.h): kernel families of cvf_metric_apply[_stats]
 METRIC_IDENTITY, METRIC_FACTORED, METRIC_FEATURES, METRIC_ALIGN, METRIC_PURE, METRIC_ROWS = range(6)
+# cvf_align_feature_deriv_route (include/cvf.h): the call asked about, and the kernel families of the answer
+DERIV_VJP, DERIV_VJP_ROWS, DERIV_JVP, DERIV_HVP, DERIV_FEATURES_FWD, DERIV_FEATURES_METRIC = range(6)
+DERIV_IDENTITY, DERIV_FEATURES, DERIV_SMALL, DERIV_LARGE = range(4)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcvf_hip.so")
@@ -50,6 +53,12 @@ class PPDesc(C.Structure):
 class MetricPlan(C.Structure):
     _fields_ = [("family", C.c_int32), ("F", C.c_int32), ("waves", C.c_int32), ("geo_pre", C.c_int32), ("multi", C.c_int32),
                 ("npb", C.c_int32), ("nets_per_wg", C.c_int32), ("fused", C.c_int32), ("fused_rows", C.c_int32),
+                ("reserved", C.c_int32), ("lds_bytes", C.c_int64), ("grid", C.c_int64)]
+
+
+class DerivPlan(C.Structure):
+    _fields_ = [("family", C.c_int32), ("tables_lds", C.c_int32), ("q_lds", C.c_int32), ("u_lds", C.c_int32), ("weighted", C.c_int32),
+                ("vec4", C.c_int32), ("lg", C.c_int32), ("rows_per_launch", C.c_int32), ("launches", C.c_int32),
                 ("reserved", C.c_int32), ("lds_bytes", C.c_int64), ("grid", C.c_int64)]
 
 
@@ -86,6 +95,7 @@ _SIGNATURES = {
                                         C.c_void_p]),
     "cvf_align_feature_hvp": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "cvf_align_feature_deriv_route": (C.c_int, [C.POINTER(PPDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(DerivPlan)]),
     "cvf_metric_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvf_metric_apply": (C.c_int, [C.POINTER(PPDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -6,6 +6,13 @@
 #pragma once
 #include "cvf_common.hpp"
 
+// The launch plans of the derivative entry points (cvf_align_feature_deriv_route, include/cvf.h): each file plans its own kernels -
+// csrc/k1_vjp.hip (vjp, vjp_rows), k1_jvp.hip, k1_hvp.hip, and k1_features.hip for every CVF_PP_FEATURES launch.
+int cvf_vjp_plan(const cvf_pp_desc* pp, int64_t B, int which, int k, int out_aligned16, cvf_deriv_plan* P);
+int cvf_jvp_plan(const cvf_pp_desc* pp, int64_t B, cvf_deriv_plan* P);
+int cvf_hvp_plan(const cvf_pp_desc* pp, int64_t B, int out_aligned16, cvf_deriv_plan* P);
+int cvf_features_deriv_plan(const cvf_pp_desc* pp, int64_t B, int which, int k, cvf_deriv_plan* P);
+
 // One entry of cvf_pp_desc.rec / rec_slot (include/cvf.h): type, four atoms (or slots), first output.
 struct Rec {
   int type, a[4], out;
@@ -38,6 +45,7 @@ __device__ __forceinline__ BondG bond_eval(V3 xa, V3 xb) {
 
 struct AngleG {
   float cs;  // cos of the angle at b
+  float sn;  // sin of the angle, from |r1 x r2|: no cancellation where the angle is nearly straight (1 - cs^2 loses its digits there)
   V3 ga, gb, gc;  // gradient of cos
 };
 __device__ __forceinline__ AngleG angle_eval(V3 xa, V3 xb, V3 xc) {
@@ -47,6 +55,8 @@ __device__ __forceinline__ AngleG angle_eval(V3 xa, V3 xb, V3 xc) {
   float cs = dot(r1, r2) * inv12;
   AngleG o;
   o.cs = cs;
+  const V3 n = cross(r1, r2);
+  o.sn = sqrtf(dot(n, n)) * inv12;
   o.ga = inv12 * r2 - (cs / (l1 * l1)) * r1;
   o.gc = inv12 * r1 - (cs / (l2 * l2)) * r2;
   o.gb = (-1.0f) * (o.ga + o.gc);
@@ -117,6 +127,8 @@ __device__ __forceinline__ DihedralG dihedral_eval(V3 x1, V3 x2, V3 x3, V3 x4) {
 // A dihedral record emits (cos phi, sin phi) or, with use_angle_value, phi: d cos = -sin dphi, d sin = cos dphi.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ float acos_den(float cs) { return sqrtf(fmaxf(1.0f - cs * cs, 1e-30f)); }
+// ... of an evaluated angle: its sine as angle_eval formed it (the same clamp)
+__device__ __forceinline__ float acos_den(const AngleG& e) { return fmaxf(e.sn, 1e-15f); }
 // the adjoint of phi from the upstream values g(j) of the record's outputs (g(1) is read only when it exists)
 template <class G>
 __device__ __forceinline__ float dihedral_adjoint(bool angle_value, float cs, float sn, G g) {
@@ -170,7 +182,7 @@ __device__ __forceinline__ void invariant_vjp(int type, bool angle_value, int n,
     const AngleG e = angle_eval(at(0), at(1), at(2));
     for (int i = 0; i < n; ++i) {
       float gs = g(i, 0);
-      if (angle_value) gs = -gs / acos_den(e.cs);
+      if (angle_value) gs = -gs / acos_den(e);
       add(i, 0, gs * e.ga);
       add(i, 1, gs * e.gb);
       add(i, 2, gs * e.gc);
@@ -196,7 +208,7 @@ __device__ __forceinline__ void invariant_jvp(int type, bool angle_value, At at,
   } else if (type == CVF_FEAT_ANGLE) {
     const AngleG e = angle_eval(at(0), at(1), at(2));
     float dv = dot(e.ga, u(0)) + dot(e.gb, u(1)) + dot(e.gc, u(2));
-    if (angle_value) dv = -dv / acos_den(e.cs);
+    if (angle_value) dv = -dv / acos_den(e);
     put(0, dv);
   } else {
     const DihedralG e = dihedral_eval<EXACT>(at(0), at(1), at(2), at(3));

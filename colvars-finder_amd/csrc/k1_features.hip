@@ -299,15 +299,11 @@ FeatPlan feat_plan(size_t bytes_per_frame, size_t budget = kLdsBudget) {
   return p;
 }
 
-int features_check(const cvf_pp_desc* pp, const char* who, bool derivative) {
-  CVF_REQUIRE(pp->n_coord > 0 && pp->n_coord % 3 == 0 && pp->d_r >= 1 && pp->n_rec >= 1 && pp->rec_slot && pp->slot_atom && pp->n_slot >= 1,
-              "%s: CVF_PP_FEATURES needs n_coord = 3 N, the records and the slot tables (rec_slot, slot_atom)", who);
-  CVF_REQUIRE(pp->n_slot <= CVF_FEATURES_MAX_SLOT, "%s: CVF_PP_FEATURES: n_slot = %d distinct feature atoms; the limit is CVF_FEATURES_MAX_SLOT = %d",
-              who, pp->n_slot, CVF_FEATURES_MAX_SLOT);
+// the pointers of the descriptor a launch reads (the counts: cvf_features_deriv_plan)
+int features_tables(const cvf_pp_desc* pp, const char* who, bool derivative) {
+  CVF_REQUIRE(pp->rec_slot && pp->slot_atom, "%s: CVF_PP_FEATURES needs n_coord = 3 N, the records and the slot tables (rec_slot, slot_atom)", who);
   if (derivative) {
-    CVF_REQUIRE(pp->n_ref <= CVF_FEATURES_MAX_REF, "%s: CVF_PP_FEATURES: n_ref = %d contribution rows; the limit is CVF_FEATURES_MAX_REF = %d", who,
-                pp->n_ref, CVF_FEATURES_MAX_REF);
-    CVF_REQUIRE(pp->mrec && pp->slot_row && pp->atom_slot && pp->n_mrec >= 1 && pp->n_ref >= pp->n_slot,
+    CVF_REQUIRE(pp->mrec && pp->slot_row && pp->atom_slot,
                 "%s: CVF_PP_FEATURES derivatives need the contribution-row tables (atom_slot, mrec, slot_row)", who);
     CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "%s: mrec must be 16-byte aligned", who);
   }
@@ -315,46 +311,105 @@ int features_check(const cvf_pp_desc* pp, const char* who, bool derivative) {
 }
 
 template <class K, class... Args>
-int features_launch(K kernel, const char* name, int64_t B, const FeatPlan& p, hipStream_t s, Args... args) {
-  const int64_t nb = cvf_ntiles(B) * (CVF_TILE >> p.lg);
-  CVF_REQUIRE(nb <= 0x7fffffff, "%s: %lld frames are too many for one launch", name, (long long)B);
-  if (p.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kFeatThreads), p.lds, s, args...);
+int features_launch(K kernel, const char* name, const cvf_deriv_plan& p, hipStream_t s, Args... args) {
+  if (p.lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(kFeatThreads), (size_t)p.lds_bytes, s, args...);
   return cvf_check_launch(name);
 }
 
 }  // namespace
 
+// The launch of every CVF_PP_FEATURES kernel (this file and features_hvp_kernel, csrc/k1_hvp.hip): frames per workgroup, LDS, grid,
+// and what else the kernel is told (u_lds, nets per pass) - host arithmetic on the descriptor's counts.  `which`: CVF_DERIV_*
+// (include/cvf.h); cvf_align_feature_deriv_route answers with it, the launches below launch by it.
+int cvf_features_deriv_plan(const cvf_pp_desc* pp, int64_t B, int which, int k, cvf_deriv_plan* P) {
+  static const char* const kWho[] = {"cvf_align_feature_vjp", "cvf_align_feature_vjp", "cvf_align_feature_jvp",
+                                     "cvf_align_feature_hvp", "cvf_align_feature_fwd", "cvf_metric_apply"};
+  *P = cvf_deriv_plan{};
+  CVF_REQUIRE(which >= CVF_DERIV_VJP && which <= CVF_DERIV_FEATURES_METRIC, "cvf_align_feature_deriv_route: unknown call %d", which);
+  const char* who = kWho[which];
+  const bool derivative = which != CVF_DERIV_FEATURES_FWD;
+  CVF_REQUIRE((which != CVF_DERIV_VJP_ROWS && which != CVF_DERIV_FEATURES_METRIC) || (k >= 1 && k <= CVF_MAX_NETS),
+              "%s: k outside 1..%d (k=%d)", who, CVF_MAX_NETS, k);
+  CVF_REQUIRE(pp->n_coord > 0 && pp->n_coord % 3 == 0 && pp->d_r >= 1 && pp->n_rec >= 1 && pp->n_slot >= 1,
+              "%s: CVF_PP_FEATURES needs n_coord = 3 N, the records and the slot tables (%s)", who,
+              which == CVF_DERIV_HVP ? "slot_atom" : "rec_slot, slot_atom");   // (features_hvp_kernel does not read rec_slot)
+  CVF_REQUIRE(pp->n_slot <= CVF_FEATURES_MAX_SLOT, "%s: CVF_PP_FEATURES: n_slot = %d distinct feature atoms; the limit is CVF_FEATURES_MAX_SLOT = %d",
+              who, pp->n_slot, CVF_FEATURES_MAX_SLOT);
+  if (derivative) {
+    CVF_REQUIRE(pp->n_ref <= CVF_FEATURES_MAX_REF, "%s: CVF_PP_FEATURES: n_ref = %d contribution rows; the limit is CVF_FEATURES_MAX_REF = %d", who,
+                pp->n_ref, CVF_FEATURES_MAX_REF);
+    CVF_REQUIRE(pp->n_mrec >= 1 && pp->n_ref >= pp->n_slot,
+                "%s: CVF_PP_FEATURES derivatives need the contribution-row tables (atom_slot, mrec, slot_row)", who);
+  }
+  const size_t ns = (size_t)pp->n_slot, nr = (size_t)pp->n_ref;
+  size_t per_frame = ns * 12, budget = kLdsBudget;
+  P->rows_per_launch = 1;
+  switch (which) {
+    case CVF_DERIV_VJP_ROWS:   // (one row after the other on the same staged atoms)
+    case CVF_DERIV_VJP:
+      P->rows_per_launch = which == CVF_DERIV_VJP_ROWS ? k : 1;
+      per_frame = (ns + nr) * 12;
+      break;
+    case CVF_DERIV_JVP: per_frame = ns * 24; break;    // the feature atoms of x and of u
+    case CVF_DERIV_HVP:                                // the feature atoms of x and, while all fits the LDS, of u; the rows
+      P->u_lds = (2 * ns + nr) * 12 <= 160 * 1024;
+      per_frame = ((P->u_lds ? 2 : 1) * ns + nr) * 12;
+      break;
+    case CVF_DERIV_FEATURES_METRIC: {
+      // nets per pass: all k while one frame's image stays within the budget, else the fewest equal passes that do
+      auto image = [&](int kc) { return ns * 12 + (size_t)kc * nr * 12; };
+      int kc = k;
+      while (kc > 1 && image(kc) > kMetricBudget) --kc;
+      const int passes = (k + kc - 1) / kc;
+      kc = (k + passes - 1) / passes;
+      P->rows_per_launch = kc;
+      per_frame = image(kc);
+      budget = kMetricBudget;
+      break;
+    }
+    default: break;
+  }
+  const FeatPlan p = feat_plan(per_frame, budget);
+  const int64_t nb = cvf_ntiles(B) * (CVF_TILE >> p.lg);
+  CVF_REQUIRE(nb <= 0x7fffffff, "%s: %lld frames are too many for one launch", who, (long long)B);
+  P->family = CVF_DERIV_ROUTE_FEATURES;
+  P->lg = p.lg;
+  P->launches = 1;
+  P->lds_bytes = (int64_t)p.lds;
+  P->grid = nb;
+  return 0;
+}
+
 int cvf_features_fwd_launch(const cvf_pp_desc* pp, const float* x, int64_t B, float* feat_tiled, float* feat_rows, hipStream_t s) {
-  if (int rc = features_check(pp, "cvf_align_feature_fwd", false)) return rc;
-  const FeatPlan p = feat_plan((size_t)pp->n_slot * 12);
-  return features_launch(features_fwd_kernel, "features_fwd_kernel", B, p, s, *pp, x, B, p.lg, feat_tiled, feat_rows);
+  cvf_deriv_plan p;
+  if (int rc = cvf_features_deriv_plan(pp, B, CVF_DERIV_FEATURES_FWD, 1, &p)) return rc;
+  if (int rc = features_tables(pp, "cvf_align_feature_fwd", false)) return rc;
+  return features_launch(features_fwd_kernel, "features_fwd_kernel", p, s, *pp, x, B, p.lg, feat_tiled, feat_rows);
 }
 
 int cvf_features_vjp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, int k, const float* g_rows, float* gx_rows, hipStream_t s) {
-  if (int rc = features_check(pp, "cvf_align_feature_vjp", true)) return rc;
+  cvf_deriv_plan p;
+  if (int rc = cvf_features_deriv_plan(pp, B, CVF_DERIV_VJP_ROWS, k, &p)) return rc;
+  if (int rc = features_tables(pp, "cvf_align_feature_vjp", true)) return rc;
   CVF_REQUIRE(x, "cvf_align_feature_vjp: CVF_PP_FEATURES needs x");
-  const FeatPlan p = feat_plan(((size_t)pp->n_slot + pp->n_ref) * 12);
-  return features_launch(features_vjp_kernel, "features_vjp_kernel", B, p, s, *pp, x, B, p.lg, k, g_rows, gx_rows);
+  return features_launch(features_vjp_kernel, "features_vjp_kernel", p, s, *pp, x, B, p.lg, k, g_rows, gx_rows);
 }
 
 int cvf_features_jvp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* u_rows, float* q_rows, hipStream_t s) {
-  if (int rc = features_check(pp, "cvf_align_feature_jvp", true)) return rc;
+  cvf_deriv_plan p;
+  if (int rc = cvf_features_deriv_plan(pp, B, CVF_DERIV_JVP, 1, &p)) return rc;
+  if (int rc = features_tables(pp, "cvf_align_feature_jvp", true)) return rc;
   CVF_REQUIRE(x, "cvf_align_feature_jvp: CVF_PP_FEATURES needs x");
-  const FeatPlan p = feat_plan((size_t)pp->n_slot * 24);   // the feature atoms of x and of u
-  return features_launch(features_jvp_kernel, "features_jvp_kernel", B, p, s, *pp, x, B, p.lg, u_rows, q_rows);
+  return features_launch(features_jvp_kernel, "features_jvp_kernel", p, s, *pp, x, B, p.lg, u_rows, q_rows);
 }
 
 int cvf_features_metric_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* a, int k, const float* g_tiled,
                                float* q_tiled, float* e_tiled, hipStream_t s) {
-  if (int rc = features_check(pp, "cvf_metric_apply", true)) return rc;
+  cvf_deriv_plan p;
+  if (int rc = cvf_features_deriv_plan(pp, B, CVF_DERIV_FEATURES_METRIC, k, &p)) return rc;
+  if (int rc = features_tables(pp, "cvf_metric_apply", true)) return rc;
   CVF_REQUIRE(x, "cvf_metric_apply: CVF_PP_FEATURES needs x");
-  // nets per pass: all k while one frame's image stays within the budget, else the fewest equal passes that do
-  auto per_frame = [&](int kc) { return (size_t)pp->n_slot * 12 + (size_t)kc * pp->n_ref * 12; };
-  int kc = k;
-  while (kc > 1 && per_frame(kc) > kMetricBudget) --kc;
-  const int passes = (k + kc - 1) / kc;
-  kc = (k + passes - 1) / passes;
-  const FeatPlan p = feat_plan(per_frame(kc), kMetricBudget);
-  return features_launch(features_metric_kernel, "features_metric_kernel", B, p, s, *pp, x, B, p.lg, kc, a, k, g_tiled, q_tiled, e_tiled);
+  return features_launch(features_metric_kernel, "features_metric_kernel", p, s, *pp, x, B, p.lg, p.rows_per_launch, a, k, g_tiled,
+                         q_tiled, e_tiled);
 }

@@ -338,7 +338,6 @@ __global__ __launch_bounds__(kLargeThreads) void hvp_large_kernel(cvf_pp_desc pp
 // the limits of include/cvf.h, whose two atom images and rows exceed the LDS) the tangents are read where they lie.
 // ------------------------------------------------------------------------------------
 constexpr int kFeatThreads = 256;
-constexpr size_t kFeatLdsBudget = 64 * 1024;   // LDS of a workgroup while G > 1 (two workgroups per CU), as k1_features.hip
 
 __device__ __forceinline__ V3 img_get(const float* img, int e, int f, int G) {
   return V3{img[(3 * e) * G + f], img[(3 * e + 1) * G + f], img[(3 * e + 2) * G + f]};
@@ -397,33 +396,65 @@ __global__ __launch_bounds__(kFeatThreads) void features_hvp_kernel(cvf_pp_desc 
   }
 }
 
-int features_hvp_launch(const cvf_pp_desc* pp, const float* x, int64_t B, const float* g_rows, const float* u_rows, float* h_rows,
-                        hipStream_t s) {
+// (P: cvf_features_deriv_plan, csrc/k1_features.hip - counts, limits, lg, u_lds)
+int features_hvp_launch(const cvf_deriv_plan& P, const cvf_pp_desc* pp, const float* x, int64_t B, const float* g_rows, const float* u_rows,
+                        float* h_rows, hipStream_t s) {
   const char* who = "cvf_align_feature_hvp";
-  CVF_REQUIRE(pp->n_coord > 0 && pp->n_coord % 3 == 0 && pp->d_r >= 1 && pp->n_rec >= 1 && pp->slot_atom && pp->n_slot >= 1,
-              "%s: CVF_PP_FEATURES needs n_coord = 3 N, the records and the slot tables (slot_atom)", who);
-  CVF_REQUIRE(pp->n_slot <= CVF_FEATURES_MAX_SLOT, "%s: CVF_PP_FEATURES: n_slot = %d distinct feature atoms; the limit is CVF_FEATURES_MAX_SLOT = %d",
-              who, pp->n_slot, CVF_FEATURES_MAX_SLOT);
-  CVF_REQUIRE(pp->n_ref <= CVF_FEATURES_MAX_REF, "%s: CVF_PP_FEATURES: n_ref = %d contribution rows; the limit is CVF_FEATURES_MAX_REF = %d", who,
-              pp->n_ref, CVF_FEATURES_MAX_REF);
-  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->atom_slot && pp->n_mrec >= 1 && pp->n_ref >= pp->n_slot,
+  CVF_REQUIRE(pp->slot_atom, "%s: CVF_PP_FEATURES needs n_coord = 3 N, the records and the slot tables (slot_atom)", who);
+  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->atom_slot,
               "%s: CVF_PP_FEATURES derivatives need the contribution-row tables (atom_slot, mrec, slot_row)", who);
   CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "%s: mrec must be 16-byte aligned", who);
   CVF_REQUIRE(x, "%s: CVF_PP_FEATURES needs x", who);
-  const size_t with_u = ((size_t)2 * pp->n_slot + pp->n_ref) * 12, without_u = ((size_t)pp->n_slot + pp->n_ref) * 12;
-  const int u_lds = with_u <= kLdsLimit;
-  const size_t per_frame = u_lds ? with_u : without_u;
-  int lg = 6;
-  while (lg > 0 && (per_frame << lg) > kFeatLdsBudget) --lg;
-  const size_t lds = per_frame << lg;
-  const int64_t nb = cvf_ntiles(B) * (CVF_TILE >> lg);
-  CVF_REQUIRE(nb <= 0x7fffffff, "%s: %lld frames are too many for one launch", who, (long long)B);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)features_hvp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(features_hvp_kernel, dim3((unsigned)nb), dim3(kFeatThreads), lds, s, *pp, x, B, lg, u_lds, g_rows, u_rows, h_rows);
+  if (P.lds_bytes > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)features_hvp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes);
+  hipLaunchKernelGGL(features_hvp_kernel, dim3((unsigned)P.grid), dim3(kFeatThreads), (size_t)P.lds_bytes, s, *pp, x, B, P.lg, P.u_lds,
+                     g_rows, u_rows, h_rows);
   return cvf_check_launch("features_hvp_kernel");
 }
 
 }  // namespace
+
+// Which kernel cvf_align_feature_hvp launches, with its LDS and grid (cvf_align_feature_deriv_route answers with it, the entry point
+// launches by it): host arithmetic on the descriptor's counts and flags - no pointer of the descriptor is read but align_w, for NULL.
+int cvf_hvp_plan(const cvf_pp_desc* pp, int64_t B, int out_aligned16, cvf_deriv_plan* P) {
+  *P = cvf_deriv_plan{};
+  CVF_REQUIRE(pp && B > 0, "cvf_align_feature_hvp: null descriptor or empty batch (B=%lld)", (long long)B);
+  P->rows_per_launch = P->launches = 1;
+  if (pp->mode == CVF_PP_IDENTITY) return P->family = CVF_DERIV_ROUTE_IDENTITY, 0;   // r(x) = x: the Hessian is 0, a zero fill
+  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
+              "cvf_align_feature_hvp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_deriv_plan(pp, B, CVF_DERIV_HVP, 1, P);
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->d_r >= 1,
+              "cvf_align_feature_hvp: malformed descriptor (n_coord=%d n_align=%d d_r=%d)", pp->n_coord, pp->n_align, pp->d_r);
+  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
+              "cvf_align_feature_hvp: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
+              kLanePerFrameMaxCoord);
+  P->weighted = pp->align_w != nullptr;
+  if (pp->n_coord <= kLanePerFrameMaxCoord) {
+    // 192 coordinates: 3 * 64 * 193 * 4 = 148 224 B of the 160 KiB; the tables join them while they still fit
+    const size_t base = (size_t)3 * CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
+    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
+    CVF_REQUIRE(base <= kLdsLimit, "cvf_align_feature_hvp: frames of %d coordinates do not fit the LDS", pp->n_coord);
+    P->family = CVF_DERIV_ROUTE_SMALL;
+    P->tables_lds = base + tables <= kLdsLimit;
+    P->lds_bytes = (int64_t)(base + (P->tables_lds ? tables : 0));
+    P->grid = cvf_ntiles(B);
+    return 0;
+  }
+  CVF_REQUIRE(pp->n_slot > 0 && pp->n_ref > 0,
+              "cvf_align_feature_hvp: frames of more than %d coordinates need the slot and contribution-row tables "
+              "(atom_align, atom_slot, slot_atom, mrec, slot_row)", kLanePerFrameMaxCoord);
+  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_hvp: at most 2^31 - 1 frames per call");
+  const size_t lds = (size_t)pp->n_ref * 3 * sizeof(float);
+  CVF_REQUIRE(lds + sizeof(float) * (kAlignSums + kRecordSums) * (kLargeThreads / CVF_WAVE) <= kLdsLimit,
+              "cvf_align_feature_hvp: %d contribution rows (atoms summed over the features) do not fit the LDS", pp->n_ref);
+  P->family = CVF_DERIV_ROUTE_LARGE;
+  P->vec4 = pp->n_coord % 4 == 0 && out_aligned16;
+  P->lds_bytes = (int64_t)lds;
+  P->grid = B;
+  return 0;
+}
 
 extern "C" int cvf_align_feature_hvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled, const float* g_rows,
                                      const float* u_rows, float* h_rows, void* stream) {
@@ -431,51 +462,37 @@ extern "C" int cvf_align_feature_hvp(const cvf_pp_desc* pp, const float* x, int6
   if (B == 0) return 0;
   CVF_REQUIRE(h_rows, "cvf_align_feature_hvp: null h_rows");
   hipStream_t s = (hipStream_t)stream;
-  if (pp->mode == CVF_PP_IDENTITY) {   // r(x) = x: the Hessian is 0
+  cvf_deriv_plan P;
+  if (const int rc = cvf_hvp_plan(pp, B, ((uintptr_t)h_rows & 15) == 0, &P)) return rc;
+  if (P.family == CVF_DERIV_ROUTE_IDENTITY) {
     const hipError_t e = hipMemsetAsync(h_rows, 0, (size_t)B * pp->n_coord * sizeof(float), s);
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_hvp: identity zero fill: %s", hipGetErrorString(e));
     return 0;
   }
-  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
-              "cvf_align_feature_hvp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
   CVF_REQUIRE(g_rows && u_rows, "cvf_align_feature_hvp: null g_rows or u_rows");
-  if (pp->mode == CVF_PP_FEATURES) return features_hvp_launch(pp, x, B, g_rows, u_rows, h_rows, s);
-  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  if (P.family == CVF_DERIV_ROUTE_FEATURES) return features_hvp_launch(P, pp, x, B, g_rows, u_rows, h_rows, s);
   CVF_REQUIRE(x && aux_tiled, "cvf_align_feature_hvp: align mode needs x and the forward's aux rows");
-  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec && pp->d_r >= 1,
+  CVF_REQUIRE(pp->align_idx && pp->ref_c && pp->rec,
               "cvf_align_feature_hvp: malformed descriptor (n_coord=%d n_align=%d d_r=%d)", pp->n_coord, pp->n_align, pp->d_r);
-  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
-              "cvf_align_feature_hvp: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
-              kLanePerFrameMaxCoord);
-  if (pp->n_coord <= kLanePerFrameMaxCoord) {
-    // 192 coordinates: 3 * 64 * 193 * 4 = 148 224 B of the 160 KiB; the tables join them while they still fit
-    const size_t base = (size_t)3 * CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
-    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
-    CVF_REQUIRE(base <= kLdsLimit, "cvf_align_feature_hvp: frames of %d coordinates do not fit the LDS", pp->n_coord);
-    const bool tables_lds = base + tables <= kLdsLimit;
-    const size_t lds = base + (tables_lds ? tables : 0);
+  const size_t lds = (size_t)P.lds_bytes;
+  if (P.family == CVF_DERIV_ROUTE_SMALL) {
     auto launch = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)cvf_ntiles(B)), dim3(64), lds, s, *pp, x, B, aux_tiled, g_rows, u_rows, h_rows);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64), lds, s, *pp, x, B, aux_tiled, g_rows, u_rows, h_rows);
     };
-    if (tables_lds) launch(hvp_align_kernel<true>);
+    if (P.tables_lds) launch(hvp_align_kernel<true>);
     else launch(hvp_align_kernel<false>);
     return cvf_check_launch("hvp_align_kernel");
   }
-  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot && pp->n_slot > 0 && pp->n_ref > 0,
+  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot,
               "cvf_align_feature_hvp: frames of more than %d coordinates need the slot and contribution-row tables "
               "(atom_align, atom_slot, slot_atom, mrec, slot_row)", kLanePerFrameMaxCoord);
   CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "cvf_align_feature_hvp: mrec must be 16-byte aligned");
-  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_hvp: at most 2^31 - 1 frames per call");
-  const size_t lds = (size_t)pp->n_ref * 3 * sizeof(float);
-  CVF_REQUIRE(lds + sizeof(float) * (kAlignSums + kRecordSums) * (kLargeThreads / CVF_WAVE) <= kLdsLimit,
-              "cvf_align_feature_hvp: %d contribution rows (atoms summed over the features) do not fit the LDS", pp->n_ref);
-  const int vec4 = pp->n_coord % 4 == 0 && ((uintptr_t)h_rows & 15) == 0;
   auto launch = [&](auto kernel) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, g_rows, u_rows, h_rows, vec4);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, g_rows, u_rows, h_rows, P.vec4);
   };
-  if (pp->align_w) launch(hvp_large_kernel<true>);
+  if (P.weighted) launch(hvp_large_kernel<true>);
   else launch(hvp_large_kernel<false>);
   return cvf_check_launch("hvp_large_kernel");
 }

@@ -194,51 +194,80 @@ __global__ __launch_bounds__(kLargeThreads) void jvp_large_kernel(cvf_pp_desc pp
 
 }  // namespace
 
+// Which kernel cvf_align_feature_jvp launches, with its LDS and grid (cvf_align_feature_deriv_route answers with it, the entry point
+// launches by it): host arithmetic on the descriptor's counts and flags - no pointer of the descriptor is read but align_w, for NULL.
+int cvf_jvp_plan(const cvf_pp_desc* pp, int64_t B, cvf_deriv_plan* P) {
+  *P = cvf_deriv_plan{};
+  CVF_REQUIRE(pp && B > 0, "cvf_align_feature_jvp: null descriptor or empty batch (B=%lld)", (long long)B);
+  P->rows_per_launch = P->launches = 1;
+  if (pp->mode == CVF_PP_IDENTITY) {
+    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+    return P->family = CVF_DERIV_ROUTE_IDENTITY, 0;
+  }
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_deriv_plan(pp, B, CVF_DERIV_JVP, 1, P);   // (csrc/k1_features.hip)
+  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
+              "cvf_align_feature_jvp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->d_r >= 1,
+              "cvf_align_feature_jvp: malformed descriptor (n_coord=%d n_align=%d d_r=%d)", pp->n_coord, pp->n_align, pp->d_r);
+  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
+              "cvf_align_feature_jvp: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
+              kLanePerFrameMaxCoord);
+  P->weighted = pp->align_w != nullptr;
+  if (pp->n_coord <= kLanePerFrameMaxCoord) {
+    const size_t tiles = (size_t)2 * CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
+    const size_t qimg = (size_t)CVF_TILE * (pp->d_r | 1) * sizeof(float);
+    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
+    const size_t limit = 160 * 1024;
+    P->family = CVF_DERIV_ROUTE_SMALL;
+    P->q_lds = tiles + qimg <= limit;
+    P->tables_lds = P->q_lds && tiles + qimg + tables <= limit;
+    P->lds_bytes = (int64_t)(tiles + (P->q_lds ? qimg : 0) + (P->tables_lds ? tables : 0));
+    P->grid = cvf_ntiles(B);
+    return 0;
+  }
+  CVF_REQUIRE(pp->n_mrec > 0 && pp->n_slot > 0,
+              "cvf_align_feature_jvp: frames of more than %d coordinates need the slot tables (slot_atom, mrec)",
+              kLanePerFrameMaxCoord);
+  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_jvp: at most 2^31 - 1 frames per call");
+  P->family = CVF_DERIV_ROUTE_LARGE;
+  P->grid = B;
+  return 0;
+}
+
 extern "C" int cvf_align_feature_jvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
                                      const float* u_rows, float* q_rows, void* stream) {
   CVF_REQUIRE(pp && B >= 0, "cvf_align_feature_jvp: null descriptor or negative batch (B=%lld)", (long long)B);
   if (B == 0) return 0;
   CVF_REQUIRE(u_rows && q_rows, "cvf_align_feature_jvp: null u_rows or q_rows");
   hipStream_t s = (hipStream_t)stream;
-  if (pp->mode == CVF_PP_IDENTITY) {
-    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+  cvf_deriv_plan P;
+  if (const int rc = cvf_jvp_plan(pp, B, &P)) return rc;
+  if (P.family == CVF_DERIV_ROUTE_IDENTITY) {
     const hipError_t e = hipMemcpyAsync(q_rows, u_rows, (size_t)B * pp->n_coord * sizeof(float), hipMemcpyDeviceToDevice, s);
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_jvp: identity copy: %s", hipGetErrorString(e));
     return 0;
   }
-  if (pp->mode == CVF_PP_FEATURES) return cvf_features_jvp_launch(pp, x, B, u_rows, q_rows, s);   // (csrc/k1_features.hip)
-  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
-              "cvf_align_feature_jvp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
-  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  if (P.family == CVF_DERIV_ROUTE_FEATURES) return cvf_features_jvp_launch(pp, x, B, u_rows, q_rows, s);   // (csrc/k1_features.hip, by the same plan)
   CVF_REQUIRE(x && aux_tiled, "cvf_align_feature_jvp: align mode needs x and the forward's aux rows");
-  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec && pp->d_r >= 1,
+  CVF_REQUIRE(pp->align_idx && pp->ref_c && pp->rec,
               "cvf_align_feature_jvp: malformed descriptor (n_coord=%d n_align=%d d_r=%d)", pp->n_coord, pp->n_align, pp->d_r);
-  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
-              "cvf_align_feature_jvp: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
-              kLanePerFrameMaxCoord);
-  if (pp->n_coord <= kLanePerFrameMaxCoord) {
-    const size_t tiles = (size_t)2 * CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
-    const size_t qimg = (size_t)CVF_TILE * (pp->d_r | 1) * sizeof(float);
-    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
-    const size_t limit = 160 * 1024;
-    const bool q_lds = tiles + qimg <= limit;
-    const bool tables_lds = q_lds && tiles + qimg + tables <= limit;
-    const size_t lds = tiles + (q_lds ? qimg : 0) + (tables_lds ? tables : 0);
+  if (P.family == CVF_DERIV_ROUTE_SMALL) {
+    const size_t lds = (size_t)P.lds_bytes;
     auto launch = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)cvf_ntiles(B)), dim3(64), lds, s, *pp, x, B, aux_tiled, u_rows, q_rows);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64), lds, s, *pp, x, B, aux_tiled, u_rows, q_rows);
     };
-    if (tables_lds) launch(jvp_align_kernel<true, true>);
-    else if (q_lds) launch(jvp_align_kernel<false, true>);
+    if (P.tables_lds) launch(jvp_align_kernel<true, true>);
+    else if (P.q_lds) launch(jvp_align_kernel<false, true>);
     else launch(jvp_align_kernel<false, false>);
     return cvf_check_launch("jvp_align_kernel");
   }
-  CVF_REQUIRE(pp->mrec && pp->slot_atom && pp->n_mrec > 0 && pp->n_slot > 0,
+  CVF_REQUIRE(pp->mrec && pp->slot_atom,
               "cvf_align_feature_jvp: frames of more than %d coordinates need the slot tables (slot_atom, mrec)",
               kLanePerFrameMaxCoord);
   CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "cvf_align_feature_jvp: mrec must be 16-byte aligned");
-  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_jvp: at most 2^31 - 1 frames per call");
-  if (pp->align_w) hipLaunchKernelGGL(jvp_large_kernel<true>, dim3((unsigned)B), dim3(kLargeThreads), 0, s, *pp, x, aux_tiled, u_rows, q_rows);
-  else hipLaunchKernelGGL(jvp_large_kernel<false>, dim3((unsigned)B), dim3(kLargeThreads), 0, s, *pp, x, aux_tiled, u_rows, q_rows);
+  if (P.weighted) hipLaunchKernelGGL(jvp_large_kernel<true>, dim3((unsigned)P.grid), dim3(kLargeThreads), 0, s, *pp, x, aux_tiled, u_rows, q_rows);
+  else hipLaunchKernelGGL(jvp_large_kernel<false>, dim3((unsigned)P.grid), dim3(kLargeThreads), 0, s, *pp, x, aux_tiled, u_rows, q_rows);
   return cvf_check_launch("jvp_large_kernel");
 }

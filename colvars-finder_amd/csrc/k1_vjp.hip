@@ -131,58 +131,138 @@ __global__ __launch_bounds__(64) void vjp_align_kernel(cvf_pp_desc pp, const flo
 #undef CVF_VJP_WEIGHTED
 }  // namespace
 
+// Which kernel cvf_align_feature_vjp (which = CVF_DERIV_VJP) or cvf_align_feature_vjp_rows (CVF_DERIV_VJP_ROWS, k cotangents) launches,
+// with its LDS, grid and row grouping (cvf_align_feature_deriv_route answers with it, the two entry points launch by it): host arithmetic
+// on the descriptor's counts and flags - no pointer of the descriptor is read but align_w, for NULL.
+int cvf_vjp_plan(const cvf_pp_desc* pp, int64_t B, int which, int k, int out_aligned16, cvf_deriv_plan* P) {
+  *P = cvf_deriv_plan{};
+  const bool rows = which == CVF_DERIV_VJP_ROWS;
+  const char* who = rows ? "cvf_align_feature_vjp_rows" : "cvf_align_feature_vjp";
+  if (!rows) k = 1;
+  CVF_REQUIRE(pp && B > 0 && k >= 1 && k <= CVF_MAX_NETS, "%s: null argument, empty batch or k outside 1..%d (B=%lld k=%d)", who,
+              CVF_MAX_NETS, (long long)B, k);
+  P->rows_per_launch = P->launches = 1;
+  if (pp->mode == CVF_PP_IDENTITY) {
+    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+    return P->family = CVF_DERIV_ROUTE_IDENTITY, P->rows_per_launch = k, 0;
+  }
+  if (pp->mode == CVF_PP_FEATURES) return cvf_features_deriv_plan(pp, B, which, k, P);   // (csrc/k1_features.hip)
+  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
+              "%s: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd", who);
+  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3, "%s: malformed descriptor (n_coord=%d n_align=%d)", who, pp->n_coord, pp->n_align);
+  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
+              "%s: per-atom alignment weights on frames of at most %d coordinates need flags == 0", who, kLanePerFrameMaxCoord);
+  P->weighted = pp->align_w != nullptr;
+  const size_t limit = 160 * 1024;
+  if (pp->n_coord <= kLanePerFrameMaxCoord) {
+    const size_t img = (size_t)CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
+    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
+    P->family = CVF_DERIV_ROUTE_SMALL;
+    P->grid = cvf_ntiles(B);
+    if (!rows) {   // the x tile and one gradient image; the tables join them while they fit
+      P->tables_lds = 2 * img + tables <= limit;
+      P->lds_bytes = (int64_t)(2 * img + (P->tables_lds ? tables : 0));
+      return 0;
+    }
+    // images per pass: as many rows as keep the LDS within 40 KB (four workgroups per CU, as the single-cotangent kernel
+    // at config 3 - one row per pass there), at least one
+    const size_t per_row = img + (size_t)12 * CVF_TILE * sizeof(float);
+    const size_t budget = 40 * 1024;
+    P->tables_lds = img + per_row + tables <= limit;
+    const size_t fixed = img + (P->tables_lds ? tables : 0);
+    int kg = fixed + per_row * k <= budget ? k : (int)((budget > fixed + per_row ? budget - fixed : per_row) / per_row);
+    kg = kg < 1 ? 1 : kg;
+    const size_t lds = fixed + per_row * kg;
+    CVF_REQUIRE(lds <= limit, "%s: frames of %d coordinates do not fit the LDS", who, pp->n_coord);
+    P->rows_per_launch = kg;
+    P->lds_bytes = (int64_t)lds;
+    return 0;
+  }
+  CVF_REQUIRE(pp->n_slot > 0 && pp->n_ref > 0,
+              "%s: frames of more than %d coordinates need the slot and contribution-row tables "
+              "(atom_align, atom_slot, slot_atom, mrec, slot_row)", who, kLanePerFrameMaxCoord);
+  CVF_REQUIRE(B <= 0x7fffffff, "%s: at most 2^31 - 1 frames per call", who);
+  P->family = CVF_DERIV_ROUTE_LARGE;
+  P->vec4 = pp->n_coord % 4 == 0 && out_aligned16;
+  P->grid = B;
+  if (!rows) {
+    const size_t lds = (size_t)pp->n_ref * 3 * sizeof(float);
+    CVF_REQUIRE(lds + sizeof(float) * 12 * (kLargeThreads / CVF_WAVE) <= limit,
+                "%s: %d contribution rows (atoms summed over the features) do not fit the LDS", who, pp->n_ref);
+    P->lds_bytes = (int64_t)lds;
+    return 0;
+  }
+  // one launch per group of kg rows whose contribution rows share 64 KB (at config 5 all k rows fit one launch)
+  const size_t per_row = ((size_t)pp->n_ref * 3 + (size_t)12 * (kLargeThreads / CVF_WAVE) + 12) * sizeof(float);
+  CVF_REQUIRE(per_row <= limit, "%s: %d contribution rows (atoms summed over the features) do not fit the LDS", who, pp->n_ref);
+  const size_t budget = 64 * 1024;
+  int kg = per_row * k <= budget ? k : (int)(budget / per_row);
+  kg = kg < 1 ? 1 : kg;
+  P->rows_per_launch = kg;
+  P->launches = (k + kg - 1) / kg;
+  P->lds_bytes = (int64_t)(per_row * kg);
+  return 0;
+}
+
+extern "C" int cvf_align_feature_deriv_route(const cvf_pp_desc* pp, int64_t B, int which, int k, int out_aligned16, cvf_deriv_plan* plan) {
+  CVF_REQUIRE(plan, "cvf_align_feature_deriv_route: null plan");
+  switch (which) {
+    case CVF_DERIV_VJP:
+    case CVF_DERIV_VJP_ROWS: return cvf_vjp_plan(pp, B, which, k, out_aligned16 != 0, plan);
+    case CVF_DERIV_JVP: return cvf_jvp_plan(pp, B, plan);
+    case CVF_DERIV_HVP: return cvf_hvp_plan(pp, B, out_aligned16 != 0, plan);
+    case CVF_DERIV_FEATURES_FWD:
+    case CVF_DERIV_FEATURES_METRIC:
+      *plan = cvf_deriv_plan{};
+      CVF_REQUIRE(pp && B > 0, "cvf_align_feature_deriv_route: null descriptor or empty batch (B=%lld)", (long long)B);
+      CVF_REQUIRE(pp->mode == CVF_PP_FEATURES, "cvf_align_feature_deriv_route: call %d is answered for CVF_PP_FEATURES only "
+                  "(cvf_align_feature_route and cvf_metric_route answer for the other modes)", which);
+      return cvf_features_deriv_plan(pp, B, which, k, plan);
+    default: break;
+  }
+  *plan = cvf_deriv_plan{};
+  CVF_REQUIRE(false, "cvf_align_feature_deriv_route: unknown call %d", which);
+}
+
 extern "C" int cvf_align_feature_vjp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
                                      const float* g_rows, float* gx_rows, void* stream) {
   CVF_REQUIRE(pp && g_rows && gx_rows && B > 0, "cvf_align_feature_vjp: null argument or empty batch (B=%lld)", (long long)B);
   hipStream_t s = (hipStream_t)stream;
-  if (pp->mode == CVF_PP_IDENTITY) {
-    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+  cvf_deriv_plan P;
+  if (const int rc = cvf_vjp_plan(pp, B, CVF_DERIV_VJP, 1, ((uintptr_t)gx_rows & 15) == 0, &P)) return rc;
+  if (P.family == CVF_DERIV_ROUTE_IDENTITY) {
     const hipError_t e = hipMemcpyAsync(gx_rows, g_rows, (size_t)B * pp->n_coord * sizeof(float), hipMemcpyDeviceToDevice, s);
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_vjp: identity copy: %s", hipGetErrorString(e));
     return 0;
   }
-  if (pp->mode == CVF_PP_FEATURES) return cvf_features_vjp_launch(pp, x, B, 1, g_rows, gx_rows, s);   // (csrc/k1_features.hip)
-  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
-              "cvf_align_feature_vjp: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own autograd");
-  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  if (P.family == CVF_DERIV_ROUTE_FEATURES) return cvf_features_vjp_launch(pp, x, B, 1, g_rows, gx_rows, s);   // (csrc/k1_features.hip, by the same plan)
   CVF_REQUIRE(x && aux_tiled, "cvf_align_feature_vjp: align mode needs x and the forward's aux rows");
-  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
-              "cvf_align_feature_vjp: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
-  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
-              "cvf_align_feature_vjp: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
-              kLanePerFrameMaxCoord);
-  if (pp->n_coord <= kLanePerFrameMaxCoord) {
-    const int stride = x_tile_stride(pp->n_coord);
-    const size_t base = (size_t)2 * CVF_TILE * stride * sizeof(float);
-    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
-    const bool tables_lds = base + tables <= 160 * 1024;
-    const size_t lds = base + (tables_lds ? tables : 0);
+  CVF_REQUIRE(pp->align_idx && pp->ref_c && pp->rec, "cvf_align_feature_vjp: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord,
+              pp->n_align);
+  const size_t lds = (size_t)P.lds_bytes;
+  if (P.family == CVF_DERIV_ROUTE_SMALL) {
     auto launch = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)cvf_ntiles(B)), dim3(64), lds, s, *pp, x, B, aux_tiled, g_rows, gx_rows);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64), lds, s, *pp, x, B, aux_tiled, g_rows, gx_rows);
     };
-    if (tables_lds) launch(vjp_align_kernel<true>);
+    if (P.tables_lds) launch(vjp_align_kernel<true>);
     else launch(vjp_align_kernel<false>);
     return cvf_check_launch("vjp_align_kernel");
   }
-  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot && pp->n_slot > 0 && pp->n_ref > 0,
+  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot,
               "cvf_align_feature_vjp: frames of more than %d coordinates need the slot and contribution-row tables "
               "(atom_align, atom_slot, slot_atom, mrec, slot_row)", kLanePerFrameMaxCoord);
   CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "cvf_align_feature_vjp: mrec must be 16-byte aligned");
-  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_vjp: at most 2^31 - 1 frames per call");
-  const size_t lds = (size_t)pp->n_ref * 3 * sizeof(float);
-  CVF_REQUIRE(lds + sizeof(float) * 12 * (kLargeThreads / CVF_WAVE) <= 160 * 1024,
-              "cvf_align_feature_vjp: %d contribution rows (atoms summed over the features) do not fit the LDS", pp->n_ref);
-  const bool vec4 = pp->n_coord % 4 == 0 && ((uintptr_t)gx_rows & 15) == 0;
   auto launch = [&](auto kernel) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, g_rows, gx_rows);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, g_rows, gx_rows);
   };
-  if (pp->align_w) {
-    if (vec4) launch(vjp_weighted_large_kernel<true>);
+  if (P.weighted) {
+    if (P.vec4) launch(vjp_weighted_large_kernel<true>);
     else launch(vjp_weighted_large_kernel<false>);
   } else {
-    if (vec4) launch(vjp_large_kernel<true>);
+    if (P.vec4) launch(vjp_large_kernel<true>);
     else launch(vjp_large_kernel<false>);
   }
   return cvf_check_launch("vjp_large_kernel");
@@ -341,69 +421,45 @@ extern "C" int cvf_align_feature_vjp_rows(const cvf_pp_desc* pp, const float* x,
               "cvf_align_feature_vjp_rows: null argument, empty batch or k outside 1..%d (B=%lld k=%d)", CVF_MAX_NETS,
               (long long)B, k);
   hipStream_t s = (hipStream_t)stream;
-  if (pp->mode == CVF_PP_IDENTITY) {
-    CVF_REQUIRE(pp->d_r == pp->n_coord, "identity preprocessing needs d_r == n_coord");
+  cvf_deriv_plan P;
+  if (const int rc = cvf_vjp_plan(pp, B, CVF_DERIV_VJP_ROWS, k, ((uintptr_t)gx_rows & 15) == 0, &P)) return rc;
+  if (P.family == CVF_DERIV_ROUTE_IDENTITY) {
     const hipError_t e = hipMemcpyAsync(gx_rows, g_rows, (size_t)B * k * pp->n_coord * sizeof(float), hipMemcpyDeviceToDevice, s);
     CVF_REQUIRE(e == hipSuccess, "cvf_align_feature_vjp_rows: identity copy: %s", hipGetErrorString(e));
     return 0;
   }
-  if (pp->mode == CVF_PP_FEATURES) return cvf_features_vjp_launch(pp, x, B, k, g_rows, gx_rows, s);   // (csrc/k1_features.hip)
-  CVF_REQUIRE(pp->mode != CVF_PP_FACTORED,
-              "cvf_align_feature_vjp_rows: CVF_PP_FACTORED records come from a torch module, which is differentiated by its own "
-              "autograd");
-  CVF_REQUIRE(pp->mode == CVF_PP_ALIGN, "unknown pp mode %d", pp->mode);
+  if (P.family == CVF_DERIV_ROUTE_FEATURES) return cvf_features_vjp_launch(pp, x, B, k, g_rows, gx_rows, s);   // (csrc/k1_features.hip, by the same plan)
   CVF_REQUIRE(x && aux_tiled, "cvf_align_feature_vjp_rows: align mode needs x and the forward's aux rows");
-  CVF_REQUIRE(pp->n_coord % 3 == 0 && pp->n_align >= 3 && pp->align_idx && pp->ref_c && pp->rec,
-              "cvf_align_feature_vjp_rows: malformed descriptor (n_coord=%d n_align=%d)", pp->n_coord, pp->n_align);
-  CVF_REQUIRE(!pp->align_w || pp->flags == 0 || pp->n_coord > kLanePerFrameMaxCoord,
-              "cvf_align_feature_vjp_rows: per-atom alignment weights on frames of at most %d coordinates need flags == 0",
-              kLanePerFrameMaxCoord);
-  if (pp->n_coord <= kLanePerFrameMaxCoord) {
-    // images per launch: as many rows as keep the LDS within 40 KB (four workgroups per CU, as the single-cotangent kernel
-    // at config 3 - one row per pass there), at least one
-    const size_t img = (size_t)CVF_TILE * x_tile_stride(pp->n_coord) * sizeof(float);
-    const size_t per_row = img + (size_t)12 * CVF_TILE * sizeof(float);
-    const size_t tables = ((size_t)6 * pp->n_rec + 4 * (size_t)pp->n_align) * sizeof(float);
-    const size_t budget = 40 * 1024;
-    bool tables_lds = img + per_row + tables <= 160 * 1024;
-    const size_t fixed = img + (tables_lds ? tables : 0);
-    int kg = fixed + per_row * k <= budget ? k : (int)((budget > fixed + per_row ? budget - fixed : per_row) / per_row);
-    kg = kg < 1 ? 1 : kg;
-    const size_t lds = fixed + per_row * kg;
-    CVF_REQUIRE(lds <= 160 * 1024, "cvf_align_feature_vjp_rows: frames of %d coordinates do not fit the LDS", pp->n_coord);
+  CVF_REQUIRE(pp->align_idx && pp->ref_c && pp->rec, "cvf_align_feature_vjp_rows: malformed descriptor (n_coord=%d n_align=%d)",
+              pp->n_coord, pp->n_align);
+  const int kg = P.rows_per_launch;
+  if (P.family == CVF_DERIV_ROUTE_SMALL) {
+    const size_t lds = (size_t)P.lds_bytes;
     auto launch = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)cvf_ntiles(B)), dim3(64), lds, s, *pp, x, B, aux_tiled, k, kg, g_rows, gx_rows);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(64), lds, s, *pp, x, B, aux_tiled, k, kg, g_rows, gx_rows);
     };
-    if (tables_lds) launch(vjp_rows_small_kernel<true>);
+    if (P.tables_lds) launch(vjp_rows_small_kernel<true>);
     else launch(vjp_rows_small_kernel<false>);
     return cvf_check_launch("vjp_rows_small_kernel");
   }
-  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot && pp->n_slot > 0 && pp->n_ref > 0,
+  CVF_REQUIRE(pp->mrec && pp->slot_row && pp->slot_atom && pp->atom_align && pp->atom_slot,
               "cvf_align_feature_vjp_rows: frames of more than %d coordinates need the slot and contribution-row tables "
               "(atom_align, atom_slot, slot_atom, mrec, slot_row)", kLanePerFrameMaxCoord);
   CVF_REQUIRE(((uintptr_t)pp->mrec & 15) == 0, "cvf_align_feature_vjp_rows: mrec must be 16-byte aligned");
-  CVF_REQUIRE(B <= 0x7fffffff, "cvf_align_feature_vjp_rows: at most 2^31 - 1 frames per call");
-  const size_t per_row = ((size_t)pp->n_ref * 3 + (size_t)12 * (kLargeThreads / CVF_WAVE) + 12) * sizeof(float);
-  CVF_REQUIRE(per_row <= 160 * 1024,
-              "cvf_align_feature_vjp_rows: %d contribution rows (atoms summed over the features) do not fit the LDS", pp->n_ref);
-  const size_t budget = 64 * 1024;
-  int kg = per_row * k <= budget ? k : (int)(budget / per_row);
-  kg = kg < 1 ? 1 : kg;
-  const bool vec4 = pp->n_coord % 4 == 0 && ((uintptr_t)gx_rows & 15) == 0;
-  // one launch per group of kg rows (at config 5 all k rows fit one launch)
-  for (int i0 = 0; i0 < k; i0 += kg) {
+  const size_t per_row = (size_t)P.lds_bytes / kg;
+  for (int i0 = 0; i0 < k; i0 += kg) {   // P.launches launches, one per group of kg rows
     const int ng = k - i0 < kg ? k - i0 : kg;
     const size_t lds = per_row * ng;
     auto launch = [&](auto kernel) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, k, i0, ng, g_rows, gx_rows);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P.grid), dim3(kLargeThreads), lds, s, *pp, x, aux_tiled, k, i0, ng, g_rows, gx_rows);
     };
-    if (pp->align_w) {
-      if (vec4) launch(vjp_rows_weighted_large_kernel<true>);
+    if (P.weighted) {
+      if (P.vec4) launch(vjp_rows_weighted_large_kernel<true>);
       else launch(vjp_rows_weighted_large_kernel<false>);
     } else {
-      if (vec4) launch(vjp_rows_large_kernel<true>);
+      if (P.vec4) launch(vjp_rows_large_kernel<true>);
       else launch(vjp_rows_large_kernel<false>);
     }
     const int rc = cvf_check_launch("vjp_rows_large_kernel");

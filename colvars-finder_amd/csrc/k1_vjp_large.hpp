@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kLargeThreads) void CVF_VJP_LARGE_KERNEL(cvf_pp_des
     } else if (type == CVF_FEAT_ANGLE) {
       const AngleG e = angle_eval(at(s0), at(s1), at(s2));
       float gs = gf[out];
-      if (pp.use_angle_value) gs = -gs / acos_den(e.cs);
+      if (pp.use_angle_value) gs = -gs / acos_den(e);
       put(r0, gs * e.ga);
       put(r1, gs * e.gb);
       put(r2, gs * e.gc);
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kLargeThreads) void CVF_VJP_ROWS_LARGE_KERNEL(cvf_p
         const AngleG e = angle_eval(at(d.s0), at(d.s1), at(d.s2));
         for (int ii = 0; ii < ng; ++ii) {
           float gs = gf[(i0 + ii) * pp.d_r + d.out];
-          if (pp.use_angle_value) gs = -gs / acos_den(e.cs);
+          if (pp.use_angle_value) gs = -gs / acos_den(e);
           put(ii, d.r0, gs * e.ga);
           put(ii, d.r1, gs * e.gb);
           put(ii, d.r2, gs * e.gc);

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64 * kMWaves) void metric_rows_kernel(cvf_pp_desc p
       const AngleG e = angle_eval(x0, x1, x2);
       ge.v0 = e.ga; ge.v1 = e.gc;
       ge.cs = e.cs;
-      ge.sn = -1.0f / acos_den(e.cs);
+      ge.sn = -1.0f / acos_den(e);
     } else if (ty == CVF_FEAT_DIHEDRAL) {
       const DihedralG e = dihedral_eval(x0, x1, x2, x3);
       ge.v0 = e.g1; ge.v1 = e.g4;

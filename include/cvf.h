@@ -258,6 +258,36 @@ int cvf_align_feature_jvp(const cvf_pp_desc* pp, const float* x, int64_t B, cons
 int cvf_align_feature_hvp(const cvf_pp_desc* pp, const float* x, int64_t B, const float* aux_tiled,
                           const float* g_rows, const float* u_rows, float* h_rows, void* stream);
 
+/* Which kernel instance a cvf_align_feature_vjp / _vjp_rows / _jvp / _hvp call on B frames launches, with its LDS, grid and row
+ * grouping, by the very function the four calls launch by (host arithmetic; no pointer of the descriptor is read but align_w, and
+ * that only for NULL, so a descriptor that carries its counts and flags is enough).  k: the cotangents of _vjp_rows (ignored by the
+ * other three).  out_aligned16: whether gx_rows / h_rows is 16-byte aligned - with n_coord % 4 == 0 it selects the 16-byte stores of
+ * the kernels for frames of more than 192 coordinates.  Returns 0 and fills *plan, or a negative value (and cvf_last_error()) for a
+ * descriptor, a batch or a k the call refuses.  Fields that do not apply to the family are 0.  For CVF_PP_FEATURES descriptors two
+ * more values of `which` answer for the launches of cvf_align_feature_fwd and cvf_metric_apply (k nets) in csrc/k1_features.hip. */
+enum { CVF_DERIV_VJP = 0, CVF_DERIV_VJP_ROWS = 1, CVF_DERIV_JVP = 2, CVF_DERIV_HVP = 3,
+       CVF_DERIV_FEATURES_FWD = 4, CVF_DERIV_FEATURES_METRIC = 5 /* CVF_PP_FEATURES only */ };
+enum {
+  CVF_DERIV_ROUTE_IDENTITY = 0, /* a copy (vjp, vjp_rows, jvp) or a zero fill (hvp): no kernel of these files */
+  CVF_DERIV_ROUTE_FEATURES = 1, /* features_{vjp,jvp,hvp,fwd,metric}_kernel: CVF_PP_FEATURES, 1 << lg frames per workgroup */
+  CVF_DERIV_ROUTE_SMALL = 2,    /* {vjp_align,vjp_rows_small,hvp_align}_kernel<tables_lds>, jvp_align_kernel<tables_lds, q_lds>: n_coord <= 192 */
+  CVF_DERIV_ROUTE_LARGE = 3     /* {vjp,vjp_rows}_[weighted_]large_kernel<vec4>, {jvp,hvp}_large_kernel<weighted>: n_coord > 192 */
+};
+typedef struct {
+  int32_t family;          /* CVF_DERIV_ROUTE_* */
+  int32_t tables_lds;      /* small: rec, align_idx and ref_c are copied to LDS */
+  int32_t q_lds;           /* small jvp: the [64][d_r | 1] result image is in LDS */
+  int32_t u_lds;           /* features hvp: the feature atoms of u are staged in LDS */
+  int32_t weighted;        /* align_w != NULL */
+  int32_t vec4;            /* large vjp, vjp_rows, hvp: 16-byte stores of the dense row */
+  int32_t lg;              /* features: log2 frames per workgroup */
+  int32_t rows_per_launch; /* vjp_rows: rows whose images share the LDS (kg); features metric: nets per pass; else 1 */
+  int32_t launches;        /* vjp_rows on large frames: ceil(k / kg); else 1 */
+  int32_t reserved;
+  int64_t lds_bytes, grid; /* dynamic LDS and workgroups of the first launch (identity: 0) */
+} cvf_deriv_plan;
+int cvf_align_feature_deriv_route(const cvf_pp_desc* pp, int64_t B, int which, int k, int out_aligned16, cvf_deriv_plan* plan);
+
 /* --- K2+K3: per frame and net, q = J A J^T g and E = g^T J A J^T g with J the Jacobian
  * of r at the frame and A = diag(a).  Replaces the k autograd.grad calls through
  * pp_layer at core.py:424 and the a-weighted square sums at core.py:426,438; the
@@ -269,7 +299,9 @@ int cvf_metric_apply(const cvf_pp_desc* pp, const float* x, int64_t B, const flo
 /* Which kernel a cvf_metric_apply (with_stats = 0) or cvf_metric_apply_stats (with_stats = 1) call on B frames and k nets launches,
  * by the very function the two calls launch by (host arithmetic; no pointer of the descriptor is read, so a descriptor that carries only
  * its counts and flags is enough).  Returns 0 and fills *plan, or a negative value (and cvf_last_error()) for a descriptor or a batch the
- * calls refuse.  Fields that do not apply to the family are 0. */
+ * calls refuse.  Fields that do not apply to the family are 0.  CVF_METRIC_ROUTE_FEATURES: the launch of csrc/k1_features.hip (frames per
+ * workgroup, nets per pass, LDS, grid) is answered by cvf_align_feature_deriv_route(pp, B, CVF_DERIV_FEATURES_METRIC, k, 0, &plan) above,
+ * beside the other launches of that file. */
 enum {
   CVF_METRIC_ROUTE_IDENTITY = 0, /* metric_identity_kernel */
   CVF_METRIC_ROUTE_FACTORED = 1, /* csrc/metric_factor.hip */

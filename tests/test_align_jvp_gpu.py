@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.autograd.forward_ad as fwAD
 
+from tests import deriv_measure as DM
 from tests.align_jvp_cases import abi_fwd, abi_jvp, abi_vjp, inputs, layer_of, oracle_of, oracle_refs, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +41,15 @@ ABI_CASES = [
     ("feat10", 131, False), ("feat10", 131, True), ("feat65", 64, False), ("feat65", 64, True)]
 
 
+assert DM.FLOOR == TOL
+
+
+def typed_refs(name, B, angle_value):
+    """The per-frame, per-type reference and twins of a shape (tests/deriv_measure.py), on the inputs of the shape."""
+    s = inputs(name, B)
+    return DM.jvp_type_refs(s.feats, angle_value, DM.oracle_builder(s.n, s.align, s.ref, s.w, angle_value), s.traj, s.u)
+
+
 @pytest.mark.parametrize("name,B,angle_value", ABI_CASES)
 def test_jvp_abi_vs_oracle(dev, name, B, angle_value):
     s = inputs(name, B)
@@ -52,6 +62,17 @@ def test_jvp_abi_vs_oracle(dev, name, B, angle_value):
     err = rel_err(got, want)
     print(f"[jvp] {name} B={B} angle_value={angle_value}: max err / max |q_ref| = {err:.2e}")
     assert err <= s.tol == TOL, err
+    # per frame and per feature type (tests/deriv_measure.py): the output columns grouped by type, the worst frame counts; bar
+    # max(1.5e-5, 3 x the fp32 twin on the same inputs and type), capped at 1e-4
+    q_ref, twins = typed_refs(name, B, angle_value)
+    bad = []
+    for t, (cols, twin) in twins.items():
+        e, bar = float(DM.frame_errors(got[:, cols], q_ref[:, cols]).max()), DM.bar_of(twin)
+        print(f"[jvp] {name} B={B} angle_value={angle_value} {t}: worst frame {e:.2e}, twin {twin:.2e}, bar {bar:.2e}")
+        assert bar <= DM.CEILING
+        if e > bar:
+            bad.append((t, e, bar))
+    assert not bad, (name, bad)
 
 
 # ------------------------------------------------------------------------------------------------ 2. adjointness

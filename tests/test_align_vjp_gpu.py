@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import deriv_measure as DM
 from tests.synth import Traj, diag_coeff_for, make_molecule_traj
 
 pytestmark = pytest.mark.gpu
@@ -111,14 +112,27 @@ def rel_err(got, want):
 
 
 # ------------------------------------------------------------------------------------------------ C ABI vs oracle
-@pytest.mark.parametrize("name,B,angle_value,tol", [
+ABI_CASES = [
     ("mixed10", 131, False, SMALL_TOL), ("mixed10", 131, True, SMALL_TOL),
     ("pos22", 1, False, SMALL_TOL), ("pos22", 64, False, SMALL_TOL), ("pos22", 20000, False, SMALL_TOL),
     ("weighted12", 64, False, SMALL_TOL), ("weighted12_mixed", 64, True, SMALL_TOL),
     ("mixed64", 64, False, SMALL_TOL), ("mixed64", 64, True, SMALL_TOL),
     ("mixed65", 64, False, LARGE_TOL), ("mixed65", 64, True, LARGE_TOL),
     ("mixed1000", 130, True, LARGE_TOL), ("mixed1000", 130, False, LARGE_TOL),
-    ("c5", 48, False, LARGE_TOL), ("c5", 48, True, LARGE_TOL)])
+    ("c5", 48, False, LARGE_TOL), ("c5", 48, True, LARGE_TOL)]
+assert DM.FLOOR == SMALL_TOL == LARGE_TOL
+
+
+def typed_refs(name, B, angle_value):
+    """The per-frame, per-type references and twins of a shape (tests/deriv_measure.py), on the inputs of build(name, B, ...)."""
+    n, align, feats, w = case(name)
+    traj, _, ref = make_molecule_traj(n, B, seed=100 + n)
+    d_r = sum(len(c) for c in DM.columns_of(feats, angle_value).values())
+    g = torch.randn(B, d_r, generator=torch.Generator().manual_seed(B + n), dtype=torch.float64)
+    return DM.vjp_type_refs(feats, angle_value, DM.oracle_builder(n, align, ref, w, angle_value), traj, g), traj, g
+
+
+@pytest.mark.parametrize("name,B,angle_value,tol", ABI_CASES)
 def test_vjp_abi_vs_oracle(dev, name, B, angle_value, tol):
     layer, traj, ref, g = build(name, B, angle_value, dev)
     _, gx = abi(layer, traj, g)
@@ -128,6 +142,18 @@ def test_vjp_abi_vs_oracle(dev, name, B, angle_value, tol):
     err = rel_err(got, want)
     print(f"[vjp] {name} B={B} angle_value={angle_value}: max err / max |g_ref| = {err:.2e}")
     assert err <= tol, err
+    # per frame and per feature type (tests/deriv_measure.py): the cotangent restricted to one type's columns, the worst frame counts;
+    # bar max(1.5e-5, 3 x the fp32 twin on the same inputs and type), capped at 1e-4
+    refs, traj2, g2 = typed_refs(name, B, angle_value)
+    assert np.array_equal(traj2, traj) and torch.equal(g2, g)
+    bad = []
+    for t, (cols, want_t, twin) in refs.items():
+        e, bar = float(DM.frame_errors(abi(layer, traj, DM.masked(g, cols))[1].cpu().numpy(), want_t).max()), DM.bar_of(twin)
+        print(f"[vjp] {name} B={B} angle_value={angle_value} {t}: worst frame {e:.2e}, twin {twin:.2e}, bar {bar:.2e}")
+        assert bar <= DM.CEILING
+        if e > bar:
+            bad.append((t, e, bar))
+    assert not bad, (name, bad)
 
 
 def test_vjp_c5_vs_torch_twin(dev):
