@@ -289,6 +289,42 @@ _SIGNATURES["cvf_cv_frame_large_shared_supported"] = _SIGNATURES["cvf_cv_frame_l
 _SIGNATURES["cvf_cv_frame_large_shared_lds_bytes"] = _SIGNATURES["cvf_cv_frame_large_lds_bytes"]
 _SIGNATURES["cvf_cv_frame_large_shared_eval"] = _SIGNATURES["cvf_cv_frame_large_eval"]
 _SIGNATURES["cvf_cv_file_n_shared"] = (C.c_int, [C.c_char_p, C.c_int64])
+
+# bias energy and forces along the CV in one launch, in the MD engine's arrays (csrc/cv_bias.hip)
+BIAS_MAX_TERMS = 16
+BIAS_HARMONIC, BIAS_UPPER_WALL, BIAS_LOWER_WALL, BIAS_LINEAR, BIAS_TABLE = range(5)
+BIAS_KINDS = {"harmonic": BIAS_HARMONIC, "upper_wall": BIAS_UPPER_WALL, "lower_wall": BIAS_LOWER_WALL, "linear": BIAS_LINEAR,
+              "table": BIAS_TABLE}
+
+
+class BiasTerm(C.Structure):
+    """``cvf_bias_term`` (include/cvf.h)."""
+    _fields_ = [("kind", C.c_int32), ("cv", C.c_int32), ("kappa", C.c_float), ("center", C.c_float), ("tab_off", C.c_int32),
+                ("n_nodes", C.c_int32), ("lo", C.c_float), ("inv_h", C.c_float)]
+
+
+class BiasDesc(C.Structure):
+    """``cvf_bias_desc`` (include/cvf.h): ``table`` is a device pointer to ``n_table`` floats, read at launch time."""
+    _fields_ = [("n_terms", C.c_int32), ("n_table", C.c_int32), ("term", BiasTerm * BIAS_MAX_TERMS), ("table", C.c_void_p)]
+
+
+class MDLayout(C.Structure):
+    """``cvf_md_layout`` (include/cvf.h): where the CV's atoms lie in the engine's position and force arrays."""
+    _fields_ = [("atom_index", C.c_void_p), ("atom_stride", C.c_int32), ("reserved", C.c_int32), ("x_frame_stride", C.c_int64),
+                ("f_frame_stride", C.c_int64)]
+
+
+_SIGNATURES["cvf_cv_bias_check"] = (C.c_int, [C.POINTER(BiasDesc), C.c_int])
+_SIGNATURES["cvf_cv_frame_bias_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+_SIGNATURES["cvf_cv_frame_bias_eval"] = (C.c_int, [C.POINTER(MLPDesc), C.c_void_p, C.c_int, C.POINTER(PPDesc), C.POINTER(BiasDesc),
+                                                   C.POINTER(MDLayout), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p])
+_SIGNATURES["cvf_cv_frame_bias_shared_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+_SIGNATURES["cvf_cv_frame_bias_shared_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
+_SIGNATURES["cvf_cv_frame_large_bias_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+_SIGNATURES["cvf_cv_frame_large_bias_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
+_SIGNATURES["cvf_cv_frame_large_bias_shared_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+_SIGNATURES["cvf_cv_frame_large_bias_shared_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

@@ -213,6 +213,8 @@ class FrameCV:
     4.17) the predicates and launches are the ``_shared`` ones and the three-call recipe runs ``cvf_cv_nets_shared_eval``;
     ``route``, ``supported`` and ``supported_large`` keep their meaning."""
 
+    _infix = ""   # the one-launch entry points are cvf_cv_frame[_large]<_infix>[_shared]_supported / _eval (BiasedCV: "_bias")
+
     def __init__(self, path_or_cv, device="cuda", large_frames=False):
         import ctypes as C
         if isinstance(path_or_cv, (str, bytes)) or hasattr(path_or_cv, "__fspath__"):
@@ -235,12 +237,11 @@ class FrameCV:
         # form C: the _shared entry points take n_shared where their namesakes take upto_layer
         sh = self.n_shared > 0
         self._cut = self.n_shared if sh else int(self.model.upto_layer)
-        self._frame_eval = lib.cvf_cv_frame_shared_eval if sh else lib.cvf_cv_frame_eval
-        self._large_eval = lib.cvf_cv_frame_large_shared_eval if sh else lib.cvf_cv_frame_large_eval
+        entry = lambda large, what: getattr(lib, "cvf_cv_frame" + large + self._infix + ("_shared" if sh else "") + what)
+        self._frame_eval, self._large_eval = entry("", "_eval"), entry("_large", "_eval")
         self._nets_scratch = lib.cvf_cv_nets_shared_scratch_floats if sh else lib.cvf_cv_nets_scratch_floats
         self._nets_eval = lib.cvf_cv_nets_shared_eval if sh else lib.cvf_cv_nets_eval
-        frame_ok = lib.cvf_cv_frame_shared_supported if sh else lib.cvf_cv_frame_supported
-        large_ok = lib.cvf_cv_frame_large_shared_supported if sh else lib.cvf_cv_frame_large_supported
+        frame_ok, large_ok = entry("", "_supported"), entry("_large", "_supported")
         ok = frame_ok(C.byref(self.model.mlp), self._cut, C.byref(self.model.pp)) == 1
         self.supported = (ok, None if ok else lib.cvf_last_error().decode())
         ok_large = large_ok(C.byref(self.model.mlp), self._cut, C.byref(self.model.pp)) == 1
@@ -297,3 +298,178 @@ class FrameCV:
         else:   # the contraction at the feature level (k terms per feature), then one coordinate pass
             g = torch.einsum("bk,bkr->br", cf, G).contiguous()
             _hip.check(lib.cvf_align_feature_vjp(pp, P(x), B, P(aux), P(g), P(D), s), "cvf_align_feature_vjp")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Bias energy and forces along the CV in one launch, in an MD engine's arrays (include/cvf.h: cvf_cv_*_bias_*)
+# ------------------------------------------------------------------------------------------------------------------------
+def bias_desc(terms, k, device=None):
+    """``(BiasDesc, table)`` of a list of bias terms on ``k`` CVs, checked with ``cvf_cv_bias_check`` (``ValueError`` with the C
+    message).  A term is a dict or a tuple in the vocabulary of ``cvf_bias_desc``:
+
+    ``{"kind": "harmonic" | "upper_wall" | "lower_wall", "cv": i, "kappa": .., "center": ..}`` or ``(kind, i, kappa, center)``;
+    ``{"kind": "linear", "cv": i, "kappa": ..}`` or ``("linear", i, kappa)``;
+    ``{"kind": "table", "cv": i, "lo": .., "inv_h": .. (or "h": spacing), "u": U at the nodes, "du": U' at the nodes}`` or
+    ``("table", i, lo, h, u, du)``.
+
+    ``table`` is the fp32 tensor (on ``device``; ``None`` without table terms) of all nodes' ``(U_j, U'_j)`` pairs that
+    ``BiasDesc.table`` points to; term ``t``'s pairs start at ``desc.term[t].tab_off``.  ``device=None`` keeps it on the CPU
+    (for checks without a GPU: the pointer is then a host pointer, which no launch may take)."""
+    import numpy as np
+    d = _hip.BiasDesc()
+    d.n_terms = len(terms)
+    pairs = []
+    n_table = 0
+    for t, term in enumerate(terms[:_hip.BIAS_MAX_TERMS]):
+        if not isinstance(term, dict):
+            kind = term[0]
+            keys = ("kind", "cv", "kappa") if kind == "linear" else ("kind", "cv", "lo", "h", "u", "du") if kind == "table" \
+                else ("kind", "cv", "kappa", "center")
+            if len(term) != len(keys):
+                raise ValueError(f"bias term {t}: a {kind!r} tuple is {keys}, got {len(term)} entries")
+            term = dict(zip(keys, term))
+        kind = term["kind"]
+        if isinstance(kind, str):
+            if kind not in _hip.BIAS_KINDS:
+                raise ValueError(f"bias term {t}: kind {kind!r} is none of {sorted(_hip.BIAS_KINDS)}")
+            kind = _hip.BIAS_KINDS[kind]
+        e = d.term[t]
+        e.kind, e.cv = int(kind), int(term["cv"])
+        if kind == _hip.BIAS_TABLE:
+            u, du = np.asarray(term["u"], dtype=np.float32).reshape(-1), np.asarray(term["du"], dtype=np.float32).reshape(-1)
+            if u.shape != du.shape:
+                raise ValueError(f"bias term {t}: {u.size} values of U and {du.size} of U' at the nodes")
+            e.lo = float(term["lo"])
+            e.inv_h = float(term["inv_h"]) if "inv_h" in term else 1.0 / float(term["h"])
+            e.tab_off, e.n_nodes = n_table, int(u.size)
+            pairs.append(np.stack([u, du], axis=1).reshape(-1))
+            n_table += 2 * int(u.size)
+        else:
+            e.kappa, e.center = float(term["kappa"]), float(term.get("center", 0.0))
+    d.n_table = n_table
+    table = torch.from_numpy(np.concatenate(pairs)) if pairs else None
+    if table is not None:
+        table = table if device is None else table.to(device)
+        d.table = table.data_ptr()
+    if _hip.lib().cvf_cv_bias_check(d, int(k)) != 1:
+        raise ValueError(_hip.lib().cvf_last_error().decode())
+    return d, table
+
+
+def bias_torch(desc, table, xi):
+    """``(U [B], dU [B, k])`` of ``xi [B, k]`` by the term formulas of csrc/cvf_bias.hpp written with torch operators in ``xi``'s
+    type and on its device, the table read now - what ``BiasedCV``'s ``"three-call"`` route evaluates in fp32."""
+    U, dU = torch.zeros_like(xi[:, 0]), torch.zeros_like(xi)
+    zero = torch.zeros_like(xi[:, 0])
+    for t in range(desc.n_terms):
+        e = desc.term[t]
+        x = xi[:, e.cv]
+        d = x - e.center
+        if e.kind == _hip.BIAS_LINEAR:
+            u, du = e.kappa * x, e.kappa + zero
+        elif e.kind == _hip.BIAS_TABLE:
+            nodes = table[e.tab_off:e.tab_off + 2 * e.n_nodes].to(device=xi.device, dtype=xi.dtype).reshape(-1, 2)
+            last, h = e.n_nodes - 1, 1.0 / e.inv_h
+            s = (x - e.lo) * e.inv_h
+            j = s.detach().clamp(0, last - 1).floor().long()
+            w = s - j
+            w2, w3 = w * w, w * w * w
+            u0, d0, u1, d1 = nodes[j, 0], nodes[j, 1], nodes[j + 1, 0], nodes[j + 1, 1]
+            g00 = 6.0 * (w2 - w)
+            u = (2.0 * w3 - 3.0 * w2 + 1.0) * u0 + (3.0 * w2 - 2.0 * w3) * u1 + h * ((w3 - 2.0 * w2 + w) * d0 + (w3 - w2) * d1)
+            du = e.inv_h * (g00 * (u0 - u1)) + (3.0 * w2 - 4.0 * w + 1.0) * d0 + (3.0 * w2 - 2.0 * w) * d1
+            below, above = ~(s >= 0), s > last
+            u = torch.where(below, nodes[0, 0] + nodes[0, 1] * (x - e.lo), torch.where(above, nodes[last, 0] + nodes[last, 1] * ((s - last) * h), u))
+            du = torch.where(below, nodes[0, 1] + zero, torch.where(above, nodes[last, 1] + zero, du))
+        else:
+            on = torch.ones_like(x, dtype=torch.bool) if e.kind == _hip.BIAS_HARMONIC else (x > e.center if e.kind == _hip.BIAS_UPPER_WALL else x < e.center)
+            u, du = torch.where(on, 0.5 * e.kappa * d * d, zero), torch.where(on, e.kappa * d, zero)
+        U = U + u
+        dU[:, e.cv] = dU[:, e.cv] + du
+    return U, dU
+
+
+class BiasedCV(FrameCV):
+    """Bias energy and forces along a saved (path) or live (``colvar_model()``) CV, accumulated into an MD engine's force array
+    in ONE launch (``cvf_cv_frame_bias_eval`` and its ``_large`` / ``_shared`` forms).
+
+    The model is bound as :class:`FrameCV` binds it.  ``terms`` is the bias (:func:`bias_desc`); ``bc.table`` is the device
+    tensor of all table nodes that the launch reads AT LAUNCH TIME - update it in place (metadynamics, ABF) and the next call
+    sees it.  ``atom_index`` (no repeats; ``None`` = the identity) and ``atom_stride`` say where the CV's ``n_coord / 3`` atoms
+    lie in the engine's arrays: atom ``a`` of frame ``b`` is ``X_all[b].reshape(-1)[atom_index[a] * atom_stride + c]``.
+
+    ``bc(X_all, F_all)`` takes float32 device tensors ``[B, ...]`` whose frames are contiguous (a frame stride larger than the
+    frame is fine: slice a larger tensor), ADDS ``- sum_t U_t'(xi) d xi / d x`` to ``F_all`` in place - only the CV's atoms'
+    three floats are touched - and returns ``(xi [B, k], U [B], dU [B, k])``, ``dU[b, i] = sum_{t: cv = i} U_t'(xi_i)``.
+
+    ``bc.route`` is ``"frame"`` (one wave per frame), ``"frame-large"`` (``large_frames=True``, one workgroup per frame) or
+    ``"three-call"``: ``FrameCV``'s recipe for all k gradient rows, the same term formulas in torch fp32 (:func:`bias_torch`)
+    and one contraction - several launches, the same result up to rounding (another summation order, torch's own elementwise
+    arithmetic), for the models the one launch declines."""
+
+    _infix = "_bias"
+
+    def __init__(self, path_or_cv, terms, device="cuda", large_frames=False, atom_index=None, atom_stride=3):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None and torch.cuda.is_available():   # (the engine's tensors are compared with it)
+            device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(path_or_cv, device=device, large_frames=large_frames)   # (binds; route and supported from the bias predicates)
+        self._bias_eval = {"frame": self._frame_eval, "frame-large": self._large_eval}
+        with torch.cuda.device(self.device):
+            self.desc, self.table = bias_desc(terms, self.k, self.device)
+        self.atom_stride = int(atom_stride)
+        if self.atom_stride < 3:
+            raise ValueError(f"atom_stride = {atom_stride}: an atom has at least 3 floats")
+        self.atom_index = None
+        if atom_index is not None:
+            if self.n_coord % 3 != 0:
+                raise ValueError(f"atom_index with n_coord = {self.n_coord}: an atom index needs frames of whole atoms")
+            idx = torch.as_tensor(atom_index).reshape(-1).to(torch.int64).cpu()
+            if idx.numel() != self.n_coord // 3 or (idx < 0).any() or idx.unique().numel() != idx.numel():
+                raise ValueError(f"atom_index: {self.n_coord // 3} distinct non-negative atom numbers are needed "
+                                 f"(got {idx.numel()}, {idx.unique().numel()} distinct, min {int(idx.min()) if idx.numel() else 0})")
+            self.atom_index = idx.to(device=self.device, dtype=torch.int32)
+        a = torch.arange(self.n_coord, device=self.device)
+        at = a // 3 if self.atom_index is None else self.atom_index.long()[a // 3]
+        self._cols = at * self.atom_stride + a % 3            # float of coordinate j inside a frame
+        self._extent = int(self._cols.max()) + 1
+
+    def _frames(self, T, name):
+        if not (torch.is_tensor(T) and T.dtype == torch.float32 and T.device == self.device and T.dim() >= 2):
+            raise ValueError(f"{name} must be a float32 tensor [B, ...] on {self.device}")
+        B = int(T.shape[0])
+        per = int(T[0].numel()) if B else 0
+        try:
+            V = T.view(B, per)      # (frames contiguous inside; any stride between them)
+        except RuntimeError as e:
+            raise ValueError(f"{name}: the frames must be contiguous ({e})") from e
+        if B and per < self._extent:
+            raise ValueError(f"{name}: frames of {per} floats, the CV's atoms reach float {self._extent - 1}")
+        return V, B, (int(V.stride(0)) if B > 1 else per)
+
+    def __call__(self, X_all, F_all):
+        import ctypes as C
+        Xv, B, xs = self._frames(X_all, "X_all")
+        Fv, Bf, fs = self._frames(F_all, "F_all")
+        if B != Bf:
+            raise ValueError(f"X_all has {B} frames, F_all {Bf}")
+        lib, m, k, dev = _hip.lib(), self.model, self.k, self.device
+        with torch.cuda.device(dev):
+            s = _hip.stream()
+            xi, U, dU = (torch.empty(B, k, device=dev), torch.empty(B, device=dev), torch.empty(B, k, device=dev))
+            if B == 0:
+                return xi, U, dU
+            if self.route in self._bias_eval:
+                lay = _hip.MDLayout(self.atom_index.data_ptr() if self.atom_index is not None else None, self.atom_stride, 0, xs, fs)
+                fn = self._bias_eval[self.route]
+                _hip.check(fn(C.byref(m.mlp), C.c_void_p(m.theta), self._cut, C.byref(m.pp), C.byref(self.desc), C.byref(lay),
+                              C.c_void_p(Xv.data_ptr()), B, _hip.ptr(xi), _hip.ptr(U), _hip.ptr(dU), C.c_void_p(Fv.data_ptr()), s),
+                           fn.__name__)
+            else:
+                x = Xv[:, self._cols].contiguous()
+                D = torch.empty(B, k, self.n_coord, device=dev)
+                self._three_call(x, None, xi, D, s)
+                U, dU = bias_torch(self.desc, self.table, xi)
+                Fv[:, self._cols] -= torch.einsum("bk,bkn->bn", dU, D)
+        return xi, U, dU
+

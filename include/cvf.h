@@ -901,6 +901,87 @@ int cvf_cv_frame_large_shared_eval(const cvf_mlp_desc* mlp, const float* theta, 
                                    int64_t B, const float* coef, float* xi_rows, float* gx_rows, void* stream);
 int cvf_cv_file_n_shared(const void* blob_host, int64_t nbytes);
 
+/* --- bias energy and forces along the CV in ONE launch, in the MD engine's own arrays (csrc/cv_bias.hip; the term formulas:
+ * csrc/cvf_bias.hpp, host and device from one text).  The coefficient of a bias force is -dU/dxi_i(xi(x)):
+ * it depends on the xi the launch is computing, so with cvf_cv_frame_eval an engine launches twice around a host round trip, or
+ * takes all k gradient rows.  Here lanes i < k evaluate the bias on the xi in LDS, and the contracted sweep is seeded from there.
+ *   U(xi) = sum over term[0 .. n_terms) of U_t(xi[cv_t]); several terms may name one CV (a restraint plus two walls); the sums
+ *   over terms run in term order inside one lane.
+ *     CVF_BIAS_HARMONIC    kappa (xi - center)^2 / 2
+ *     CVF_BIAS_UPPER_WALL  kappa (xi - center)^2 / 2 for xi > center, else 0
+ *     CVF_BIAS_LOWER_WALL  kappa (xi - center)^2 / 2 for xi < center, else 0
+ *     CVF_BIAS_LINEAR      kappa xi
+ *     CVF_BIAS_TABLE       a uniform 1-D grid: nodes j = 0 .. n_nodes - 1 at lo + j / inv_h, the pair (U_j, U'_j) at
+ *                          table[tab_off + 2 j]; cubic Hermite interpolation - U is C1 and the force is the exact derivative of
+ *                          the interpolated U; xi on the last node belongs to the last interval; below lo and above the last node
+ *                          U continues linearly with the end node's value and slope.  `table` (device, n_table floats) is read
+ *                          AT LAUNCH TIME: metadynamics or ABF update it in place between launches, a captured graph stays valid.
+ *   cvf_cv_bias_check(bias, k): 1, or 0 with the reason - which names the field - in cvf_last_error(): a known kind, 0 <= cv < k,
+ *     finite kappa, center and lo, and for a table inv_h > 0, n_nodes >= 2, tab_off >= 0 and even, tab_off + 2 n_nodes <= n_table,
+ *     table != NULL; 0 <= n_terms <= CVF_BIAS_MAX_TERMS.  Host arithmetic; every eval below refuses what it refuses.
+ * cvf_md_layout: atom a (0 .. n_coord / 3) of replica b is read from x_all[b x_frame_stride + atom_index[a] atom_stride + c],
+ * c = 0, 1, 2, and the force is ACCUMULATED at the same place of f_all with its own frame stride:
+ *     f_all[...] += - sum_t U_t'(xi) d xi / d x
+ *   atom_index (device, n_coord / 3 entries WITHOUT REPEATS - the caller vouches for it) or NULL for the identity; atom_stride >= 3
+ *   floats per atom.  Each element is touched by exactly one thread; elements of other atoms, the padding floats of a 4-float atom
+ *   and the gaps between frames are neither read nor written.  The three floats of EVERY atom of the CV's group are read and
+ *   written, those whose gradient is an exact 0 included (a -0.0f there becomes +0.0f).  x_all is only read: its frames may
+ *   overlap or repeat (x_frame_stride = 0 broadcasts one frame).  The force frames of a batch must not overlap: with B > 1 the
+ *   caller vouches that f_frame_stride is past the last float of a frame's atoms, as it vouches for "no repeats"; a stride below
+ *   (n_coord / 3 - 1) atom_stride + 3, which no index can fit in, is refused.  A NULL layout pointer means the dense
+ *   [B][n_coord] arrays of cvf_cv_frame_eval (still +=).  With atom_index n_coord must be a multiple of 3 (a CVF_PP_IDENTITY model with another n_coord
+ *   is refused by name).
+ * The four evals take forms A, B and C (_shared) as their namesakes cvf_cv_frame[_large][_shared]_eval do, under the same limits
+ * (the wave kernel keeps 2 k more floats of LDS inside its 64 KiB; the workgroup kernel reuses the alignment's):
+ *   xi_rows [B][k]; u_rows [B] = U; du_rows [B][k] (may be NULL), du_rows[b][i] = sum_{t: cv_t = i} U_t'(xi_i) - minus the
+ *   coefficient the launch used (ABF-style estimators want it); f_all accumulated as above.
+ * One launch; no aux, no scratch, no allocation, no host synchronisation, no atomics; fixed summation orders; a frame's bits do
+ * not depend on B nor on its place in the batch; xi_rows holds the bits of the namesake's, and the force added to a zero-filled
+ * dense f_all those of the namesake's coef form with coef = -du_rows.  Every refusal (the namesake's, the bias check, the layout)
+ * happens before any launch and leaves the outputs untouched; B == 0 returns 0 and writes nothing. */
+#define CVF_BIAS_MAX_TERMS 16
+enum { CVF_BIAS_HARMONIC = 0, CVF_BIAS_UPPER_WALL = 1, CVF_BIAS_LOWER_WALL = 2, CVF_BIAS_LINEAR = 3, CVF_BIAS_TABLE = 4 };
+typedef struct cvf_bias_term {
+  int32_t kind;     /* CVF_BIAS_* */
+  int32_t cv;       /* the CV the term acts on, 0 .. k - 1 */
+  float kappa;      /* not CVF_BIAS_TABLE */
+  float center;     /* harmonic and walls */
+  int32_t tab_off;  /* CVF_BIAS_TABLE: node j's (U_j, U'_j) at table[tab_off + 2 j] */
+  int32_t n_nodes;
+  float lo;         /* position of node 0 */
+  float inv_h;      /* 1 / node spacing */
+} cvf_bias_term;
+typedef struct cvf_bias_desc {
+  int32_t n_terms;
+  int32_t n_table;      /* floats behind `table` */
+  cvf_bias_term term[CVF_BIAS_MAX_TERMS];
+  const float* table;   /* device; NULL when no term is a table */
+} cvf_bias_desc;
+typedef struct cvf_md_layout {
+  const int32_t* atom_index;   /* device [n_coord / 3], or NULL: atom a is the engine's atom a */
+  int32_t atom_stride;         /* floats per atom, >= 3 */
+  int32_t reserved;            /* 0 */
+  int64_t x_frame_stride;      /* floats between the replicas of x_all */
+  int64_t f_frame_stride;      /* floats between the replicas of f_all */
+} cvf_md_layout;
+int cvf_cv_bias_check(const cvf_bias_desc* bias, int k);
+int cvf_cv_frame_bias_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int cvf_cv_frame_bias_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
+                           const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B, float* xi_rows,
+                           float* u_rows, float* du_rows, float* f_all, void* stream);
+int cvf_cv_frame_bias_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int cvf_cv_frame_bias_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                  const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
+                                  float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream);
+int cvf_cv_frame_large_bias_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int cvf_cv_frame_large_bias_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
+                                 const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B, float* xi_rows,
+                                 float* u_rows, float* du_rows, float* f_all, void* stream);
+int cvf_cv_frame_large_bias_shared_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int cvf_cv_frame_large_bias_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                        const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
+                                        float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream);
+
 /* --- K6: Adam (torch.optim.Adam defaults as constructed at core.py:164: betas
  * (0.9,0.999), eps 1e-8, no weight decay, no amsgrad), one launch over the flat buffer.
  * step_count is a device int32 holding the number t of the CURRENT step (>= 1): it is advanced by the
