@@ -300,7 +300,9 @@ BIAS_KINDS = {"harmonic": BIAS_HARMONIC, "upper_wall": BIAS_UPPER_WALL, "lower_w
 class BiasTerm(C.Structure):
     """``cvf_bias_term`` (include/cvf.h)."""
     _fields_ = [("kind", C.c_int32), ("cv", C.c_int32), ("kappa", C.c_float), ("center", C.c_float), ("tab_off", C.c_int32),
-                ("n_nodes", C.c_int32), ("lo", C.c_float), ("inv_h", C.c_float)]
+                ("n_nodes", C.c_int32), ("lo", C.c_float), ("inv_h", C.c_float),
+                # a joint grid on (cv, cv2) where n_nodes2 >= 2 (DESIGN.md section 4.19); n_nodes2 == 0: the 1-D table
+                ("cv2", C.c_int32), ("n_nodes2", C.c_int32), ("lo2", C.c_float), ("inv_h2", C.c_float)]
 
 
 class BiasDesc(C.Structure):
@@ -325,6 +327,19 @@ _SIGNATURES["cvf_cv_frame_large_bias_supported"] = _SIGNATURES["cvf_cv_frame_sup
 _SIGNATURES["cvf_cv_frame_large_bias_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
 _SIGNATURES["cvf_cv_frame_large_bias_shared_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
 _SIGNATURES["cvf_cv_frame_large_bias_shared_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
+
+# hill deposition into a table term on the device (csrc/cv_bias_hills.hip)
+HILL_CHUNK = 64   # CVF_HILL_CHUNK: the hills a node launch stages through LDS at a time
+
+
+class HillDesc(C.Structure):
+    """``cvf_hill_desc`` (include/cvf.h)."""
+    _fields_ = [("term", C.c_int32), ("reserved", C.c_int32), ("height", C.c_float), ("sigma", C.c_float), ("sigma2", C.c_float),
+                ("inv_kdt", C.c_float)]
+
+
+_SIGNATURES["cvf_cv_bias_deposit"] = (C.c_int, [C.POINTER(BiasDesc), C.c_int, C.POINTER(HillDesc), C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None

@@ -310,10 +310,14 @@ def bias_desc(terms, k, device=None):
     ``{"kind": "harmonic" | "upper_wall" | "lower_wall", "cv": i, "kappa": .., "center": ..}`` or ``(kind, i, kappa, center)``;
     ``{"kind": "linear", "cv": i, "kappa": ..}`` or ``("linear", i, kappa)``;
     ``{"kind": "table", "cv": i, "lo": .., "inv_h": .. (or "h": spacing), "u": U at the nodes, "du": U' at the nodes}`` or
-    ``("table", i, lo, h, u, du)``.
+    ``("table", i, lo, h, u, du)``;
+    ``{"kind": "table2d", "cv": i, "cv2": j, "lo": (a, b), "h": (h1, h2) (or "inv_h": ..), "u", "d1", "d2", "d12": arrays [n1, n2]}``:
+    a joint grid ``U(xi_i, xi_j)`` of bicubic Hermite cells.  Both table kinds take ``"n": (n1, n2)``
+    (``"n": n1`` for ``"table"``) in place of the arrays: a zero-filled grid to deposit hills into (:meth:`BiasedCV.deposit`).
 
-    ``table`` is the fp32 tensor (on ``device``; ``None`` without table terms) of all nodes' ``(U_j, U'_j)`` pairs that
-    ``BiasDesc.table`` points to; term ``t``'s pairs start at ``desc.term[t].tab_off``.  ``device=None`` keeps it on the CPU
+    ``table`` is the fp32 tensor (on ``device``; ``None`` without table terms) of all nodes' ``(U_j, U'_j)`` pairs - of a 2-D term
+    the four floats ``(U, d1 U, d2 U, d12 U)`` per node, ``j2`` fastest, from a multiple of 4 floats on - that
+    ``BiasDesc.table`` points to; term ``t``'s nodes start at ``desc.term[t].tab_off``.  ``device=None`` keeps it on the CPU
     (for checks without a GPU: the pointer is then a host pointer, which no launch may take)."""
     import numpy as np
     d = _hip.BiasDesc()
@@ -329,14 +333,37 @@ def bias_desc(terms, k, device=None):
                 raise ValueError(f"bias term {t}: a {kind!r} tuple is {keys}, got {len(term)} entries")
             term = dict(zip(keys, term))
         kind = term["kind"]
+        two_d = kind == "table2d"
+        if two_d:
+            kind = "table"
         if isinstance(kind, str):
             if kind not in _hip.BIAS_KINDS:
-                raise ValueError(f"bias term {t}: kind {kind!r} is none of {sorted(_hip.BIAS_KINDS)}")
+                raise ValueError(f"bias term {t}: kind {kind!r} is none of {sorted(_hip.BIAS_KINDS) + ['table2d']}")
             kind = _hip.BIAS_KINDS[kind]
         e = d.term[t]
         e.kind, e.cv = int(kind), int(term["cv"])
-        if kind == _hip.BIAS_TABLE:
-            u, du = np.asarray(term["u"], dtype=np.float32).reshape(-1), np.asarray(term["du"], dtype=np.float32).reshape(-1)
+        if two_d:
+            if "n" in term:
+                n1, n2 = (int(v) for v in term["n"])
+                nodes = np.zeros((n1, n2, 4), dtype=np.float32)
+            else:
+                four = [np.asarray(term[key], dtype=np.float32) for key in ("u", "d1", "d2", "d12")]
+                if four[0].ndim != 2 or any(a.shape != four[0].shape for a in four):
+                    raise ValueError(f"bias term {t}: u, d1, d2 and d12 are arrays [n1, n2] of one shape, got {[a.shape for a in four]}")
+                nodes = np.stack(four, axis=2)
+            (e.lo, e.lo2), e.cv2 = (float(v) for v in term["lo"]), int(term["cv2"])
+            e.inv_h, e.inv_h2 = (float(v) for v in term["inv_h"]) if "inv_h" in term else (1.0 / float(v) for v in term["h"])
+            if n_table % 4:    # a 2-D node is one 16-byte access
+                pairs.append(np.zeros(4 - n_table % 4, dtype=np.float32))
+                n_table += 4 - n_table % 4
+            e.tab_off, e.n_nodes, e.n_nodes2 = n_table, int(nodes.shape[0]), int(nodes.shape[1])
+            pairs.append(nodes.reshape(-1))
+            n_table += nodes.size
+        elif kind == _hip.BIAS_TABLE:
+            if "n" in term:
+                u = du = np.zeros(int(term["n"]), dtype=np.float32)
+            else:
+                u, du = np.asarray(term["u"], dtype=np.float32).reshape(-1), np.asarray(term["du"], dtype=np.float32).reshape(-1)
             if u.shape != du.shape:
                 raise ValueError(f"bias term {t}: {u.size} values of U and {du.size} of U' at the nodes")
             e.lo = float(term["lo"])
@@ -347,13 +374,50 @@ def bias_desc(terms, k, device=None):
         else:
             e.kappa, e.center = float(term["kappa"]), float(term.get("center", 0.0))
     d.n_table = n_table
-    table = torch.from_numpy(np.concatenate(pairs)) if pairs else None
-    if table is not None:
-        table = table if device is None else table.to(device)
+    table = None
+    if pairs:
+        table = torch.empty(n_table, dtype=torch.float32, device="cpu" if device is None else device)   # (torch's own, aligned storage)
+        table.copy_(torch.from_numpy(np.concatenate(pairs)))
         d.table = table.data_ptr()
     if _hip.lib().cvf_cv_bias_check(d, int(k)) != 1:
         raise ValueError(_hip.lib().cvf_last_error().decode())
     return d, table
+
+
+def _table2d_torch(e, table, a, b):
+    """``(U, dU/da, dU/db)`` of a joint grid term at ``(a, b)``: cvf_bias_term2_eval of csrc/cvf_bias.hpp with torch operators."""
+    n1, n2 = e.n_nodes, e.n_nodes2
+    nodes = table[e.tab_off:e.tab_off + 4 * n1 * n2].to(device=a.device, dtype=a.dtype).reshape(n1, n2, 4)
+
+    def axis(x, lo, inv_h, n):
+        s = (x - lo) * inv_h
+        below, above = ~(s >= 0), s > n - 1
+        j = torch.nan_to_num(s.detach(), nan=0.0).clamp(0, n - 2).floor().long()
+        w = torch.where(below, torch.zeros_like(s), torch.where(above, torch.ones_like(s), s - j))
+        d = torch.where(below, x - lo, torch.where(above, (s - (n - 1)) * (1.0 / inv_h), torch.zeros_like(s)))
+        return j, w, d
+
+    def hermite(w, h, inv_h, u0, d0, u1, d1, diff=None):
+        w2, w3 = w * w, w * w * w
+        diff = u0 - u1 if diff is None else diff       # (taken between neighbouring nodes: inv_h magnifies what it has lost)
+        v = (2.0 * w3 - 3.0 * w2 + 1.0) * u0 + (3.0 * w2 - 2.0 * w3) * u1 + h * ((w3 - 2.0 * w2 + w) * d0 + (w3 - w2) * d1)
+        dv = inv_h * (6.0 * (w2 - w) * diff) + (3.0 * w2 - 4.0 * w + 1.0) * d0 + (3.0 * w2 - 2.0 * w) * d1
+        return v, dv
+
+    j1, x, e1 = axis(a, e.lo, e.inv_h, n1)
+    j2, y, e2 = axis(b, e.lo2, e.inv_h2, n2)
+    h1, h2 = 1.0 / e.inv_h, 1.0 / e.inv_h2
+    c = [[nodes[j1 + i, j2 + j] for j in (0, 1)] for i in (0, 1)]      # the cell's corners
+    line = []
+    for i in (0, 1):     # on node line j1 + i: (U, d2 U) and (d1 U, d12 U) along cv2
+        line.append(hermite(y, h2, e.inv_h2, c[i][0][:, 0], c[i][0][:, 2], c[i][1][:, 0], c[i][1][:, 2])
+                    + hermite(y, h2, e.inv_h2, c[i][0][:, 1], c[i][0][:, 3], c[i][1][:, 1], c[i][1][:, 3]))
+    (p0, q0, r0, s0), (p1, q1, r1, s1) = line
+    pd, qd = hermite(y, h2, e.inv_h2, c[0][0][:, 0] - c[1][0][:, 0], c[0][0][:, 2] - c[1][0][:, 2], c[0][1][:, 0] - c[1][1][:, 0],
+                     c[0][1][:, 2] - c[1][1][:, 2])          # p0 - p1 and q0 - q1 from the corner differences
+    U, U1 = hermite(x, h1, e.inv_h, p0, r0, p1, r1, pd)
+    U2, U12 = hermite(x, h1, e.inv_h, q0, s0, q1, s1, qd)
+    return U + U1 * e1 + U2 * e2 + U12 * (e1 * e2), U1 + U12 * e2, U2 + U12 * e1
 
 
 def bias_torch(desc, table, xi):
@@ -367,6 +431,9 @@ def bias_torch(desc, table, xi):
         d = x - e.center
         if e.kind == _hip.BIAS_LINEAR:
             u, du = e.kappa * x, e.kappa + zero
+        elif e.kind == _hip.BIAS_TABLE and e.n_nodes2 != 0:
+            u, du, du2 = _table2d_torch(e, table, x, xi[:, e.cv2])
+            dU[:, e.cv2] = dU[:, e.cv2] + du2
         elif e.kind == _hip.BIAS_TABLE:
             nodes = table[e.tab_off:e.tab_off + 2 * e.n_nodes].to(device=xi.device, dtype=xi.dtype).reshape(-1, 2)
             last, h = e.n_nodes - 1, 1.0 / e.inv_h
@@ -405,7 +472,10 @@ class BiasedCV(FrameCV):
     ``bc.route`` is ``"frame"`` (one wave per frame), ``"frame-large"`` (``large_frames=True``, one workgroup per frame) or
     ``"three-call"``: ``FrameCV``'s recipe for all k gradient rows, the same term formulas in torch fp32 (:func:`bias_torch`)
     and one contraction - several launches, the same result up to rounding (another summation order, torch's own elementwise
-    arithmetic), for the models the one launch declines."""
+    arithmetic), for the models the one launch declines.
+
+    ``bc.deposit(xi, height, sigma, ...)`` adds metadynamics hills to a table term of ``bc.table`` on the device, from the ``xi`` a
+    call returned; a ``"table"`` or ``"table2d"`` term given by ``"n"`` starts as a zero-filled grid."""
 
     _infix = "_bias"
 
@@ -472,4 +542,35 @@ class BiasedCV(FrameCV):
                 U, dU = bias_torch(self.desc, self.table, xi)
                 Fv[:, self._cols] -= torch.einsum("bk,bkn->bn", dU, D)
         return xi, U, dU
+
+    def deposit(self, xi, height, sigma, term=None, bias_factor=None, kT=None):
+        """Add one Gaussian hill per row of ``xi [B, k]`` (float32 on the device - what a call just returned) to a table term, in
+        ``bc.table``, on the device (``cvf_cv_bias_deposit``): the next call sees it, on every route.
+
+        ``sigma`` is the width, ``(sigma1, sigma2)`` for a ``"table2d"`` term; ``term`` the index of the table term (``None``: the
+        only one).  ``bias_factor`` and ``kT`` together make the deposit well-tempered, ``w = height exp(-V / ((bias_factor - 1)
+        kT))`` with ``V`` the term's own value at the centre before this call.  Returns ``hills [B, 4] = (c1, c2, w, V)``."""
+        import ctypes as C
+        tables = [t for t in range(self.desc.n_terms) if self.desc.term[t].kind == _hip.BIAS_TABLE]
+        if term is None:
+            if len(tables) != 1:
+                raise ValueError(f"term=None needs exactly one table term, the bias has {len(tables)}: name one of {tables}")
+            term = tables[0]
+        if (bias_factor is None) != (kT is None):
+            raise ValueError("bias_factor and kT go together (well-tempered) or are both left out (plain metadynamics)")
+        inv_kdt = 0.0 if kT is None else 1.0 / ((float(bias_factor) - 1.0) * float(kT))
+        s1, s2 = (float(v) for v in sigma) if hasattr(sigma, "__len__") else (float(sigma), 0.0)
+        if not (torch.is_tensor(xi) and xi.dtype == torch.float32 and xi.device == self.device and xi.dim() == 2 and xi.shape[1] == self.k):
+            raise ValueError(f"xi must be a float32 tensor [B, {self.k}] on {self.device}")
+        xi = xi.contiguous()
+        B = int(xi.shape[0])
+        hill = _hip.HillDesc(int(term), 0, float(height), s1, s2, inv_kdt)
+        with torch.cuda.device(self.device):
+            hills = torch.empty(B, 4, device=self.device)
+            rc = _hip.lib().cvf_cv_bias_deposit(C.byref(self.desc), self.k, C.byref(hill), _hip.ptr(xi), B, _hip.ptr(self.table),
+                                                _hip.ptr(hills), _hip.stream())
+        if rc == -1:
+            raise ValueError(_hip.lib().cvf_last_error().decode())
+        _hip.check(rc, "cvf_cv_bias_deposit")
+        return hills
 

@@ -4,7 +4,8 @@
 // text:
 //
 //   frame   atom a of replica b from x_all[b x_frame_stride + atom_index[a] atom_stride + c] (cvf_md_layout; NULL: dense)
-//   seed    once xi is in LDS, lane i < k sums its terms' U_t(xi_i) and U_t'(xi_i) in term order (cvf_bias.hpp), writes du_rows,
+//   seed    once xi is in LDS, lane i < k sums its terms' U_t(xi_i) and U_t'(xi_i) in term order (cvf_bias.hpp; of a joint grid
+//           term on (cv, cv2) lane cv takes U and dU/dxi_cv, lane cv2 dU/dxi_cv2: DESIGN.md section 4.19), writes du_rows,
 //           stores -du_i and its share of U to 2 k LDS floats; behind a barrier thread 0 adds the k shares in index order into
 //           u_rows, and the contracted sweep (coef form: one cotangent row) reads its seed from the LDS row instead of a global coef
 //   force   f_all[b f_frame_stride + atom_index[a] atom_stride + c] += the row, each element by the one thread that owns it
@@ -36,7 +37,7 @@ __device__ __forceinline__ const float* bias_seeds(const cvf_bias_desc& bias, co
                                                    int64_t frame, int k, int idx) {
   if (idx < k) {
     float u, du;
-    cvf_bias_cv_eval(bias, idx, top[idx], &u, &du);
+    cvf_bias_cv_eval(bias, idx, top, &u, &du);   // (the whole row: a joint grid term reads two of its k values)
     spare[idx] = -du;
     spare[k + idx] = u;
     if (md.du_rows != nullptr) md.du_rows[frame * k + idx] = du;

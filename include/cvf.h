@@ -950,6 +950,10 @@ typedef struct cvf_bias_term {
   int32_t n_nodes;
   float lo;         /* position of node 0 */
   float inv_h;      /* 1 / node spacing */
+  int32_t cv2;      /* CVF_BIAS_TABLE with n_nodes2 >= 2: the second CV of a joint grid (below), 0 .. k - 1 and not cv */
+  int32_t n_nodes2; /* 0: the 1-D table, whatever cv2, lo2 and inv_h2 hold; >= 2: nodes along cv2 */
+  float lo2;        /* position of node 0 along cv2 */
+  float inv_h2;     /* 1 / node spacing along cv2 */
 } cvf_bias_term;
 typedef struct cvf_bias_desc {
   int32_t n_terms;
@@ -981,6 +985,51 @@ int cvf_cv_frame_large_bias_shared_supported(const cvf_mlp_desc* mlp, int n_shar
 int cvf_cv_frame_large_bias_shared_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
                                         const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
                                         float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream);
+
+/* --- metadynamics along the CV: joint 2-D grid terms and hill deposition on the device (csrc/cvf_bias.hpp, csrc/cv_bias_hills.hip;
+ * DESIGN.md section 4.19).
+ * A CVF_BIAS_TABLE term with n_nodes2 >= 2 is a joint grid U(xi_cv, xi_cv2) (n_nodes2 == 0: the 1-D table above, bit for bit):
+ *   node (j1, j2), j2 fastest, at (lo + j1 / inv_h, lo2 + j2 / inv_h2) holds the four floats (U, d1 U, d2 U, d12 U) at
+ *   table[tab_off + 4 (j1 n_nodes2 + j2)]; tab_off is a multiple of 4 and `table` 16-byte aligned (a node is one 16-byte access).
+ *   Inside the grid U is the bicubic Hermite interpolant of the cell - the tensor product of the 1-D basis, d_a U scaled by h_a and
+ *   d12 U by h1 h2 - so U is C1 and the two gradient components are the exact gradient of that polynomial.  Outside, with P = xi
+ *   clamped to the grid per axis and d = xi - P:
+ *     U = U(P) + d1U(P) d_1 + d2U(P) d_2 + d12U(P) d_1 d_2,   d1 U = d1U(P) + d12U(P) d_2,   d2 U = d2U(P) + d12U(P) d_1
+ *   (the 1-D rule per axis: C1 across every edge and corner, the force stays the exact gradient).  NaN takes the "below" branch; xi
+ *   on the last node line belongs to the last cell; on a node the node's values come back bit for bit.
+ *   In the launches above lane i < k sums in term order: its 1-D terms; for a 2-D term with cv == i its U and dU/dxi_cv; for a 2-D
+ *   term with cv2 == i only dU/dxi_cv2.  du_rows[b][i] is that sum; u_rows, the sweep and the force are as before.
+ *   cvf_cv_bias_check additionally refuses, naming the field: n_nodes2 == 1 or negative, cv2 outside 0 .. k - 1 or equal to cv, a
+ *   non-finite lo2, inv_h2 not positive and finite, tab_off % 4 != 0, tab_off + 4 n_nodes n_nodes2 > n_table (in 64 bits), a table
+ *   that is not 16-byte aligned.
+ * cvf_cv_bias_deposit adds B Gaussian hills to ONE table term (1-D or 2-D) of `bias`, in place, centred on the xi_rows [B][k] a bias
+ * launch wrote (device):  hill b has the centre c = (xi_b[cv], xi_b[cv2]) and the height
+ *     w_b = height exp(-V_b inv_kdt),   V_b = the TARGET TERM's own U at c (not the whole bias), read through the interpolation above
+ *                                             from the table as it is BEFORE any hill of this call (inv_kdt == 0: w_b = height)
+ *   hills [B][4] (device, written) = (c_1, c_2 (0 in 1-D), w_b, V_b): the caller's HILLS log and reweighting input.  A non-finite
+ *   centre, or a w_b that is not finite (exp overflows on a very negative V_b), gives w_b = 0 and the hill is skipped: no node
+ *   receives NaN.  Every node, at x = lo + (float)j / inv_h per axis in fp32,
+ *   with delta = x - c and G = exp(-(delta_1^2 / sigma^2 + delta_2^2 / sigma2^2) / 2), takes
+ *     U += w G,  d1 U += -w G delta_1 / sigma^2,  d2 U += -w G delta_2 / sigma2^2,  d12 U += w G delta_1 delta_2 / (sigma^2 sigma2^2)
+ *   (1-D: the first two).  Full Gaussians, no cut-off: values and slopes stay the exact derivatives of one smooth function.
+ *   Two launches on `stream` - the heights (one thread per hill), then the nodes (one thread per node: read once, the hills added in
+ *   order b = 0 .. B - 1 in registers, staged through LDS CVF_HILL_CHUNK at a time, written once) - because every height must see the
+ *   table before any workgroup has written to it.  No atomics, no allocation, no host synchronisation; graph-capturable on one stream
+ *   behind the launch that writes xi_rows; the bits do not depend on the launch geometry, and with inv_kdt == 0 one call of B hills
+ *   gives the bits of B calls of one hill each.  Refused before any launch, table and hills untouched: what cvf_cv_bias_check refuses;
+ *   term out of range or no CVF_BIAS_TABLE; height, sigma or (2-D) sigma2 not positive and finite, or so small that 1 / sigma^2
+ *   overflows fp32; inv_kdt negative or not finite;
+ *   table != bias->table; NULL pointers; B < 0.  B == 0 returns 0 and writes nothing. */
+#define CVF_HILL_CHUNK 64
+typedef struct cvf_hill_desc {
+  int32_t term;         /* index of the CVF_BIAS_TABLE term (1-D or 2-D) that receives the hills */
+  int32_t reserved;     /* 0 */
+  float height;         /* w0 > 0 */
+  float sigma, sigma2;  /* widths along cv and cv2 (sigma2 unused in 1-D), > 0 */
+  float inv_kdt;        /* well-tempered: 1 / (k_B dT) = 1 / ((gamma - 1) k_B T) in the units of U; 0 = plain metadynamics */
+} cvf_hill_desc;
+int cvf_cv_bias_deposit(const cvf_bias_desc* bias, int k, const cvf_hill_desc* hill, const float* xi_rows, int64_t B, float* table,
+                        float* hills, void* stream);
 
 /* --- K6: Adam (torch.optim.Adam defaults as constructed at core.py:164: betas
  * (0.9,0.999), eps 1e-8, no weight decay, no amsgrad), one launch over the flat buffer.
