@@ -328,6 +328,20 @@ _SIGNATURES["cvf_cv_frame_large_bias_eval"] = _SIGNATURES["cvf_cv_frame_bias_eva
 _SIGNATURES["cvf_cv_frame_large_bias_shared_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
 _SIGNATURES["cvf_cv_frame_large_bias_shared_eval"] = _SIGNATURES["cvf_cv_frame_bias_eval"]
 
+
+# periodic cells in the bias launches: whole molecules and the virial (csrc/cv_bias.hip, csrc/cvf_cell.hpp)
+class MDCell(C.Structure):
+    """``cvf_md_cell`` (include/cvf.h): ``cell`` is a device pointer to 9 floats per frame (lower-triangular rows), read at launch
+    time; ``virial_rows`` a device pointer to ``[B][9]`` floats; either may be NULL, not both."""
+    _fields_ = [("cell", C.c_void_p), ("cell_frame_stride", C.c_int64), ("virial_rows", C.c_void_p)]
+
+
+for _name in ("cvf_cv_frame_bias", "cvf_cv_frame_bias_shared", "cvf_cv_frame_large_bias", "cvf_cv_frame_large_bias_shared"):
+    _SIGNATURES[_name + "_cell_supported"] = _SIGNATURES["cvf_cv_frame_supported"]
+    _SIGNATURES[_name + "_cell_eval"] = (C.c_int, _SIGNATURES["cvf_cv_frame_bias_eval"][1] + [C.POINTER(MDCell)])
+_SIGNATURES["cvf_md_make_whole"] = (C.c_int, [C.POINTER(MDLayout), C.POINTER(MDCell), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                              C.c_void_p])
+
 # hill deposition into a table term on the device (csrc/cv_bias_hills.hip; DESIGN.md section 4.19)
 HILL_CHUNK = 64   # CVF_HILL_CHUNK: the hills a node launch stages through LDS at a time
 

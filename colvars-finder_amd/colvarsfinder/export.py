@@ -474,6 +474,15 @@ class BiasedCV(FrameCV):
     and one contraction - several launches, the same result up to rounding (another summation order, torch's own elementwise
     arithmetic), for the models the one launch declines.
 
+    Periodic cells: ``bc(X_all, F_all, cell=cell)`` takes the engine's WRAPPED positions and makes the CV's
+    atoms whole inside the launch, along the order of ``atom_index`` (atom j takes the image nearest to the whole atom j - 1: consecutive
+    atoms must lie closer than half the shortest cell height).  ``cell`` is a float32 device tensor ``[9]``, ``[3, 3]`` (one cell for
+    all frames) or ``[B, 9]``, ``[B, 3, 3]``, the lattice vectors as rows in lower-triangular form, read AT LAUNCH TIME (a barostat
+    rescales it in place; an axis with a diagonal entry <= 0 is not periodic).  ``virial=V`` (float32 device ``[B, 9]`` or ``[B, 3, 3]``)
+    is filled with ``V[b, i, j] = sum_a r_a[i] f_a[j]`` over the whole positions and the force just added; it is also taken without
+    a cell, for positions that are whole already.  ``bc.route_cell`` is the route such a call takes (the workgroup launch keeps 4
+    more bytes of LDS per atom).  With ``cell is None and virial is None`` the call is the one above, bit for bit.
+
     ``bc.deposit(xi, height, sigma, ...)`` adds metadynamics hills to a table term of ``bc.table`` on the device, from the ``xi`` a
     call returned; a ``"table"`` or ``"table2d"`` term given by ``"n"`` starts as a zero-filled grid."""
 
@@ -485,6 +494,16 @@ class BiasedCV(FrameCV):
             device = torch.device("cuda", torch.cuda.current_device())
         super().__init__(path_or_cv, device=device, large_frames=large_frames)   # (binds; route and supported from the bias predicates)
         self._bias_eval = {"frame": self._frame_eval, "frame-large": self._large_eval}
+        # the same with a periodic cell and / or the virial (the _cell entry points; their limits differ by the image counts' LDS)
+        import ctypes as C
+        lib, sh = _hip.lib(), "_shared" if self.n_shared > 0 else ""
+        self._cell_eval = {"frame": getattr(lib, f"cvf_cv_frame_bias{sh}_cell_eval"), "frame-large": getattr(lib, f"cvf_cv_frame_large_bias{sh}_cell_eval")}
+        m = self.model
+        ok = getattr(lib, f"cvf_cv_frame_bias{sh}_cell_supported")(C.byref(m.mlp), self._cut, C.byref(m.pp)) == 1
+        self.supported_cell = (ok, None if ok else lib.cvf_last_error().decode())
+        ok_large = getattr(lib, f"cvf_cv_frame_large_bias{sh}_cell_supported")(C.byref(m.mlp), self._cut, C.byref(m.pp)) == 1
+        self.supported_large_cell = (ok_large, None if ok_large else lib.cvf_last_error().decode())
+        self.route_cell = "frame" if ok else ("frame-large" if large_frames and ok_large else "three-call")
         with torch.cuda.device(self.device):
             self.desc, self.table = bias_desc(terms, self.k, self.device)
         self.atom_stride = int(atom_stride)
@@ -517,12 +536,34 @@ class BiasedCV(FrameCV):
             raise ValueError(f"{name}: frames of {per} floats, the CV's atoms reach float {self._extent - 1}")
         return V, B, (int(V.stride(0)) if B > 1 else per)
 
-    def __call__(self, X_all, F_all):
+    def _cell_args(self, cell, virial, B):
+        """(cell tensor or None, its frame stride, virial tensor [B, 9] or None) of a call's ``cell`` and ``virial``."""
+        if self.n_coord % 3 != 0:
+            raise ValueError(f"cell / virial with n_coord = {self.n_coord}: a cell and a virial need frames of whole atoms")
+        stride = 0
+        if cell is not None:
+            cell = torch.as_tensor(cell).to(device=self.device, dtype=torch.float32)
+            if cell.numel() == 9:
+                cell = cell.reshape(9)
+            elif cell.numel() == 9 * B and cell.shape[0] == B:
+                cell, stride = cell.reshape(B, 9), 9
+            else:
+                raise ValueError(f"cell: [9], [3, 3], [{B}, 9] or [{B}, 3, 3] floats are needed, got {tuple(cell.shape)}")
+            cell = cell.contiguous()
+        if virial is not None:
+            if not (torch.is_tensor(virial) and virial.dtype == torch.float32 and virial.device == self.device and virial.is_contiguous()
+                    and virial.numel() == 9 * B and (B == 0 or virial.shape[0] == B)):
+                raise ValueError(f"virial must be a contiguous float32 tensor [{B}, 9] or [{B}, 3, 3] on {self.device}")
+        return cell, stride, virial
+
+    def __call__(self, X_all, F_all, cell=None, virial=None):
         import ctypes as C
         Xv, B, xs = self._frames(X_all, "X_all")
         Fv, Bf, fs = self._frames(F_all, "F_all")
         if B != Bf:
             raise ValueError(f"X_all has {B} frames, F_all {Bf}")
+        if cell is not None or virial is not None:
+            return self._call_cell(Xv, Fv, B, xs, fs, *self._cell_args(cell, virial, B))
         lib, m, k, dev = _hip.lib(), self.model, self.k, self.device
         with torch.cuda.device(dev):
             s = _hip.stream()
@@ -541,6 +582,38 @@ class BiasedCV(FrameCV):
                 self._three_call(x, None, xi, D, s)
                 U, dU = bias_torch(self.desc, self.table, xi)
                 Fv[:, self._cols] -= torch.einsum("bk,bkn->bn", dU, D)
+        return xi, U, dU
+
+    def _call_cell(self, Xv, Fv, B, xs, fs, cell, cell_stride, virial):
+        """The call with a periodic cell and / or the virial, on ``self.route_cell``."""
+        import ctypes as C
+        lib, m, k, dev = _hip.lib(), self.model, self.k, self.device
+        with torch.cuda.device(dev):
+            s = _hip.stream()
+            xi, U, dU = (torch.empty(B, k, device=dev), torch.empty(B, device=dev), torch.empty(B, k, device=dev))
+            if B == 0:
+                return xi, U, dU
+            lay = _hip.MDLayout(self.atom_index.data_ptr() if self.atom_index is not None else None, self.atom_stride, 0, xs, fs)
+            mc = _hip.MDCell(cell.data_ptr() if cell is not None else None, cell_stride, virial.data_ptr() if virial is not None else None)
+            if self.route_cell in self._cell_eval:
+                fn = self._cell_eval[self.route_cell]
+                _hip.check(fn(C.byref(m.mlp), C.c_void_p(m.theta), self._cut, C.byref(m.pp), C.byref(self.desc), C.byref(lay),
+                              C.c_void_p(Xv.data_ptr()), B, _hip.ptr(xi), _hip.ptr(U), _hip.ptr(dU), C.c_void_p(Fv.data_ptr()), s, C.byref(mc)),
+                           fn.__name__)
+            else:     # cvf_md_make_whole (the gather and the chain in one launch), the three calls, the virial from the dense arrays
+                if cell is not None:
+                    x = torch.empty(B, self.n_coord, device=dev)
+                    _hip.check(lib.cvf_md_make_whole(C.byref(lay), C.byref(mc), C.c_void_p(Xv.data_ptr()), self.n_coord // 3, B, _hip.ptr(x), s),
+                               "cvf_md_make_whole")
+                else:
+                    x = Xv[:, self._cols].contiguous()
+                D = torch.empty(B, k, self.n_coord, device=dev)
+                self._three_call(x, None, xi, D, s)
+                U, dU = bias_torch(self.desc, self.table, xi)
+                f = -torch.einsum("bk,bkn->bn", dU, D)
+                Fv[:, self._cols] += f
+                if virial is not None:
+                    virial.view(B, 3, 3).copy_(torch.einsum("bai,baj->bij", x.view(B, -1, 3), f.view(B, -1, 3)))
         return xi, U, dU
 
     def deposit(self, xi, height, sigma, term=None, bias_factor=None, kT=None):
@@ -574,3 +647,59 @@ class BiasedCV(FrameCV):
         _hip.check(rc, "cvf_cv_bias_deposit")
         return hills
 
+
+def make_whole(X, cell, atom_index=None, atom_stride=3, device="cuda"):
+    """The atoms of wrapped frames made whole under a periodic cell, in one launch (``cvf_md_make_whole``; the rule of
+    csrc/cvf_cell.hpp): atom 0 stays, atom j takes the periodic image nearest to the whole atom j - 1, in
+    the order of ``atom_index`` (``None``: all atoms of a frame in their order).  For trajectories read from an engine's wrapped
+    output before training, and what ``BiasedCV``'s ``"three-call"`` route runs first.
+
+    ``X``: ``[B, ...]`` frames whose atoms are ``atom_stride`` floats apart (array or tensor; a float32 tensor on the device is read
+    in place, frames contiguous inside); ``cell``: ``[9]`` / ``[3, 3]`` for all frames or ``[B, 9]`` / ``[B, 3, 3]``, lattice vectors as
+    rows, lower-triangular (an axis with a diagonal entry <= 0 or not finite is not periodic).  Consecutive atoms must lie closer
+    than half the shortest cell height.  Returns the dense float32 device tensor ``[B, n_atoms, 3]``.
+
+    ``device`` (beyond the plain ``make_whole(X, cell, atom_index, atom_stride)``): where host arrays are taken to and the launch
+    runs; leave it at its default unless several GPUs are in use.  ``atom_index`` is range-checked on the host against the frame
+    size, so an index that is a device tensor costs one copy back and a synchronisation per call - pass a list or a CPU tensor in
+    a loop."""
+    import ctypes as C
+    import numpy as np
+    device = _hip.require_gpu(device)
+    X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X).detach().to(device=device, dtype=torch.float32)
+    if X.dim() < 2:
+        raise ValueError("X must be [B, ...] frames")
+    B = int(X.shape[0])
+    per = int(X[0].numel()) if B else 0
+    try:
+        Xv = X.view(B, per)
+    except RuntimeError:
+        Xv = X.reshape(B, per).contiguous()
+    atom_stride = int(atom_stride)
+    if atom_stride < 3:
+        raise ValueError(f"atom_stride = {atom_stride}: an atom has at least 3 floats")
+    idx = None
+    if atom_index is not None:
+        idx = torch.as_tensor(atom_index).reshape(-1).to(torch.int64).cpu()
+        if idx.numel() < 1 or (idx < 0).any() or (B and int(idx.max()) * atom_stride + 3 > per):
+            raise ValueError(f"atom_index: atom numbers inside frames of {per} floats are needed")
+        n_atoms = int(idx.numel())
+        idx = idx.to(device=device, dtype=torch.int32)
+    else:
+        n_atoms = (per - 3) // atom_stride + 1 if per >= 3 else 0
+    cell = torch.as_tensor(np.asarray(cell) if not torch.is_tensor(cell) else cell).to(device=device, dtype=torch.float32)
+    if cell.numel() == 9:
+        cell, stride = cell.reshape(9).contiguous(), 0
+    elif cell.numel() == 9 * B and cell.shape[0] == B:
+        cell, stride = cell.reshape(B, 9).contiguous(), 9
+    else:
+        raise ValueError(f"cell: [9], [3, 3], [{B}, 9] or [{B}, 3, 3] floats are needed, got {tuple(cell.shape)}")
+    out = torch.empty(B, n_atoms, 3, device=device, dtype=torch.float32)
+    if B == 0 or n_atoms == 0:
+        return out
+    with torch.cuda.device(device):
+        lay = _hip.MDLayout(idx.data_ptr() if idx is not None else None, atom_stride, 0, int(Xv.stride(0)) if B > 1 else per, 0)
+        mc = _hip.MDCell(cell.data_ptr(), stride, None)
+        _hip.check(_hip.lib().cvf_md_make_whole(C.byref(lay), C.byref(mc), C.c_void_p(Xv.data_ptr()), n_atoms, B, _hip.ptr(out), _hip.stream()),
+                   "cvf_md_make_whole")
+    return out

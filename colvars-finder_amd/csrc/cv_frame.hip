@@ -11,6 +11,7 @@ struct DenseIO {
   const float* x;
   const float* coef;
   float* gx_rows;
+  static constexpr bool kCell = false;
   __device__ __forceinline__ float load(int64_t frame, int nc, int j) const { return x[frame * nc + j]; }
   __device__ __forceinline__ const float* seeds(float*, const float*, int64_t frame, int k, int) const {
     return coef != nullptr ? coef + frame * k : nullptr;

@@ -34,6 +34,9 @@
 //   const float* IO::seeds(spare, top, frame, k, lane)     once xi = top[0..k) is in LDS: the frame's k seeds of the contracted
 //                                                          sweep (global, or in `spare` behind a barrier); unused for k rows
 //   void         IO::store(frame, kk, nc, e, v)            element e of the frame's [kk][n_coord] gradient
+//   IO::kCell (a compile-time flag): the frame in LDS is made whole first and the gradient image is seen
+//   before the store -  void IO::whole(xs, nc, frame, lane)  in place on the staged frame, every lane, behind the load's barrier;
+//                       void IO::finish(xs, grad, nc, frame, lane)  the one row about to be stored (the virial)
 #pragma once
 #include "cvf_cv_shared.hpp"
 #include "cvf_cv_shared_sweep.hpp"
@@ -77,6 +80,10 @@ __device__ __forceinline__ void cv_frame_body(const cvf_mlp_desc& mlp, const cvf
     for (int j = lane; j < kk * nc; j += CVF_WAVE) gimg[j] = 0.0f;
   }
   lds_barrier();
+  if constexpr (IO::kCell) {
+    io.whole(xs, nc, frame, lane);
+    lds_barrier();
+  }
 
   // ---- alignment: every lane ends with the same R, centroid and Kinv
   float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Kinv[6] = {0, 0, 0, 0, 0, 0};
@@ -193,6 +200,7 @@ __device__ __forceinline__ void cv_frame_body(const cvf_mlp_desc& mlp, const cvf
 
   // ---- coordinate part
   if (identity) {   // d xi / d x = d xi / d r
+    if constexpr (IO::kCell) io.finish(xs, g, nc, frame, lane);
     for (int e = lane; e < kk * nc; e += CVF_WAVE) io.store(frame, kk, nc, e, g[e]);
     return;
   }
@@ -289,6 +297,7 @@ __device__ __forceinline__ void cv_frame_body(const cvf_mlp_desc& mlp, const cvf
     }
   }
   lds_barrier();
+  if constexpr (IO::kCell) io.finish(xs, gimg, nc, frame, lane);
   for (int e = lane; e < kk * nc; e += CVF_WAVE) io.store(frame, kk, nc, e, gimg[e]);
 }
 

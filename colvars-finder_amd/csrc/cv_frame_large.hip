@@ -12,7 +12,7 @@ struct DenseIO {
   const float* coef;
   float* gx_rows;
   int nc;
-  static constexpr bool kByAtom = false;
+  static constexpr bool kByAtom = false, kCell = false;
   __device__ __forceinline__ const float* atom(int64_t frame, int a) const { return x + frame * nc + 3 * a; }
   __device__ __forceinline__ const float* seeds(float*, const float*, int64_t frame, int k, int) const {
     return coef != nullptr ? coef + frame * k : nullptr;

@@ -39,6 +39,12 @@
 //   void         IO::put(rows, nc, ii, j, A, c, v)         coordinate j = 3 A + c of row ii of the pass (VEC4 instances write
 //                                                          float4s through `rows` themselves: dense policies only), or, with
 //   IO::kByAtom: void IO::put_atom(rows, nc, ii, A, v)     the three coordinates of atom A at once, thread = atom
+//   IO::kCell (a compile-time flag): the atoms are read as a whole molecule -
+//     void IO::prologue(words, red, frame, n_atoms, tid)    every atom's summed image triple into n_atoms LDS words, all threads
+//                                                           (red: the moments' LDS, free before the alignment)
+//     V3   IO::whole(words, frame, a)                        atom a at its whole position (what xyz and xyz_c below read)
+//     void IO::finish(red, frame, tid)                       behind the store loop of a pass, all threads (the virial)
+//   `words` lies behind the one row table of the contracted form (lay.rows + 3 n_ref floats in): cvfl_why's `extra` floats.
 #pragma once
 #include "cvf_cv_shared.hpp"
 #include "cvf_cv_shared_sweep.hpp"
@@ -95,8 +101,20 @@ __device__ __forceinline__ void cv_frame_large_body(const cvf_mlp_desc& mlp, con
   const int nc = pp.n_coord, d0 = mlp.dims[0], L = lay.L, k = lay.k, nn = lay.nn;
   const int kk = contracted ? 1 : k;   // cotangent rows of the coordinate part
   constexpr bool aligned = MODE != 0, weighted = MODE == 2;
-  auto xyz = [&](int a) { return atom_xyz(io.atom(frame, a), 0); };
-  auto xyz_c = [&](int a, const Centre& ce) { return centred(io.atom(frame, a), 0, ce); };
+  uint32_t* words = reinterpret_cast<uint32_t*>(lds + lay.rows + 3 * pp.n_ref);   // (kCell only)
+  auto xyz = [&](int a) {
+    if constexpr (IO::kCell) return io.whole(words, frame, a);
+    else return atom_xyz(io.atom(frame, a), 0);
+  };
+  auto xyz_c = [&](int a, const Centre& ce) {
+    if constexpr (IO::kCell) {
+      const V3 p = io.whole(words, frame, a);
+      const float t[3] = {p.x, p.y, p.z};
+      return centred(t, 0, ce);
+    } else {
+      return centred(io.atom(frame, a), 0, ce);
+    }
+  };
   float* a0 = lds + lay.a[0];
   // The tables and the output of the dense write, used last, live in VECTOR registers from here on (the kernel has them to spare):
   // as uniform values they would sit in the scalar registers through every phase before, which are what this kernel runs out of.
@@ -107,6 +125,10 @@ __device__ __forceinline__ void cv_frame_large_body(const cvf_mlp_desc& mlp, con
   float* gx_frame = io.out(frame, kk, nc);
   asm volatile("" : "+v"(t_align), "+v"(t_slot), "+v"(t_ref), "+v"(t_w), "+v"(gx_frame));
   for (int j = tid; j < d0; j += kThreads) a0[j] = 0.0f;
+  if constexpr (IO::kCell) {
+    io.prologue(words, lds + lay.redd, frame, nc / 3, tid);
+    lds_barrier();
+  }
 
   // ---- alignment: every thread ends with the same R, centroid and Kinv
   float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Kinv[6] = {0, 0, 0, 0, 0, 0};
@@ -369,6 +391,7 @@ __device__ __forceinline__ void cv_frame_large_body(const cvf_mlp_desc& mlp, con
         const AtomRef ua = lookup(A);
         for (int ii = 0; ii < ng; ++ii) io.put_atom(gx0, nc, ii, A, grad_of(ii, ua));
       }
+      if constexpr (IO::kCell) io.finish(redf, frame, tid);
     } else {
       for (int j = tid; j < nc; j += kThreads) {
         const int A = j / 3, kc = j - 3 * A;
@@ -385,7 +408,8 @@ __device__ __forceinline__ void cv_frame_large_body(const cvf_mlp_desc& mlp, con
 
 // nullptr and *lay filled, or why the launch declines the model (ns > 0: form C, which the caller has checked with
 // cvf_form_c_why)
-inline const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, LgLayout* lay, int ns = 0) {
+// `extra`: floats of LDS that the launch keeps behind ONE row of the contribution table (a contracted launch's own; the limit counts them)
+inline const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc* pp, LgLayout* lay, int ns = 0, int64_t extra = 0) {
   static thread_local char buf[360];
 #define CVFL_NO(...)                                              \
   do {                                                            \
@@ -454,8 +478,11 @@ inline const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc
   Y.zs = (int)pos; pos += kZs;
   pos = (pos + 3) & ~(int64_t)3;
   Y.rows = (int)pos;
-  const int64_t row = 3 * (int64_t)pp->n_ref, room = kMaxLds / 4 - pos;
+  const int64_t row = 3 * (int64_t)pp->n_ref, room = kMaxLds / 4 - pos - extra;
   const int64_t rpp = room < row ? 0 : (room / row < k ? room / row : k);
+  if (rpp < 1 && extra > 0)
+    CVFL_NO("one frame needs %lld bytes of LDS with one row of the contribution table (n_ref = %d) and %lld bytes of image counts (4 per atom), the workgroup kernel keeps within %d",
+            (long long)(pos + row + extra) * 4, pp->n_ref, (long long)extra * 4, kMaxLds);
   if (rpp < 1)
     CVFL_NO("one frame needs %lld bytes of LDS with one row of the contribution table (n_ref = %d), the workgroup kernel keeps within %d",
             (long long)(pos + row) * 4, pp->n_ref, kMaxLds);
@@ -467,10 +494,10 @@ inline const char* cvfl_why(const cvf_mlp_desc* mlp, int upto, const cvf_pp_desc
 }
 
 inline const char* cvfl_shared_why(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp, LgLayout* lay,
-                                   const char* plain = "cvf_cv_frame_large_eval") {
+                                   const char* plain = "cvf_cv_frame_large_eval", int64_t extra = 0) {
   static thread_local char buf[240];
   const char* why = cvf_form_c_why(mlp, n_shared, plain, buf, sizeof buf);
-  return why != nullptr ? why : cvfl_why(mlp, mlp->n_layers, pp, lay, n_shared);
+  return why != nullptr ? why : cvfl_why(mlp, mlp->n_layers, pp, lay, n_shared, extra);
 }
 
 }  // namespace cvfl

@@ -986,6 +986,60 @@ int cvf_cv_frame_large_bias_shared_eval(const cvf_mlp_desc* mlp, const float* th
                                         const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
                                         float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream);
 
+/* --- periodic cells in the bias launches: whole molecules and the virial (csrc/cv_bias.hip; the rule: csrc/cvf_cell.hpp, host and
+ * device from one text).  An MD engine keeps its atoms wrapped into the periodic cell, so a molecule that
+ * crosses a cell face arrives torn.  The four _cell_eval calls take the arguments of their namesakes plus a cvf_md_cell and make the
+ * CV's atoms whole INSIDE the launch, before the alignment or any feature reads them; the namesakes are unchanged.
+ *   cell: 9 floats per frame, the lattice vectors as rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) (the reduced
+ *     lower-triangular form of OpenMM, GROMACS and LAMMPS), device memory read AT LAUNCH TIME - a barostat rescales it in place and a
+ *     captured graph stays valid; frame b's cell is cell + b cell_frame_stride (0: one cell for all replicas).  An axis whose
+ *     diagonal entry is 0, negative or not finite is not periodic (a slab: cz = 0); the upper triangle is never read.
+ *   rule: atom 0 of the CV's atom order (the order of atom_index) stays where the engine has it; atom j takes the periodic image
+ *     nearest to the whole atom j - 1 (PLUMED's WHOLEMOLECULES), the minimum image taken axis by axis in the order z, y, x with
+ *     n = rint(d / diagonal).  The image counts are summed as integers, so the result does not depend on how the launch associates
+ *     them; the subtraction x_j - (N.x a + N.y b + N.z c) has one form (csrc/cvf_cell.hpp), shared by every kernel and the host; an
+ *     atom whose count is 0 keeps its bits.  Counts saturate at +-511 images per axis.
+ *   precondition: consecutive atoms of the CV lie closer than half the shortest cell height; frames are whole atoms.
+ *   forces: the shift is piecewise constant, so f_all gets the gradient at the whole positions, at the engine's own atom slots.
+ *   virial_rows (optional, [B][9]): virial_rows[b][3 i + j] = sum_a r_a[i] f_a[j], r the whole position the launch used and f the
+ *     force it adds to f_all; a fixed summation order, no atomics, a frame's 9 floats do not depend on B.  The caller applies its
+ *     engine's sign and factor.  virial_rows is also taken with cell == NULL inside the struct: the virial of positions that the
+ *     engine keeps whole, the forces then the namesake's bit for bit.
+ *   refused before any launch, outputs untouched: what the namesake refuses; a NULL cvf_md_cell pointer; n_coord % 3 != 0; a negative
+ *     cell_frame_stride; cell == NULL and virial_rows == NULL together.
+ *   limits: those of the namesakes; the workgroup kernel keeps 4 more bytes of LDS per atom (the summed image counts), which the
+ *     _cell_supported predicates count.
+ * xi_rows, u_rows, du_rows and the force are, bit for bit, those of the namesake on the dense output of cvf_md_make_whole.
+ * cvf_md_make_whole: the same rule stand-alone, one workgroup per frame, any n_atoms: atom a of frame b is read through `layout`
+ *   (NULL: dense [B][3 n_atoms]; f_frame_stride is not used) and written whole to x_whole[b][3 a ..], dense.  cell->cell is needed,
+ *   cell->virial_rows is not used. */
+typedef struct cvf_md_cell {
+  const float* cell;          /* device, 9 floats per frame (lower-triangular rows), or NULL: positions are whole already */
+  int64_t cell_frame_stride;  /* floats between the replicas' cells; 0: one cell for all */
+  float* virial_rows;         /* device [B][9], or NULL */
+} cvf_md_cell;
+int cvf_cv_frame_bias_cell_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int cvf_cv_frame_bias_cell_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
+                                const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B, float* xi_rows,
+                                float* u_rows, float* du_rows, float* f_all, void* stream, const cvf_md_cell* cell);
+int cvf_cv_frame_bias_shared_cell_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int cvf_cv_frame_bias_shared_cell_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                       const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
+                                       float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream,
+                                       const cvf_md_cell* cell);
+int cvf_cv_frame_large_bias_cell_supported(const cvf_mlp_desc* mlp, int upto_layer, const cvf_pp_desc* pp);
+int cvf_cv_frame_large_bias_cell_eval(const cvf_mlp_desc* mlp, const float* theta, int upto_layer, const cvf_pp_desc* pp,
+                                      const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
+                                      float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream,
+                                      const cvf_md_cell* cell);
+int cvf_cv_frame_large_bias_shared_cell_supported(const cvf_mlp_desc* mlp, int n_shared, const cvf_pp_desc* pp);
+int cvf_cv_frame_large_bias_shared_cell_eval(const cvf_mlp_desc* mlp, const float* theta, int n_shared, const cvf_pp_desc* pp,
+                                             const cvf_bias_desc* bias, const cvf_md_layout* layout, const float* x_all, int64_t B,
+                                             float* xi_rows, float* u_rows, float* du_rows, float* f_all, void* stream,
+                                             const cvf_md_cell* cell);
+int cvf_md_make_whole(const cvf_md_layout* layout, const cvf_md_cell* cell, const float* x_all, int64_t n_atoms, int64_t B,
+                      float* x_whole, void* stream);
+
 /* --- metadynamics along the CV: joint 2-D grid terms and hill deposition on the device (csrc/cvf_bias.hpp, csrc/cv_bias_hills.hip;
  * DESIGN.md section 4.19).
  * A CVF_BIAS_TABLE term with n_nodes2 >= 2 is a joint grid U(xi_cv, xi_cv2) (n_nodes2 == 0: the 1-D table above, bit for bit):
