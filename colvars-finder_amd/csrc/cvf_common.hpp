@@ -152,7 +152,10 @@ __host__ __device__ __forceinline__ int x_tile_stride(int nc) { return (nc & 3) 
 
 // `tid` of `nthreads` (a multiple of 64) threads share the work; callers follow with a barrier.
 // `frames` (a multiple of 4) frames per tile: 64, or 16 for the four-lanes-per-frame kernels.
-template <int kBatch = 18>
+// kPlainRagged: the loop of a tile that runs past the batch (its last one) stays as written.  Left to itself the compiler unrolls it
+// four times, integer divisions included - for a caller that holds requested data in registers across the staging (the 16-frame
+// front kernel's ROWS twins) that one cold loop then sets the kernel's register count.
+template <int kBatch = 18, bool kPlainRagged = false>
 __device__ __forceinline__ void load_x_tile(const float* __restrict__ x, int64_t B, int nc, int64_t tile, float* lds,
                                             int tid, int nthreads = CVF_WAVE, int frames = CVF_TILE) {
   const int stride = x_tile_stride(nc);
@@ -213,12 +216,18 @@ __device__ __forceinline__ void load_x_tile(const float* __restrict__ x, int64_t
       }
     }
   } else {
-    for (int e = tid; e < total; e += nthreads) {
+    auto one = [&](const int e) {
       int fr = e / nc;
       int j = e - fr * nc;
       int64_t src = f0 + fr;
       if (src > B - 1) src = B - 1;
       lds[fr * stride + j] = x[src * nc + j];
+    };
+    if constexpr (kPlainRagged) {
+#pragma unroll 1
+      for (int e = tid; e < total; e += nthreads) one(e);
+    } else {
+      for (int e = tid; e < total; e += nthreads) one(e);
     }
   }
 }

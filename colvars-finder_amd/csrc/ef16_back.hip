@@ -205,9 +205,18 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back
     const int64_t frame = t0 * CVF_TILE + fo;
     const bool valid = frame < args.B;
     const float wraw = w[valid ? frame : args.B - 1];
+    // the frame's y of the k nets that exist: a buffer resource on the tile's k rows, the lane's frame as the one lane offset and the
+    // row as the instruction's offset - a row past k lies outside the resource, reads 0 without a request to memory and is not used
+    // (with pointers: eight 64-bit vector addresses, and for j >= k the last row requested again)
     float yb[CVF_MAX_NETS];
+    if constexpr (MULTI) {   // (the multi-tile form as it was: the resource's four scalar registers, live in its loop, cost it spills)
 #pragma unroll
-    for (int j = 0; j < CVF_MAX_NETS; ++j) yb[j] = y_tiled[(t0 * k + (j < k ? j : k - 1)) * CVF_TILE + fo];
+      for (int j = 0; j < CVF_MAX_NETS; ++j) yb[j] = y_tiled[(t0 * k + (j < k ? j : k - 1)) * CVF_TILE + fo];
+    } else {
+      const URows yrows = urows(y_tiled + t0 * k * CVF_TILE, k * CVF_TILE, fo);
+#pragma unroll
+      for (int j = 0; j < CVF_MAX_NETS; ++j) yb[j] = yrows.ld(j * CVF_TILE);
+    }
     float ylag = 0.0f, wlraw = 0.0f;
     if constexpr (!GEN) {
       ylag = y_tiled[((args.T + t0) * k + net) * CVF_TILE + fo];
@@ -433,9 +442,18 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back
         // one half of the contraction of column tile `ct` for the row tiles rt0, rt0 + rstep, ..: A rows from the LDS image
         // `SA`, B rows in registers; columns: features, then the ones (bias) column when `ones`, zeros past it
         // (no MFMA under lane-divergent control flow: operand values are selected per lane, the MFMAs are uniform)
-        auto half0 = [&](f32x4 (&acc)[RTO], const float* SA, const float4 (&b)[4], int ct, int rt0, int rstep, bool ones) {
+        // The rows of a column tile past D - zeros, and the ones (bias) column at D when `ones` - are put into the operand registers
+        // ONCE, when the operand is first used, and only where there are any: a tile that lies below D whole (every tile but the
+        // last; wave-uniform) is used as it was loaded.  (Selected inside half0 / tail0 the choice `i < D ? b : pad` was made per
+        // matrix instruction: 16 selects per row tile and half.)
+        auto pad_rows = [&](float4 (&b)[4], int ct, bool ones) {
+          if (!MULTI && 16 * ct + 16 <= D) return;   // wave-uniform (the multi-tile form selects on every tile: the branch costs its loop two spilled scalar registers)
           const int i = 16 * ct + row16;
           const float pad = (ones && i == D) ? 1.0f : 0.0f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) b[j] = float4{i < D ? b[j].x : pad, i < D ? b[j].y : pad, i < D ? b[j].z : pad, i < D ? b[j].w : pad};
+        };
+        auto half0 = [&](f32x4 (&acc)[RTO], const float* SA, const float4 (&b)[4], int rt0, int rstep) {
 #pragma unroll
           for (int rt = 0; rt < RTO; ++rt) {
             if (rt >= rt0 && (rt - rt0) % rstep == 0) {
@@ -445,10 +463,10 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back
               for (int j = 0; j < 4; ++j) av[j] = a1[4 * j];
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
-                acc[rt] = mfma4(av[j].x, i < D ? b[j].x : pad, acc[rt]);
-                acc[rt] = mfma4(av[j].y, i < D ? b[j].y : pad, acc[rt]);
-                acc[rt] = mfma4(av[j].z, i < D ? b[j].z : pad, acc[rt]);
-                acc[rt] = mfma4(av[j].w, i < D ? b[j].w : pad, acc[rt]);
+                acc[rt] = mfma4(av[j].x, b[j].x, acc[rt]);
+                acc[rt] = mfma4(av[j].y, b[j].y, acc[rt]);
+                acc[rt] = mfma4(av[j].z, b[j].z, acc[rt]);
+                acc[rt] = mfma4(av[j].w, b[j].w, acc[rt]);
               }
             }
           }
@@ -461,29 +479,29 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back
         // TAIL4: the same half for the 1..4 useful rows of row tile 1 as sixteen 4x4x1 blocks (rows_sum_scatter, ef16_common.hpp).
         // The B registers are read as they are: lane (c, q) holds feature 16 ct + c at frames 16 j + 4 q + e, i.e. column lane & 3
         // of block (q, c >> 2); the A operand of that block is rows 16 + (lane & 3) at the same frames.
-        auto tail0 = [&](f32x4& tacc, const float* SA, const float4 (&b)[4], int ct, bool ones) {
-          const int i = 16 * ct + row16;
-          const float pad = (ones && i == D) ? 1.0f : 0.0f;
+        auto tail0 = [&](f32x4& tacc, const float* SA, const float4 (&b)[4]) {
           const float4* a1 = reinterpret_cast<const float4*>(SA + (16 + (lane & 3)) * kPitch + 4 * q);
           float4 av[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) av[j] = a1[4 * j];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            tacc = mfma1(av[j].x, i < D ? b[j].x : pad, tacc);
-            tacc = mfma1(av[j].y, i < D ? b[j].y : pad, tacc);
-            tacc = mfma1(av[j].z, i < D ? b[j].z : pad, tacc);
-            tacc = mfma1(av[j].w, i < D ? b[j].w : pad, tacc);
+            tacc = mfma1(av[j].x, b[j].x, tacc);
+            tacc = mfma1(av[j].y, b[j].y, tacc);
+            tacc = mfma1(av[j].z, b[j].z, tacc);
+            tacc = mfma1(av[j].w, b[j].w, tacc);
           }
         };
         if (wave < CTM) {   // wave-uniform
           f32x4 tacc = {0.0f, 0.0f, 0.0f, 0.0f};
-          half0(acc, SA1, bA, wave, 0, TAIL4 ? RTO : 1, true);
-          if constexpr (TAIL4) tail0(tacc, SA1, bA, wave, true);
+          pad_rows(bA, wave, true);
+          half0(acc, SA1, bA, 0, TAIL4 ? RTO : 1);
+          if constexpr (TAIL4) tail0(tacc, SA1, bA);
           if (wave < extra) request(bA, f_tile, WPB + wave / RTO);   // the extra pair's rows, behind the second half
           if constexpr (GEN) {
-            half0(acc, SA2, bB, wave, 0, TAIL4 ? RTO : 1, false);
-            if constexpr (TAIL4) tail0(tacc, SA2, bB, wave, false);
+            pad_rows(bB, wave, false);
+            half0(acc, SA2, bB, 0, TAIL4 ? RTO : 1);
+            if constexpr (TAIL4) tail0(tacc, SA2, bB);
           }
 #pragma unroll
           for (int rt = 0; rt < (TAIL4 ? 1 : RTO); ++rt) emit_tile(0, D, rt, wave, acc[rt]);
@@ -502,8 +520,12 @@ __global__ __launch_bounds__(256, 4) void ef16_back_kernel(Back16Args args, Back
           if constexpr (GEN) request(bB, q_tile, ct);
 #pragma unroll
           for (int r_ = 0; r_ < RTO; ++r_) acc[r_] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          half0(acc, SA1, bA, ct, rt, RTO, true);
-          if constexpr (GEN) half0(acc, SA2, bB, ct, rt, RTO, false);
+          pad_rows(bA, ct, true);
+          half0(acc, SA1, bA, rt, RTO);
+          if constexpr (GEN) {
+            pad_rows(bB, ct, false);
+            half0(acc, SA2, bB, rt, RTO);
+          }
 #pragma unroll
           for (int r_ = 0; r_ < RTO; ++r_)
             if (r_ == rt) emit_tile(0, D, r_, ct, acc[r_]);

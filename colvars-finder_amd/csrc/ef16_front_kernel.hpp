@@ -65,6 +65,26 @@ __device__ __forceinline__ V3 ef16_feature(const float* my, const int at, const 
   return row_times(centred(my, at, c), R);
 }
 
+// Iteration `it` of a four-lanes-per-frame pass: the lane's atom pb + 4 it (pb = lane & 3, made opaque once per pass by the caller).
+// Three times its index is ONE register per pass (3 pb) and a constant, so the rows of an array at the lane's atoms are one
+// address and immediate offsets of 48 bytes.  Only the last iteration can run past the last atom: there, and only there, the
+// index is clamped - the lane works on a duplicate of atom N - 1 with lv = 0.
+struct AtomSlot {
+  int ac, i3;   // the atom, and three times it
+  float lv;     // 1 / 0 past the last atom
+};
+template <int NIT>
+__device__ __forceinline__ AtomSlot atom_slot(const int pb, const int it, const int N) {
+  // (the iteration's LDS reads stay behind it: all of a pass's reads requested at once cost up to nine registers.  Nothing in the
+  //  language promises this order - the compiler's instruction scheduler does not move memory operations across an `asm volatile`;
+  //  results do not depend on it, only the register counts, which tests/test_ef16_front_lean_host.py holds against the parent's)
+  asm volatile("");
+  const int at = pb + 4 * it;
+  if (it < NIT - 1) return AtomSlot{at, 3 * pb + 12 * it, 1.0f};
+  const int ac = at >= N ? N - 1 : at;
+  return AtomSlot{ac, 3 * ac, at >= N ? 0.0f : 1.0f};
+}
+
 // ROWS: the instance starts from what a previous visit of its resident batch left in global memory (cvf_ef16_align_rows_tile)
 // instead of deriving it again - the alignment rows (`rows`, see kRowsUnit) and the feature tile (`feat_tiled`, here an INPUT):
 //   * wave 0's covariance + solve and the barrier behind it, the feature phase and its barrier, and the tile's store at the
@@ -232,7 +252,7 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       if (tid + nthreads < n4) dst[tid + nthreads] = cx1;
       for (int v = tid + 2 * nthreads; v < n4; v += nthreads) dst[v] = xsrc[v];
     } else {
-      load_x_tile<6>(x, B, nc, unit, xt, tid, nthreads, kU);
+      load_x_tile<3, true>(x, B, nc, unit, xt, tid, nthreads, kU);   // (behind the requests above: see kPlainRagged)
     }
     if (tid < nt) refL[tid] = tv;
     for (int j = tid + nthreads; j < nt; j += nthreads) refL[j] = j < 3 * nal ? pp.ref_c[j] : (a != nullptr ? a[j - 3 * nal] : 0.0f);
@@ -299,6 +319,9 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       fi[1] = al.y;
       fi[2] = al.z;
     }
+    // (the rest of the frame's row up to the end of the last k-step, at most three floats: layer 0 reads rows 4 s + q without a
+    //  clamp, and a row past D meets a zero weight AND a zero this block wrote)
+    if (wave == 0 && D + p < 4 * S) featI[f * kImgP + D + p] = 0.0f;
     lds_barrier();
   }
   CVF_STAMP(23);
@@ -330,9 +353,8 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     }
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      const int kf = 4 * (s < S ? s : S - 1) + q;
       if constexpr (ROWS) bf[s] = bf0[s];
-      else bf[s] = fr[kf < D ? kf : D - 1];   // rows past D meet zero weights
+      else bf[s] = fr[q + 4 * s];   // (one address and immediate offsets; rows past D: zeros meet zero weights; steps past S: inside the frame's row, unused)
     }
     HFrag<H> hf[NH > 1 ? NH - 1 : 1];
 #pragma unroll
@@ -382,7 +404,7 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     // (all four q groups hold the same value and store it to the same place: no lane-divergent branch around a store,
     //  behind which the compiler could no longer count the outstanding memory operations and would drain them all)
     yL[net * kU + col] = yv;
-    y_tiled[(tile * k + net) * CVF_TILE + kU * sub + col] = yv;
+    urows(y_tiled + (tile * k + net) * CVF_TILE + kU * sub, kU, col).st(0, yv);   // (the unit's 16 values of this net: a uniform base and the lane's column)
   }
   CVF_STAMP(25);
   if constexpr (kTransfer) {   // transfer-operator mode: y, h_1..h_NH and the feature tile are all the backward pass needs
@@ -468,15 +490,16 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     // The lane, duplicate-atom and mask conventions are those of the general passes.
     const float* Fl = featI + f * kImgP;
     V3 gsum = v3(0.0f, 0.0f, 0.0f), tau = v3(0.0f, 0.0f, 0.0f);
+    int pb = p;
+    asm volatile("" : "+v"(pb));   // (opaque, once per pass: the pass's addresses are formed here, not hoisted and kept across the passes)
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));   // (opaque: the atom's addresses are formed here, not hoisted and kept across the passes)
+      const AtomSlot sl = atom_slot<NIT>(pb, it, N);
       const bool last = it == NIT - 1;
-      const int ac = (last && at >= N) ? N - 1 : at;
-      const float lv = (last && at >= N) ? 0.0f : 1.0f;
-      gv[it] = v3(Ul[3 * ac], Ul[3 * ac + 1], Ul[3 * ac + 2]);
-      const V3 fb = v3(Fl[3 * ac], Fl[3 * ac + 1], Fl[3 * ac + 2]);
+      const int i3 = sl.i3;
+      const float lv = sl.lv;
+      gv[it] = v3(Ul[i3], Ul[i3 + 1], Ul[i3 + 2]);
+      const V3 fb = v3(Fl[i3], Fl[i3 + 1], Fl[i3 + 2]);
       const V3 gm = last ? lv * gv[it] : gv[it];
       gsum = gsum + gm;
       tau.x = fmaf(gm.y, fb.z, fmaf(-gm.z, fb.y, tau.x));
@@ -494,23 +517,24 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     const V3 gbar = inv_nal * gsum;
     float E = 0.0f;
     V3 usum = v3(0.0f, 0.0f, 0.0f), tau2 = v3(0.0f, 0.0f, 0.0f);
+    pb = p;
+    asm volatile("" : "+v"(pb));
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));
+      const AtomSlot sl = atom_slot<NIT>(pb, it, N);
       const bool last = it == NIT - 1;
-      const int ac = (last && at >= N) ? N - 1 : at;
-      const float lv = (last && at >= N) ? 0.0f : 1.0f;             // alive (not a duplicate): counts in the sums
+      const int ac = sl.ac;
+      const float lv = sl.lv;                                        // alive (not a duplicate): counts in the sums
       const float ma = ALLAL ? 1.0f : (ac < nal ? 1.0f : 0.0f);      // align atom
-      const int ar_ = ALLAL ? ac : (ac < nal ? ac : 0);
-      V3 rf = v3(refL[3 * ar_], refL[3 * ar_ + 1], refL[3 * ar_ + 2]);
+      const int r3 = ALLAL ? sl.i3 : (ac < nal ? sl.i3 : 0);
+      V3 rf = v3(refL[r3], refL[r3 + 1], refL[r3 + 2]);
       if (!ALLAL) rf = ma * rf;
       const V3 sh = ALLAL ? gbar : ma * gbar;
       V3 G;
       G.x = fmaf(s.y, rf.z, fmaf(-s.z, rf.y, gv[it].x - sh.x));
       G.y = fmaf(s.z, rf.x, fmaf(-s.x, rf.z, gv[it].y - sh.y));
       G.z = fmaf(s.x, rf.y, fmaf(-s.y, rf.x, gv[it].z - sh.z));
-      const V3 u = aL[3 * ac] * G;
+      const V3 u = aL[sl.i3] * G;
       gv[it] = u;
       const bool masked = last || !ALLAL;                            // (compile-time)
       const V3 ue = last ? lv * u : u;
@@ -527,27 +551,27 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     tau2 = v3(quad_sumf16(tau2.x), quad_sumf16(tau2.y), quad_sumf16(tau2.z));
     const V3 rsum = v3(rsL[0], rsL[1], rsL[2]);   // sum of the reference over the align atoms (the fp32 residue of its centring)
     eL[net * kU + f] = E;   // (the four lanes of a frame hold the same sum and store it to the same place)
-    e_tiled[(tile * k + net) * CVF_TILE + kU * sub + f] = E;
+    urows(e_tiled + (tile * k + net) * CVF_TILE + kU * sub, kU, f).st(0, E);
     const V3 ubar = inv_nal * usum;
     tau2.x = fmaf(-rsum.y, ubar.z, fmaf(rsum.z, ubar.y, tau2.x));
     tau2.y = fmaf(-rsum.z, ubar.x, fmaf(rsum.x, ubar.z, tau2.y));
     tau2.z = fmaf(-rsum.x, ubar.y, fmaf(rsum.y, ubar.x, tau2.z));
     const V3 om = sym_times(Kinv, tau2);
     CVF_STAMP(31);
+    pb = p;
+    asm volatile("" : "+v"(pb));
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));
-      const int ac = (it == NIT - 1 && at >= N) ? N - 1 : at;
-      const V3 fb = v3(Fl[3 * ac], Fl[3 * ac + 1], Fl[3 * ac + 2]);
+      const int i3 = atom_slot<NIT>(pb, it, N).i3;
+      const V3 fb = v3(Fl[i3], Fl[i3 + 1], Fl[i3 + 2]);
       V3 qv;
       qv.x = fmaf(fb.y, om.z, fmaf(-fb.z, om.y, gv[it].x - ubar.x));
       qv.y = fmaf(fb.z, om.x, fmaf(-fb.x, om.z, gv[it].y - ubar.y));
       qv.z = fmaf(fb.x, om.y, fmaf(-fb.y, om.x, gv[it].z - ubar.z));
       gv[it] = qv;   // (kept: q leaves for global memory at the very end, behind every load of this kernel)
-      Ul[3 * ac] = qv.x;
-      Ul[3 * ac + 1] = qv.y;
-      Ul[3 * ac + 2] = qv.z;
+      Ul[i3] = qv.x;
+      Ul[i3 + 1] = qv.y;
+      Ul[i3 + 2] = qv.z;
     }
     } else {
     float R[9];
@@ -557,19 +581,20 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     // pass 1: sum_b g_b and M = sum_b (x_b - c) (x) g_b
     V3 gsum = v3(0.0f, 0.0f, 0.0f);
     Outer3 Mo = {{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}}, {0.0f, 0.0f, 0.0f}};
+    int pb = p;
+    asm volatile("" : "+v"(pb));   // (opaque, once per pass: the pass's addresses are formed here, not hoisted and kept across the passes)
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));   // (opaque: the atom's addresses are formed here, not hoisted and kept across the passes)
+      const AtomSlot sl = atom_slot<NIT>(pb, it, N);
       const bool last = it == NIT - 1;           // (compile-time: the only iteration that can run past the last atom)
-      const int ac = (last && at >= N) ? N - 1 : at;
-      const float lv = (last && at >= N) ? 0.0f : 1.0f;
+      const int i3 = sl.i3;
+      const float lv = sl.lv;
       // (a lane past the last atom works on a DUPLICATE of atom N - 1 - masked out of every sum, but carried through so that
       //  it computes and stores the same u and q as that atom's owner: no lane-divergent branch around the stores)
-      gv[it] = v3(Ul[3 * ac], Ul[3 * ac + 1], Ul[3 * ac + 2]);
+      gv[it] = v3(Ul[i3], Ul[i3 + 1], Ul[i3 + 2]);
       const V3 gm = last ? lv * gv[it] : gv[it];
       gsum = gsum + gm;
-      outer_acc(Mo, centred(my, ac, c), gm);
+      outer_acc(Mo, centred(my + i3, 0, c), gm);
     }
     CVF_STAMP(27);
     gsum = v3(quad_sumf16(gsum.x), quad_sumf16(gsum.y), quad_sumf16(gsum.z));
@@ -602,23 +627,25 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     f2 usum_xy = {0.0f, 0.0f};
     float usum_z = 0.0f;
     Outer3 dHo = {{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}}, {0.0f, 0.0f, 0.0f}};
+    pb = p;
+    asm volatile("" : "+v"(pb));
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));   // (opaque: the atom's addresses are formed here, not hoisted and kept across the passes)
+      const AtomSlot sl = atom_slot<NIT>(pb, it, N);
       const bool last = it == NIT - 1;
-      const int ac = (last && at >= N) ? N - 1 : at;
-      const float lv = (last && at >= N) ? 0.0f : 1.0f;             // alive (not a duplicate): counts in the sums
+      const int ac = sl.ac, i3 = sl.i3;
+      const float lv = sl.lv;                                        // alive (not a duplicate): counts in the sums
       const float ma = ALLAL ? 1.0f : (ac < nal ? 1.0f : 0.0f);      // align atom: carries the rotation's and the centroid's derivative
-      const int ar_ = ALLAL ? ac : (ac < nal ? ac : 0);
-      V3 rf = v3(refL[3 * ar_], refL[3 * ar_ + 1], refL[3 * ar_ + 2]);
+      const int r3 = ALLAL ? i3 : (ac < nal ? i3 : 0);
+      V3 rf = v3(refL[r3], refL[r3 + 1], refL[r3 + 2]);
       if (!ALLAL) rf = ma * rf;
       f2 Gxy = ALLAL ? f2{-shift.x, -shift.y} : f2{-ma * shift.x, -ma * shift.y};
       float Gz = ALLAL ? -shift.z : -ma * shift.z;
       mat_times_acc(Rc, gv[it], Gxy, Gz);
       mat_times_acc(Zc, rf, Gxy, Gz);
-      const f2 uxy = f2{aL[3 * ac], aL[3 * ac + 1]} * Gxy;
-      const float uz = aL[3 * ac + 2] * Gz;
+      asm volatile("");   // (the coefficients' reads behind G: see atom_slot)
+      const f2 uxy = f2{aL[i3], aL[i3 + 1]} * Gxy;
+      const float uz = aL[i3 + 2] * Gz;
       gv[it] = v3(uxy.x, uxy.y, uz);
       const bool masked = last || !ALLAL;                            // (compile-time)
       const float m = ma * lv;
@@ -638,7 +665,7 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
 #pragma unroll
     for (int i = 0; i < 9; ++i) dH[i] = quad_sumf16(dH[i]);
     eL[net * kU + f] = E;   // (the four lanes of a frame hold the same sum and store it to the same place)
-    e_tiled[(tile * k + net) * CVF_TILE + kU * sub + f] = E;
+    urows(e_tiled + (tile * k + net) * CVF_TILE + kU * sub, kU, f).st(0, E);
     const V3 ubar = inv_nal * usum;
     dH[0] -= ubar.x * rsum.x; dH[1] -= ubar.x * rsum.y; dH[2] -= ubar.x * rsum.z;
     dH[3] -= ubar.y * rsum.x; dH[4] -= ubar.y * rsum.y; dH[5] -= ubar.y * rsum.z;
@@ -661,27 +688,32 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     // pass 3: q_b = (u_b - ubar) R + (x_b - c) dR  -> in place of g, this wave's image (the B operand of s = W_1 q below)
     CVF_STAMP(31);
     const MatRows Rr = mat_rows(R), dRr = mat_rows(dR);
+    pb = p;
+    asm volatile("" : "+v"(pb));
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));   // (opaque: the atom's addresses are formed here, not hoisted and kept across the passes)
-      const int ac = (it == NIT - 1 && at >= N) ? N - 1 : at;
+      const int i3 = atom_slot<NIT>(pb, it, N).i3;
       f2 qxy = {0.0f, 0.0f};
       float qz = 0.0f;
       row_times_acc(Rr, gv[it] - ubar, qxy, qz);
-      row_times_acc(dRr, centred(my, ac, c), qxy, qz);
+      row_times_acc(dRr, centred(my + i3, 0, c), qxy, qz);
       gv[it] = v3(qxy.x, qxy.y, qz);   // (kept: q leaves for global memory at the very end, behind every load of this kernel)
-      Ul[3 * ac] = qxy.x;
-      Ul[3 * ac + 1] = qxy.y;
-      Ul[3 * ac + 2] = qz;
+      Ul[i3] = qxy.x;
+      Ul[i3 + 1] = qxy.y;
+      Ul[i3 + 2] = qz;
     }
     }   // (general metric)
     CVF_STAMP(32);
     asm volatile("" ::: "memory");   // (not earlier: 36 more live registers during the passes spill, and a spill's reload
                                      //  drains every outstanding store)
+    // (S opaque from here on: the row offsets of the fragments and the k-step tests below are scalar arithmetic of their own.  Shared
+    //  with the head's request of the same rows and with layer 0's loop, the 36 offsets and the `s < S` masks were formed once,
+    //  kept across the whole kernel and spilled into lanes of a vector register - a v_readlane and its wait states per use)
+    int Sq = S;
+    asm volatile("" : "+s"(Sq));
 #pragma unroll
     for (int s_ = 0; s_ < SMAX; ++s_) {
-      const int se = s_ < S ? s_ : S - 1;
+      const int se = s_ < Sq ? s_ : Sq - 1;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) f0b[s_][rt] = pk.ld(L.f0() + (se * RT + rt) * 64);
     }
@@ -691,12 +723,16 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       Vec<H, 1> sv0;
       init_bias<H, 1>(sv0, nullptr, q);
-      const float* qr = gI + col * kImgP;
+      // (one address and the k-step as the read's immediate offset, no clamp: a row past D of the last k-step, 4 s + q <= 4 S - 1,
+      //  holds what this wave's g tile put there above - the 16-byte writes cover the row up to 4 S - 1, the passes replace
+      //  what lies below D only - and meets a zero weight, as the clamped row did.  That value is a zero because the rows past D
+      //  of the T0 fragments are zero, like those of F0: cvf_ef_pack clears the packed buffer before it scatters, and so must
+      //  whoever else fills it - a NaN there would reach s through 0 x NaN)
+      const float* qr = gI + col * kImgP + q;
 #pragma unroll
       for (int s = 0; s < SMAX; ++s) {
-        if (s < S) {   // wave-uniform
-          const int kf = 4 * s + q;
-          const float b = qr[kf < D ? kf : D - 1];
+        if (s < Sq) {   // wave-uniform
+          const float b = qr[4 * s];
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) sv0.v[rt][0] = mfma4(f0b[s][rt], b, sv0.v[rt][0]);
         }
@@ -706,15 +742,22 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
     }
     CVF_STAMP(33);
     // ---- q -> the tiled hand-off (the first layer's weight-gradient operand of the backward kernel)
-    float* qt = q_tiled + (tile * k + net) * (int64_t)D * CVF_TILE + kU * sub + f;
+    //      (as the hand-off rows: a buffer resource on this (tile, net, unit)'s columns, ONE lane offset - row 3 p, frame f - and
+    //       the rows of the lane's further atoms as scalar offsets; the clamped last atom has a lane offset of its own.  With
+    //       pointers every store formed a 64-bit address in a register pair)
+    const int q_floats = D * CVF_TILE - kU * sub;
+    const __amdgpu_buffer_rsrc_t qres =
+        __builtin_amdgcn_make_buffer_rsrc(q_tiled + (tile * k + net) * (int64_t)D * CVF_TILE + kU * sub, 0, q_floats * 4, 0x00020000);
+    int pb = p;
+    asm volatile("" : "+v"(pb));
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      int at = p + 4 * it;
-      asm volatile("" : "+v"(at));
-      const int ac = (it == NIT - 1 && at >= N) ? N - 1 : at;
-      qt[(3 * ac) * CVF_TILE] = gv[it].x;
-      qt[(3 * ac + 1) * CVF_TILE] = gv[it].y;
-      qt[(3 * ac + 2) * CVF_TILE] = gv[it].z;
+      const bool last = it == NIT - 1;
+      const URows qt{qres, ((last ? atom_slot<NIT>(pb, it, N).i3 : 3 * pb) * CVF_TILE + f) * 4};
+      const int row = last ? 0 : 12 * it;
+      qt.st(row * CVF_TILE, gv[it].x);
+      qt.st((row + 1) * CVF_TILE, gv[it].y);
+      qt.st((row + 2) * CVF_TILE, gv[it].z);
     }
   }
   CVF_STAMP(34);
@@ -730,6 +773,26 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
   }
   CVF_STAMP(29);
   if (partial == nullptr) return;   // (uniform) large batches: the caller reduces y / E with cvf_ef_stats
+  // wave 0: where its registers of the two matrix results below go in the unit's row - the byte offset of statistic t of this unit,
+  // t * G + unit (G = the launch's units, its rows; at most kMaxRows16 where the launch is given `partial`, and t < 170: 32 bits
+  // and 24-bit products), or an offset past the end of the rows for a register that holds nothing: the buffer store drops it, as the
+  // backward launch's dead tile entries are dropped - no lane-divergent branch around a store.  They depend on the lane, k and the launch alone and are
+  // formed HERE, in front of the barrier at which the wave waits for the others anyway; behind the matrix instructions they
+  // were the tail of every block (64-bit products and adds per store, after the other waves had left).
+  //   D1 (row ri, column cj): (0, 0) -> W; (0, j) -> S1_j; (i, j), 1 <= i <= j <= k -> S2 pair (i-1, j-1) in row-major i <= j order
+  //   D2: (ri < k, 0) -> E_ri
+  constexpr int kDeadRow = 0x7fff0000;   // (positive, and far past 170 rows of at most 16 384 doubles)
+  int o1[4], o2[4];
+  if (wave == 0) {
+    const int cj = lane & 15, G = (int)units_x, u = (int)unit;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ri = (lane >> 4) + 4 * r, a_ = ri - 1;
+      const int t = ri == 0 ? cj : 1 + k + __mul24(a_, k) - (__mul24(a_, a_ - 1) >> 1) + (cj - ri);
+      o1[r] = (ri <= cj && cj <= k) ? (__mul24(t, G) + u) * 8 : kDeadRow;
+      o2[r] = (cj == 0 && ri < k) ? (__mul24(1 + k + CVF_NPAIR(k) + ri, G) + u) * 8 : kDeadRow;
+    }
+  }
   lds_barrier();                    // y and E of every net are in LDS
 
   // ---- wave 0: this unit's row of the batch sums [W | S1(k) | S2(i<=j) | E(k)] in fp64 on the matrix cores: with the frames
@@ -757,21 +820,14 @@ __global__ __launch_bounds__(1024, 4) void ef16_front_kernel(cvf_mlp_desc mlp, c
       d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, d1, 0, 0, 0);
       d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b, d2, 0, 0, 0);
     }
-    // C/D of the f64 form: column = lane & 15, row = (lane >> 4) + 4 r
-    const int cj = lane & 15;
-    const int64_t G = units_x;   // rows of the launch = its units
+    // C/D of the f64 form: column = lane & 15, row = (lane >> 4) + 4 r - to the offsets formed in front of the barrier
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const __amdgpu_buffer_rsrc_t pres = __builtin_amdgcn_make_buffer_rsrc(partial, 0, __mul24(1 + 2 * k + np, (int)units_x) * 8, 0x00020000);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int ri = (lane >> 4) + 4 * r;
-      // D1: (0, 0) -> W; (0, j) -> S1_j; (i, j), 1 <= i <= j <= k -> S2 pair (i-1, j-1) in row-major i <= j order
-      int t = -1;
-      if (ri == 0 && cj <= k) t = cj;
-      else if (ri >= 1 && ri <= cj && cj <= k) {
-        const int a_ = ri - 1, b_ = cj - 1;
-        t = 1 + k + a_ * k - (a_ * (a_ - 1)) / 2 + (b_ - a_);
-      }
-      if (t >= 0) partial[t * G + unit] = d1[r];
-      if (cj == 0 && ri < k) partial[(1 + k + np + ri) * G + unit] = d2[r];
+      const double v1 = d1[r], v2 = d2[r];   // (by value: bit casts of vector elements)
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v1), pres, o1[r], 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v2), pres, o2[r], 0, 0);
     }
   }
   CVF_STAMP(30);
